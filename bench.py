@@ -30,7 +30,15 @@ configs[3] (32 queries x 4096 templates sharded over the GPUs), each with its ow
 of `--templates` templates per GPU in `--bank-dtype` (default: BASELINE configs[4]'s per-GPU slice, 32 queries x 1024 fp16
 templates); for N>1 every rank scores its slice, the (B, N/G) scores are all-gathered over RCCL and ranked.
 
-Extra legs on rank 0 at N=1 (outside the timed region):
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`value`, `ms_per_step` = milliseconds per timed step).
+`--dump-outputs DIR` then writes what the last timed step returned to its caller as DIR/<name>.npy (float32; integer indices as float64):
+`sim` and `idx` (scores and top-5), and `bank` (the template embeddings; rank 0's slice for N>1; --scoring-only has no bank output);
+an array larger than its share of 64 MB is replaced by a fixed, seeded sample of its rows, `<name>_rows.npy` holding their indices.
+Inputs and weights are seeded, so two builds of the project can be compared output for output.
+`--full` adds everything else after the timed steps: `value_unpipelined`, `scaling_lines` and, on rank 0 at N=1, the legs below
+(`--extras` picks some of them, `--skip-extras` none).
+
+Extra legs of --full on rank 0 at N=1 (outside the timed region):
   roofline      the dominant kernel of the step, conv3x3_halo_kernel (the 3x3 convs: 45 of the U-Net's 83 implicit-GEMM launches,
                 ~two thirds of the step): `achieved` / `frac` (= `algorithmic_frac`) = multiply-adds x2 its launches EXECUTE, once per
                 product, / their summed duration (HIP events around every launch on the launch stream) vs the 2.5 PFLOP/s dense
@@ -341,6 +349,33 @@ def parity_record(a, dev, batch, bench_model, bench_sim, bench_idx, bench_ms, sp
     return rec
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy, float32 (integer arrays as float64: exact for any index).  The arrays share
+    DUMP_LIMIT_BYTES in the order given; one larger than its share keeps a fixed, seeded sample of its rows (the leading two axes, e.g.
+    (query, template) of a bank) in ascending order, and out_dir/<name>_rows.npy holds the row numbers of the flattened leading axes."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    header = 1024                                   # per-file allowance for the .npy header (128 bytes for these shapes)
+    left = DUMP_LIMIT_BYTES
+    for i, (name, t) in enumerate(arrays.items()):
+        t = t.detach().as_subclass(torch.Tensor)
+        t = t.to("cpu", torch.float64 if not t.is_floating_point() else torch.float32)
+        share = left // (len(arrays) - i) - header
+        if t.numel() * t.element_size() > share:
+            lead = t.shape[:2] if t.dim() > 2 else t.shape
+            flat = t.reshape(-1, t[(0,) * len(lead)].numel())
+            keep = max(1, (share - header) // (flat.shape[1] * t.element_size() + 8))
+            rows = torch.randperm(flat.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = flat[rows]
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.double().numpy())
+            left -= rows.numel() * 8 + header
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.contiguous().numpy())
+        left -= t.numel() * t.element_size() + header
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -361,11 +396,18 @@ def main():
                          "MFMA, the parity mode.  All five are timed in the `parity` record.")
     ap.add_argument("--bank-dtype", default=None, choices=["bf16", "f32", "f16"], help="template-bank storage (default: --dtype; f16 for --scoring-only)")
     ap.add_argument("--scoring-only", action="store_true", help="time scoring + top-5 on a resident bank (SURVEY 8(d) metric (i))")
-    ap.add_argument("--skip-extras", action="store_true", help="skip roofline / cpu_baseline legs")
-    ap.add_argument("--extras", default="scaling,roofline,parity,scoring,cpu", help="comma list of the extra legs to run (scaling, roofline, parity, scoring, cpu)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, run the extra legs too (unpipelined schedule, scaling lines, roofline, "
+                                                         "parity over all modes, scoring roofline, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--skip-extras", action="store_true", help="with --full: skip every extra leg (a plain run has none)")
+    ap.add_argument("--extras", default=None, help="with --full: comma list of the extra legs to run (scaling, roofline, parity, scoring, cpu; default all)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--two-calls", action="store_true", help="generate_templates then retrieval as two calls (no stream overlap)")
     ap.add_argument("--no-pipeline", action="store_true", help="each step's encoder passes wait for the previous step (PoseConditional.pipeline_encoders off)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.extras is not None and not a.full:
+        ap.error("--extras selects legs of --full: pass --full too")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -428,16 +470,16 @@ def main():
         def step():
             if a.two_calls:                      # the reference's literal call sequence (model.py:313,323)
                 bank, _, _ = model.generate_templates(reference, poses, None)
-                return model.retrieval(query, bank)
-            sim, idx, _ = model.generate_and_retrieve(query, reference, poses)   # same values, query encoder on a side stream
-            return sim, idx
+                sim, idx = model.retrieval(query, bank)
+                return sim, idx, bank
+            return model.generate_and_retrieve(query, reference, poses)   # same values, query encoder on a side stream
         for _ in range(warmup):
-            sim, idx = step()
+            sim, idx, bank = step()
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            sim, idx = step()
+            sim, idx, bank = step()
         torch.cuda.synchronize()
         barrier()
         dt = time.perf_counter() - t0
@@ -445,11 +487,14 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t)
-        return {"batch": batch, "step": step, "sim": sim, "idx": idx, "dt": dt, "hyp": batch_size * templates_total,
+        return {"batch": batch, "step": step, "sim": sim, "idx": idx, "bank": bank, "dt": dt, "hyp": batch_size * templates_total,
                 "value": batch_size * templates_total * steps / dt, "ms_per_step": dt / steps * 1e3}
 
     main_case = run_case(a.batch, n_total, a.steps, a.warmup)
     batch, step, sim, idx, dt = main_case["batch"], main_case["step"], main_case["sim"], main_case["idx"], main_case["dt"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"sim": sim, "idx": idx, "bank": main_case["bank"]})
+    del main_case["bank"]
     poses = batch["all_relativeR"]
     per_gpu = (n_total + world - 1) // world
     res = {
@@ -472,14 +517,16 @@ def main():
                    "schedule": ("encoder passes of step k+1 on a side stream under step k's U-Net (pipeline_encoders); every step's work inside the timed region"
                                 if model.pipeline_encoders else "each step waits for the previous one")},
     }
-    if model.pipeline_encoders and not a.skip_extras:
+    full = a.full and not a.skip_extras           # everything below the headline: --full only
+    legs = {e for e in (a.extras or "scaling,roofline,parity,scoring,cpu").split(",") if e} if full else set()
+    if model.pipeline_encoders and full:
         model.pipeline_encoders = False
         c = run_case(a.batch, n_total, a.steps, 1)
         model.pipeline_encoders = True
         res["value_unpipelined"], res["ms_per_step_unpipelined"] = c["value"], c["ms_per_step"]
         assert torch.equal(c["idx"], idx) and torch.equal(c["sim"], sim), "pipelined and unpipelined steps differ"
         del c
-    if not a.skip_extras and "scaling" in a.extras.split(",") and not weak and a.batch == 1 and n_total == 512:
+    if "scaling" in legs and not weak and a.batch == 1 and n_total == 512:
         # The other two scaling lines, measured by the same ranks (few steps: they are whole-job rates, not tuning runs): N = 1 gives
         # their baselines, so the driver's 1 / 2 / 4 / 8 sweep yields all three curves.
         lines = []
@@ -495,7 +542,7 @@ def main():
         del c
         torch.cuda.empty_cache()
         res["scaling_lines"] = lines
-    extras = set() if a.skip_extras else {e for e in a.extras.split(",") if e and e != "scaling"}
+    extras = legs - {"scaling"}
     def ref_flops_frac(rf):
         # the reference graph's multiply-adds x2 per hypothesis at a 32x32 latent (35.05 GFLOP) x hypotheses / step / peak
         rf["mfma_utilisation_reference_flops"] = 35.05e9 * (a.size / 256.0) ** 2 * main_case["hyp"] / (main_case["ms_per_step"] * 1e-3) / (rf["peak"] * 1e12)
@@ -593,6 +640,8 @@ def scoring_only(a, dev, rank, world):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"sim": sim, "idx": idx})
     ok = bool((idx[:, 0] == 3).all()) and sim.shape == (B, n_total)
     byts = B * n_local * (8 * h * h * bank.element_size() + 4)
     res = {"metric": "pose-hypotheses/sec (queries x templates), scoring + top-5 on a resident bank", "value": B * n_total * a.steps / dt,

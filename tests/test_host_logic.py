@@ -538,3 +538,28 @@ def test_bench_power_ceiling_record(tmp_path, monkeypatch):
     assert "frac_of_registers_only" not in bench.power_ceiling(rf, "f32")                                      # exact-f32 MFMA: no such record
     exe.write_text("#!/bin/sh\necho not json\n")
     assert bench.power_ceiling(rf, "f16x2") is None
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: small arrays exactly (float32, integer indices as float64); a bank larger than its share of the 64 MB is
+    a seeded sample of its (query, template) rows, the same rows on every call, and the directory stays within the limit."""
+    import numpy as np
+    import bench
+    from nope_amd.dist import ShardedBank
+    g = torch.Generator().manual_seed(1)
+    sim = torch.randn(2, 512, generator=g)
+    idx = sim.topk(5, dim=1).indices
+    bank = ShardedBank(torch.randn(2, 512, 8, 16, 16, generator=g), 0, 512, 512)
+    bench.dump_outputs(str(tmp_path / "small"), {"sim": sim, "idx": idx, "bank": bank})
+    assert sorted(os.listdir(tmp_path / "small")) == ["bank.npy", "idx.npy", "sim.npy"]
+    assert np.load(tmp_path / "small" / "idx.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "small" / "idx.npy"), idx.double().numpy())
+    assert np.array_equal(np.load(tmp_path / "small" / "bank.npy"), bank.as_subclass(torch.Tensor).numpy())
+    big = torch.randn(16, 4096, 8, 16, 16, generator=g)                  # 128 MB in float32
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"sim": sim, "idx": idx, "bank": big})
+    size = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert size <= bench.DUMP_LIMIT_BYTES and size > bench.DUMP_LIMIT_BYTES * 0.95
+    rows = np.load(tmp_path / "a" / "bank_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "bank_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "bank.npy"), big.reshape(-1, 8 * 16 * 16).numpy()[rows.astype(np.int64)])

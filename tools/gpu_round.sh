@@ -13,7 +13,7 @@ echo "== pytest -m gpu"
 timeout 900 python -m pytest tests -m gpu -x -q -s > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log
 tail -25 $OUT/pytest_gpu.log
 echo "== bench"
-timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 cat $OUT/bench.json; tail -5 $OUT/bench.err
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   echo "== rocprofv3 kernel stats"
