@@ -73,9 +73,10 @@ typedef void* nope_stream_t;
  * 3: NOPE_F16 / NOPE_BF16X3 compute modes, 4x4 STRIDE2, nope_ldm_config.transformer_depth;
  * 4: nope_op_geodesic, nope_unet_graph_limit -- hipGraph replay became opt-in;
  * 5: NOPE_F16X2, nope_tuning_reload, nope_gather_topk, nope_topk_merge;
- * 6: nope_unet_x2_poll / _x2_range_check / _x2_enable / _x2_shifts, NOPE_ERR_RANGE*).  Callers compare nope_abi_version() against the header they were
+ * 6: nope_unet_x2_poll / _x2_range_check / _x2_enable / _x2_shifts, NOPE_ERR_RANGE*;
+ * 7: nope_ldm_config.head_channels / resblock_updown / conv_resample, nope_op_token_attention dim_head 64 / 128).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 6
+#define NOPE_ABI_VERSION 7
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -233,9 +234,11 @@ int nope_unet_profile_launches(nope_unet* net, nope_conv_launch_info* out, int m
  * Upsample :93-174; SpatialTransformer / BasicTransformerBlock / CrossAttention / GEGLU, ldm/attention.py:37-277): the variant
  * whose pose conditioning is cross-attention against context = pose_mlp(pose).  Tensor names are UNetModelPose's own
  * state-dict keys ("input_blocks.1.1.transformer_blocks.0.attn2.to_v.weight", "middle_block.0.in_layers.2.weight", ...).
- * Supported: use_spatial_transformer = true with transformer_depth >= 1 and num_head_channels = 32 (the shipped
- * configs/model/vae_cin_ldm.yaml), conv_resample, ResBlocks with or without use_scale_shift_norm (FiLM, openaimodel.py:277-281),
- * no resblock_updown; pose_mlp "single_layer" / "two_layers"; injecting_condition_twice on or off. */
+ * Supported: use_spatial_transformer = true with transformer_depth >= 1 and attention heads 32, 64 or 128 channels wide, per level
+ * (num_head_channels / num_heads, openaimodel.py:560-580; the shipped configs/model/vae_cin_ldm.yaml has 32 everywhere), conv_resample on
+ * or off (Downsample / Upsample with or without their conv, :94-175), resblock_updown on or off (ResBlocks with up / down, :177-288),
+ * ResBlocks with or without use_scale_shift_norm (FiLM, openaimodel.py:277-281); pose_mlp "single_layer" / "two_layers";
+ * injecting_condition_twice on or off. */
 typedef struct nope_ldm nope_ldm;
 typedef struct {
     int in_channels;        /* 4 in vae_cin_ldm.yaml (any count: the input conv's K axis is zero-padded to a multiple of 8 at pack time) */
@@ -245,7 +248,7 @@ typedef struct {
     int n_levels;           /* len(channel_mult) = 3 */
     int channel_mult[8];    /* (1,2,4) */
     int attn_levels[8];     /* 1 where the level's downsampling factor is in attention_resolutions: (1,1,1) */
-    int num_head_channels;  /* 32 */
+    int num_head_channels;  /* 32; 0 = per level, from head_channels (ABI 7) */
     int context_dim;        /* 512 */
     int pose_dim;           /* rot_representation_dim, 6 */
     int pose_mlp_layers;    /* 1 = "single_layer", 2 = "two_layers" */
@@ -253,6 +256,11 @@ typedef struct {
     int compute_dtype;      /* NOPE_F32 | NOPE_BF16 | NOPE_F16 | NOPE_BF16X3 | NOPE_F16X2 (= NOPE_BF16X3 here: its layers carry no second weight pack), as nope_unet_config */
     int use_scale_shift_norm;        /* 1: ResBlocks apply out_norm(h) * (1 + scale) + shift with (scale, shift) = emb_layers(emb) */
     int transformer_depth;           /* BasicTransformerBlocks per SpatialTransformer (attention.py:232-262); 1 in vae_cin_ldm.yaml; 0 reads as 1 */
+    int head_channels[8];   /* (ABI 7) attention head width of each level's SpatialTransformers, 32 / 64 / 128, heads * head_channels = the level's
+                             * channels; the middle block uses the last level's.  Read when num_head_channels = 0 (else every level has num_head_channels) */
+    int resblock_updown;    /* (ABI 7) 1: the resampling slots are ResBlocks with down / up (avg_pool 2x2 / nearest x2 on h and x, openaimodel.py:177-288) */
+    int conv_resample;      /* (ABI 7) 1 (vae_cin_ldm.yaml): Downsample = conv 3x3 stride 2, Upsample = nearest x2 + conv 3x3; 0: avg_pool 2x2 / nearest x2
+                             * alone (:94-175).  Ignored under resblock_updown */
 } nope_ldm_config;
 
 int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors, int n_tensors, nope_stream_t stream, nope_ldm** out);
@@ -346,7 +354,7 @@ int nope_op_warp_perspective(const void* src, int src_is_u8, int Hs, int Ws, int
                              float scale, float shift, nope_stream_t s);
 /* Token-space operators of the LDM variant (ldm/attention.py), tokens = NHWC pixels [M][C]:
  * LayerNorm over C (:210-212); GEGLU in [M][2D] -> out [M][D] (:37-44); softmax self-attention over the N tokens of each
- * sample on a fused [n][N][3C] q|k|v tensor, heads of 32 channels (:168-189).  dtype = a storage code; nope_op_token_attention also takes the
+ * sample on a fused [n][N][3C] q|k|v tensor, heads of dim_head = 32, 64 or 128 channels, C % dim_head = 0 (:168-189).  dtype = a storage code; nope_op_token_attention also takes the
  * compute tags NOPE_BF16X3 / NOPE_F16X2 (f32 tensors, every product as three bf16 MFMA passes over (hi, lo) splits: what the LDM runtime
  * launches in those modes; NOPE_F32 = all-f32 VALU arithmetic, the parity mode). */
 int nope_op_layer_norm(int dtype, const void* x, void* y, const float* gamma, const float* beta, int64_t M, int C, float eps, nope_stream_t s);

@@ -91,24 +91,26 @@ __global__ __launch_bounds__(NT) void add_rowvec_kernel(const T* __restrict__ x,
 }
 
 // ---- softmax self-attention over the tokens of a sample (CrossAttention with context = x, attention.py:168-189) ------------
-// qkv (S, N, 3*C): [q | k | v], head h = channels h*D .. h*D+D-1 (rearrange "b n (h d)"), D = 32.  One thread owns one query
-// (q and the output accumulator in registers); keys / values of the (sample, head) stream through LDS in f32 chunks that all
-// threads read at the same address (broadcast), with an online softmax.  f32 arithmetic throughout.
+// qkv (S, N, 3*C): [q | k | v], head h = channels h*D .. h*D+D-1 (rearrange "b n (h d)"), D = 32, 64 or 128.  L = D / 32 adjacent lanes
+// own one query, 32 channels each (q and the output accumulator in registers: 64 VGPRs whatever D is); a score is the lanes' partial
+// dot products summed with an xor butterfly, so every lane of the group holds the same value bit for bit.  Keys / values of the
+// (sample, head) stream through LDS in f32 chunks of 4096 / D keys that the threads read at L addresses per key (broadcast), with an
+// online softmax.  f32 arithmetic throughout.  (At D = 32, L = 1: one thread per query, 128-key chunks, no exchange.)
 // (A VALU kernel: at D = 32 this op is ~5 % of the variant's FLOPs; the convolutions and linears run on the MFMA kernels.)
-constexpr int AD = 32;
-constexpr int KCH = 128;
-template <class T>
+constexpr int AD = 32;           // channels per lane (and the head width of the shipped configuration)
+template <class T, int D>
 __global__ __launch_bounds__(NT) void token_attn_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int C, float scale) {
-    __shared__ __attribute__((aligned(16))) float s_k[KCH][AD];
-    __shared__ __attribute__((aligned(16))) float s_v[KCH][AD];
+    constexpr int L = D / AD, QPB = NT / L, KCH = 128 * AD / D;
+    __shared__ __attribute__((aligned(16))) float s_k[KCH][D];
+    __shared__ __attribute__((aligned(16))) float s_v[KCH][D];
     const int tid = threadIdx.x;
     const int head = blockIdx.y, smp = blockIdx.z;
-    const int qi = blockIdx.x * NT + tid;
+    const int qi = blockIdx.x * QPB + tid / L, part = tid % L;
     const T* base = qkv + (size_t)smp * N * 3 * C;
     float q[AD], o[AD];
     const bool qok = qi < N;
     {
-        const T* qp = base + (size_t)(qok ? qi : 0) * 3 * C + head * AD;
+        const T* qp = base + (size_t)(qok ? qi : 0) * 3 * C + head * D + part * AD;
         constexpr int VEC = Elt<T>::VEC;
 #pragma unroll
         for (int v = 0; v < AD / VEC; ++v) {
@@ -125,14 +127,14 @@ __global__ __launch_bounds__(NT) void token_attn_kernel(const T* __restrict__ qk
         __syncthreads();
         // stage KCH keys and values of this head as f32: thread -> (key, 16-byte vector)
         constexpr int VEC = Elt<T>::VEC;
-        constexpr int VPK = AD / VEC;
+        constexpr int VPK = D / VEC;
         for (int i = tid; i < KCH * VPK * 2; i += NT) {
             const int which = i / (KCH * VPK), r = i - which * (KCH * VPK);
             const int key = r / VPK, v = r - key * VPK;
             float t[VEC];
 #pragma unroll
             for (int e = 0; e < VEC; ++e) t[e] = 0.f;
-            if (k0 + key < N) Elt<T>::unpack(ld16(base + (size_t)(k0 + key) * 3 * C + (1 + which) * C + head * AD + v * VEC), t);
+            if (k0 + key < N) Elt<T>::unpack(ld16(base + (size_t)(k0 + key) * 3 * C + (1 + which) * C + head * D + v * VEC), t);
             float* dst = which ? &s_v[key][v * VEC] : &s_k[key][v * VEC];
 #pragma unroll
             for (int e = 0; e < VEC; ++e) dst[e] = t[e];
@@ -142,18 +144,20 @@ __global__ __launch_bounds__(NT) void token_attn_kernel(const T* __restrict__ qk
         for (int j = 0; j < kn; ++j) {
             float s = 0.f;
 #pragma unroll
-            for (int d = 0; d < AD; ++d) s += q[d] * s_k[j][d];
+            for (int d = 0; d < AD; ++d) s += q[d] * s_k[j][part * AD + d];
+#pragma unroll
+            for (int m = 1; m < L; m <<= 1) s += __shfl_xor(s, m, 64);      // (a + b == b + a: the group's lanes agree exactly)
             const float nm = s > mx ? s : mx;
             const float corr = __expf(mx - nm), p = __expf(s - nm);
             den = den * corr + p;
 #pragma unroll
-            for (int d = 0; d < AD; ++d) o[d] = o[d] * corr + p * s_v[j][d];
+            for (int d = 0; d < AD; ++d) o[d] = o[d] * corr + p * s_v[j][part * AD + d];
             mx = nm;
         }
     }
     if (qok) {
         const float inv = 1.0f / den;
-        T* op = out + ((size_t)smp * N + qi) * C + head * AD;
+        T* op = out + ((size_t)smp * N + qi) * C + head * D + part * AD;
         constexpr int VEC = Elt<T>::VEC;
 #pragma unroll
         for (int v = 0; v < AD / VEC; ++v) {
@@ -176,13 +180,16 @@ __global__ __launch_bounds__(NT) void token_attn_kernel(const T* __restrict__ qk
 //                      accumulator layout left it, and the A operand V^T (staged transposed, [d][key]) is read in that key order
 //                      (two 8-byte LDS reads per step)
 // P is rounded to bf16 before P V (as V is stored); scores, max, sums and the output accumulate in f32.
+// D = 64 / 128: D / 16 MFMA steps per score block (Q^T fragments qf[D / 16]) and D / 32 output accumulators (V^T rows li + 32 dt); the
+// softmax and the P^T fragments do not depend on D.  At D = 32 the instructions and their order are those of the 32-wide kernel.
 constexpr int MQ = 128;          // queries per workgroup
 constexpr int MK = 64;           // keys per iteration
-constexpr int K_LD = 40;         // bf16 per staged K row (32 + pad: conflict-free 16-byte fragment reads)
-constexpr int VT_LD = 68;        // bf16 per staged V^T row (64 keys + pad: conflict-free 8-byte reads)
-template <class T>      // bf16_t or f16_t (v_mfma_f32_32x32x16_bf16 / _f16; P rounded to the same 16-bit type as V is stored in)
+constexpr int VT_LD = 68;        // 16-bit elements per staged V^T row (64 keys + pad: conflict-free 8-byte reads)
+template <int D> constexpr int k_ld() { return D + 8; }        // per staged K row (D + pad: conflict-free 16-byte fragment reads)
+template <class T, int D>      // bf16_t or f16_t (v_mfma_f32_32x32x16_bf16 / _f16; P rounded to the same 16-bit type as V is stored in)
 __global__ __launch_bounds__(NT) void token_attn_mfma_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int C, float scale_log2e) {
     constexpr bool F16 = Elt<T>::DT == NOPE_F16;
+    constexpr int KS = D / 16, DT = D / 32, K_LD = k_ld<D>();
     auto mma = [](const u32x4& a, const u32x4& b, const __attribute__((ext_vector_type(16))) float& c) {
         if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
         else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -190,38 +197,45 @@ __global__ __launch_bounds__(NT) void token_attn_mfma_kernel(const T* __restrict
     typedef __attribute__((ext_vector_type(16))) float f32x16;
     typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
     __shared__ __attribute__((aligned(16))) unsigned short s_k[MK][K_LD];          // (raw 16-bit elements of either type)
-    __shared__ __attribute__((aligned(16))) unsigned short s_vt[AD][VT_LD];
+    __shared__ __attribute__((aligned(16))) unsigned short s_vt[D][VT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int head = blockIdx.y, smp = blockIdx.z;
     const int h = lane >> 5, li = lane & 31;
-    const T* base = qkv + (size_t)smp * N * 3 * C + head * AD;
+    const T* base = qkv + (size_t)smp * N * 3 * C + head * D;
     const int q = blockIdx.x * MQ + wave * 32 + li;            // this lane's query (accumulator column)
-    // Q^T fragments (B operand): column = query, k = d: 8 consecutive d at 8 h (+ 16 for the second step)
-    u32x4 qf[2];
+    // Q^T fragments (B operand): column = query, k = d: 8 consecutive d at 8 h (+ 16 kk for step kk)
+    u32x4 qf[KS];
     {
         const T* qp = base + (size_t)(q < N ? q : N - 1) * 3 * C + 8 * h;
-        qf[0] = ld16(qp); qf[1] = ld16(qp + 16);
-    }
-    f32x16 o;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+        for (int kk = 0; kk < KS; ++kk) qf[kk] = ld16(qp + 16 * kk);
+    }
+    f32x16 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     float mx = -3.0e38f, den = 0.f;                              // (in log2 units; den: this lane's half of the row sum)
-    // staging role: thread -> (key, 16-byte vector of its K row and of its V row); the next block's loads fly under the MFMAs
+    // staging role: thread -> (key, 16-byte vectors 8 svec + 32 j of its K row and of its V row); the next block's loads fly under the MFMAs
     const int skey = tid >> 2, svec = tid & 3;
-    u32x4 nk, nv;
+    u32x4 nk[DT], nv[DT];
     auto fetch = [&](int k0) {
         const int key = k0 + skey;
         const T* kp = base + (size_t)(key < N ? key : N - 1) * 3 * C + C + svec * 8;
-        nk = ld16(kp); nv = ld16(kp + C);
+#pragma unroll
+        for (int j = 0; j < DT; ++j) { nk[j] = ld16(kp + 32 * j); nv[j] = ld16(kp + C + 32 * j); }
     };
     fetch(0);
     for (int k0 = 0; k0 < N; k0 += MK) {
         __syncthreads();                                         // everyone is done reading the previous block
-        st16(&s_k[skey][svec * 8], nk);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {                            // V^T: [d][key]
-            const unsigned w = nv[e >> 1];
-            s_vt[svec * 8 + e][skey] = (unsigned short)((e & 1) ? (w >> 16) : (w & 0xffffu));
+        for (int j = 0; j < DT; ++j) {
+            st16(&s_k[skey][svec * 8 + 32 * j], nk[j]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {                        // V^T: [d][key]
+                const unsigned w = nv[j][e >> 1];
+                s_vt[svec * 8 + 32 * j + e][skey] = (unsigned short)((e & 1) ? (w >> 16) : (w & 0xffffu));
+            }
         }
         __syncthreads();
         if (k0 + MK < N) fetch(k0 + MK);
@@ -231,7 +245,7 @@ __global__ __launch_bounds__(NT) void token_attn_mfma_kernel(const T* __restrict
 #pragma unroll
             for (int r = 0; r < 16; ++r) sc[sb][r] = 0.f;
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
+            for (int kk = 0; kk < KS; ++kk) {
                 const u32x4 kf = ld16(&s_k[sb * 32 + li][8 * h + 16 * kk]);
                 sc[sb] = mma(kf, qf[kk], sc[sb]);
             }
@@ -276,27 +290,34 @@ __global__ __launch_bounds__(NT) void token_attn_mfma_kernel(const T* __restrict
                 }
         den = den * corr + ps;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] *= corr;
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[dt][r] *= corr;
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int kb = sb * 32 + 16 * t + 4 * h;        // keys kb .. kb + 3 and kb + 8 .. kb + 11 are this lane's 8 k slots
-                const u32x2 v0 = *reinterpret_cast<const u32x2*>(&s_vt[li][kb]);
-                const u32x2 v1 = *reinterpret_cast<const u32x2*>(&s_vt[li][kb + 8]);
-                const u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
-                o = mma(vf, pf[sb][t], o);
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) {
+                    const u32x2 v0 = *reinterpret_cast<const u32x2*>(&s_vt[32 * dt + li][kb]);
+                    const u32x2 v1 = *reinterpret_cast<const u32x2*>(&s_vt[32 * dt + li][kb + 8]);
+                    const u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
+                    o[dt] = mma(vf, pf[sb][t], o[dt]);
+                }
             }
     }
     den += __shfl_xor(den, 32, 64);
     if (q < N) {
         const float inv = 1.0f / den;
-        T* op = out + ((size_t)smp * N + q) * C + head * AD + 4 * h;       // rows of O^T this lane holds: d = 8 g + 4 h + (r & 3)
+        T* op = out + ((size_t)smp * N + q) * C + head * D + 4 * h;       // rows of O^T this lane holds: d = 32 dt + 8 g + 4 h + (r & 3)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const unsigned long long lo = Elt<T>::cvt_pk(o[4 * g] * inv, o[4 * g + 1] * inv), hi = Elt<T>::cvt_pk(o[4 * g + 2] * inv, o[4 * g + 3] * inv);
-            *reinterpret_cast<unsigned long long*>(op + 8 * g) = lo | (hi << 32);
-        }
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const unsigned long long lo = Elt<T>::cvt_pk(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv), hi = Elt<T>::cvt_pk(o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
+                *reinterpret_cast<unsigned long long*>(op + 32 * dt + 8 * g) = lo | (hi << 32);
+            }
     }
 }
 
@@ -322,21 +343,23 @@ __device__ __forceinline__ void split8_bf16(const u32x4 a, const u32x4 b, u32x4&
         lo[e] = cvt_pk_bf16(x[2 * e] - h0, x[2 * e + 1] - h1);
     }
 }
+template <int D>
 __global__ __launch_bounds__(NT) void token_attn_mfma_x3_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, int C, float scale_log2e) {
+    constexpr int KS = D / 16, DT = D / 32, K_LD = k_ld<D>();
     typedef __attribute__((ext_vector_type(16))) float f32x16;
     typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
     __shared__ __attribute__((aligned(16))) bf16_t s_k[2][MK][K_LD];          // [hi | lo]
-    __shared__ __attribute__((aligned(16))) bf16_t s_vt[2][AD][VT_LD];
+    __shared__ __attribute__((aligned(16))) bf16_t s_vt[2][D][VT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int head = blockIdx.y, smp = blockIdx.z;
     const int h = lane >> 5, li = lane & 31;
-    const float* base = qkv + (size_t)smp * N * 3 * C + head * AD;
+    const float* base = qkv + (size_t)smp * N * 3 * C + head * D;
     const int q = blockIdx.x * MQ + wave * 32 + li;            // this lane's query (accumulator column)
-    u32x4 qh[2], ql[2];                                        // Q^T fragments (B operand): column = query, k = d: 8 consecutive d at 8 h (+ 16 for the second step)
+    u32x4 qh[KS], ql[KS];                                      // Q^T fragments (B operand): column = query, k = d: 8 consecutive d at 8 h (+ 16 kk for step kk)
     {
         const float* qp = base + (size_t)(q < N ? q : N - 1) * 3 * C + 8 * h;
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {                       // q * (scale log2 e) in f32, then split: the scores come out of the MFMAs in log2 units
+        for (int kk = 0; kk < KS; ++kk) {                      // q * (scale log2 e) in f32, then split: the scores come out of the MFMAs in log2 units
             u32x4 a = ld16(qp + 16 * kk), b = ld16(qp + 16 * kk + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -347,32 +370,38 @@ __global__ __launch_bounds__(NT) void token_attn_mfma_x3_kernel(const float* __r
             split8_bf16(a, b, qh[kk], ql[kk]);
         }
     }
-    f32x16 o;
+    f32x16 o[DT];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
     float mx = -3.0e38f, den = 0.f;                              // (in log2 units; den: this lane's half of the row sum)
-    // staging role: thread -> (key, 8 channels of its K row and of its V row); the next block's loads fly under the MFMAs
+    // staging role: thread -> (key, channels 8 svec + 32 j .. + 7 of its K row and of its V row); the next block's loads fly under the MFMAs
     const int skey = tid >> 2, svec = tid & 3;
-    u32x4 nk[2], nv[2];
+    u32x4 nk[DT][2], nv[DT][2];
     auto fetch = [&](int k0) {
         const int key = k0 + skey;
         const float* kp = base + (size_t)(key < N ? key : N - 1) * 3 * C + C + svec * 8;
-        nk[0] = ld16(kp); nk[1] = ld16(kp + 4); nv[0] = ld16(kp + C); nv[1] = ld16(kp + C + 4);
+#pragma unroll
+        for (int j = 0; j < DT; ++j) {
+            nk[j][0] = ld16(kp + 32 * j); nk[j][1] = ld16(kp + 32 * j + 4); nv[j][0] = ld16(kp + C + 32 * j); nv[j][1] = ld16(kp + C + 32 * j + 4);
+        }
     };
     fetch(0);
     for (int k0 = 0; k0 < N; k0 += MK) {
         __syncthreads();                                         // everyone is done reading the previous block
-        {
+#pragma unroll
+        for (int j = 0; j < DT; ++j) {
             u32x4 kh, kl, vh, vl;
-            split8_bf16(nk[0], nk[1], kh, kl);
-            split8_bf16(nv[0], nv[1], vh, vl);
-            st16(&s_k[0][skey][svec * 8], kh);
-            st16(&s_k[1][skey][svec * 8], kl);
+            split8_bf16(nk[j][0], nk[j][1], kh, kl);
+            split8_bf16(nv[j][0], nv[j][1], vh, vl);
+            st16(&s_k[0][skey][svec * 8 + 32 * j], kh);
+            st16(&s_k[1][skey][svec * 8 + 32 * j], kl);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {                        // V^T: [d][key]
                 const unsigned wh = vh[e >> 1], wl = vl[e >> 1];
-                s_vt[0][svec * 8 + e][skey] = (bf16_t)((e & 1) ? (wh >> 16) : (wh & 0xffffu));
-                s_vt[1][svec * 8 + e][skey] = (bf16_t)((e & 1) ? (wl >> 16) : (wl & 0xffffu));
+                s_vt[0][svec * 8 + 32 * j + e][skey] = (bf16_t)((e & 1) ? (wh >> 16) : (wh & 0xffffu));
+                s_vt[1][svec * 8 + 32 * j + e][skey] = (bf16_t)((e & 1) ? (wl >> 16) : (wl & 0xffffu));
             }
         }
         __syncthreads();
@@ -387,7 +416,7 @@ __global__ __launch_bounds__(NT) void token_attn_mfma_x3_kernel(const float* __r
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
+                for (int kk = 0; kk < KS; ++kk) {
                     const u32x4 kf = ld16(&s_k[t == 0 ? 1 : 0][sb * 32 + li][8 * h + 16 * kk]);
                     const u32x4 qf = t == 1 ? ql[kk] : qh[kk];
                     sc[sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf), sc[sb], 0, 0, 0);
@@ -427,7 +456,9 @@ __global__ __launch_bounds__(NT) void token_attn_mfma_x3_kernel(const float* __r
                 }
         den = den * corr + ps;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] *= corr;
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[dt][r] *= corr;
 #pragma unroll
         for (int tm = 0; tm < 3; ++tm)
 #pragma unroll
@@ -435,26 +466,31 @@ __global__ __launch_bounds__(NT) void token_attn_mfma_x3_kernel(const float* __r
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const int kb = sb * 32 + 16 * t + 4 * h;        // keys kb .. kb + 3 and kb + 8 .. kb + 11 are this lane's 8 k slots
-                    const bf16_t* vr = &s_vt[tm == 0 ? 1 : 0][li][kb];
-                    const u32x2 v0 = *reinterpret_cast<const u32x2*>(vr);
-                    const u32x2 v1 = *reinterpret_cast<const u32x2*>(vr + 8);
-                    const u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
                     const u32x4 pf = tm == 1 ? pl[sb][t] : ph[sb][t];
-                    o = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf), o, 0, 0, 0);
+#pragma unroll
+                    for (int dt = 0; dt < DT; ++dt) {
+                        const bf16_t* vr = &s_vt[tm == 0 ? 1 : 0][32 * dt + li][kb];
+                        const u32x2 v0 = *reinterpret_cast<const u32x2*>(vr);
+                        const u32x2 v1 = *reinterpret_cast<const u32x2*>(vr + 8);
+                        const u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
+                        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf), o[dt], 0, 0, 0);
+                    }
                 }
     }
     den += __shfl_xor(den, 32, 64);
     if (q < N) {
         const float inv = 1.0f / den;
-        float* op = out + ((size_t)smp * N + q) * C + head * AD + 4 * h;        // rows of O^T this lane holds: d = 8 g + 4 h + (r & 3)
+        float* op = out + ((size_t)smp * N + q) * C + head * D + 4 * h;        // rows of O^T this lane holds: d = 32 dt + 8 g + 4 h + (r & 3)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float t4[4] = {o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv};
-            u32x4 w;
+        for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = __builtin_bit_cast(unsigned, t4[e]);
-            st16(op + 8 * g, w);
-        }
+            for (int g = 0; g < 4; ++g) {
+                float t4[4] = {o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv};
+                u32x4 w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[e] = __builtin_bit_cast(unsigned, t4[e]);
+                st16(op + 32 * dt + 8 * g, w);
+            }
     }
 }
 
@@ -469,6 +505,49 @@ __global__ __launch_bounds__(NT) void copy_cols_kernel(const T* __restrict__ x, 
         const long long m = i / nv;
         const int v = (int)(i - m * nv);
         st16(y + m * C2 + off + v * VEC, ld16(x + m * C + v * VEC));
+    }
+}
+
+// ---- parameter-free resampling on NHWC activations (openaimodel.py:94-175, and ResBlock's h_upd / x_upd, :262-271) ----------------
+// avg_pool2d(2): y[n, i, j, :] = (x[2i, 2j] + x[2i, 2j+1] + x[2i+1, 2j] + x[2i+1, 2j+1]) / 4, H and W even; thread -> (output pixel, 16 bytes)
+template <class T>
+__global__ __launch_bounds__(NT) void avg_pool2_kernel(const T* __restrict__ x, T* __restrict__ y, long long n, int Ho, int Wo, int C) {
+    constexpr int VEC = Elt<T>::VEC;
+    const int nv = C / VEC;
+    const long long total = n * Ho * Wo * nv;
+    const long long rs = (long long)2 * Wo * C;           // one input row
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+        const long long pix = i / nv;
+        const int v = (int)(i - pix * nv);
+        const long long s = pix / ((long long)Ho * Wo);
+        const int r = (int)(pix - s * Ho * Wo), oi = r / Wo, oj = r - oi * Wo;
+        const T* xp = x + ((s * 2 * Ho + 2 * oi) * 2 * Wo + 2 * oj) * C + v * VEC;
+        float a[VEC], b[VEC], c[VEC], d[VEC];
+        Elt<T>::unpack(ld16(xp), a);
+        Elt<T>::unpack(ld16(xp + C), b);
+        Elt<T>::unpack(ld16(xp + rs), c);
+        Elt<T>::unpack(ld16(xp + rs + C), d);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) a[e] = ((a[e] + b[e]) + (c[e] + d[e])) * 0.25f;
+        st16(y + pix * C + v * VEC, Elt<T>::pack(a));
+    }
+}
+
+// nearest x2 (F.interpolate(scale_factor=2, mode="nearest")): y[n, i, j, :] = x[n, i / 2, j / 2, :]; thread -> (input pixel, 16 bytes), four stores
+template <class T>
+__global__ __launch_bounds__(NT) void nearest2_kernel(const T* __restrict__ x, T* __restrict__ y, long long n, int H, int W, int C) {
+    constexpr int VEC = Elt<T>::VEC;
+    const int nv = C / VEC;
+    const long long total = n * H * W * nv;
+    const long long rs = (long long)2 * W * C;            // one output row
+    for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < total; i += (long long)gridDim.x * NT) {
+        const long long pix = i / nv;
+        const int v = (int)(i - pix * nv);
+        const long long s = pix / ((long long)H * W);
+        const int r = (int)(pix - s * H * W), ii = r / W, jj = r - ii * W;
+        const u32x4 t = ld16(x + pix * C + v * VEC);
+        T* yp = y + ((s * 2 * H + 2 * ii) * 2 * W + 2 * jj) * C + v * VEC;
+        st16(yp, t); st16(yp + C, t); st16(yp + rs, t); st16(yp + rs + C, t);
     }
 }
 
@@ -510,25 +589,56 @@ int launch_add_rowvec(int dt, const void* x, void* y, const float* u, long long 
     return NOPE_OK;
 }
 
-int launch_token_attention(int dt, const void* qkv, void* out, int nsmp, int N, int C, int dim_head, hipStream_t s) {
-    if (!qkv || !out || nsmp <= 0 || N <= 0 || C <= 0 || dim_head != AD || C % AD) return NOPE_ERR_ARG;
-    const dim3 grid((unsigned)cdiv(N, NT), (unsigned)(C / AD), (unsigned)nsmp);
-    const float scale = 1.0f / sqrtf((float)dim_head);
-    // bf16 / f16: the matrix-core kernel (NOPE_LDM_ATTN=0 keeps the VALU one: the tests compare the two); f32 -- the parity mode -- stays
-    // on the all-f32 VALU kernel
-    // on the all-f32 VALU kernel; the compute tags NOPE_BF16X3 / NOPE_F16X2 (f32 storage): the same schedule on three bf16 passes per product
-    const bool mfma = NOPE_ENV("NOPE_LDM_ATTN", -1) != 0;
-    const dim3 g2((unsigned)cdiv(N, MQ), (unsigned)(C / AD), (unsigned)nsmp);
+namespace {
+
+template <int D>
+int launch_token_attention_d(int dt, bool mfma, const void* qkv, void* out, int nsmp, int N, int C, hipStream_t s) {
+    const float scale = 1.0f / sqrtf((float)D);
+    const dim3 g2((unsigned)cdiv(N, MQ), (unsigned)(C / D), (unsigned)nsmp);
     if (dt == NOPE_BF16 && mfma) {
-        hipLaunchKernelGGL((token_attn_mfma_kernel<bf16_t>), g2, dim3(NT), 0, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, scale * 1.4426950408889634f);
+        hipLaunchKernelGGL((token_attn_mfma_kernel<bf16_t, D>), g2, dim3(NT), 0, s, (const bf16_t*)qkv, (bf16_t*)out, N, C, scale * 1.4426950408889634f);
     } else if (dt == NOPE_F16 && mfma) {
-        hipLaunchKernelGGL((token_attn_mfma_kernel<f16_t>), g2, dim3(NT), 0, s, (const f16_t*)qkv, (f16_t*)out, N, C, scale * 1.4426950408889634f);
+        hipLaunchKernelGGL((token_attn_mfma_kernel<f16_t, D>), g2, dim3(NT), 0, s, (const f16_t*)qkv, (f16_t*)out, N, C, scale * 1.4426950408889634f);
     } else if ((dt == NOPE_BF16X3 || dt == NOPE_F16X2) && mfma) {
-        hipLaunchKernelGGL(token_attn_mfma_x3_kernel, g2, dim3(NT), 0, s, (const float*)qkv, (float*)out, N, C, scale * 1.4426950408889634f);
+        hipLaunchKernelGGL((token_attn_mfma_x3_kernel<D>), g2, dim3(NT), 0, s, (const float*)qkv, (float*)out, N, C, scale * 1.4426950408889634f);
     } else {
         const int sdt = dt_storage(dt);
-        NOPE_DISPATCH_T(sdt, T, hipLaunchKernelGGL((token_attn_kernel<T>), grid, dim3(NT), 0, s, (const T*)qkv, (T*)out, N, C, scale));
+        const dim3 grid((unsigned)cdiv(N, NT / (D / AD)), (unsigned)(C / D), (unsigned)nsmp);
+        NOPE_DISPATCH_T(sdt, T, hipLaunchKernelGGL((token_attn_kernel<T, D>), grid, dim3(NT), 0, s, (const T*)qkv, (T*)out, N, C, scale));
     }
+    return NOPE_OK;
+}
+
+}  // namespace
+
+int launch_token_attention(int dt, const void* qkv, void* out, int nsmp, int N, int C, int dim_head, hipStream_t s) {
+    if (!qkv || !out || nsmp <= 0 || N <= 0 || C <= 0 || (dim_head != 32 && dim_head != 64 && dim_head != 128) || C % dim_head) return NOPE_ERR_ARG;
+    // bf16 / f16: the matrix-core kernel (NOPE_LDM_ATTN=0 keeps the VALU one: the tests compare the two); f32 -- the parity mode -- stays
+    // on the all-f32 VALU kernel; the compute tags NOPE_BF16X3 / NOPE_F16X2 (f32 storage): the same schedule on three bf16 passes per product.
+    // Head widths 32 / 64 / 128 (dim_head, attention.py:149-166), each kernel instantiated per width
+    const bool mfma = NOPE_ENV("NOPE_LDM_ATTN", -1) != 0;
+    const int e = dim_head == 32 ? launch_token_attention_d<32>(dt, mfma, qkv, out, nsmp, N, C, s)
+                : dim_head == 64 ? launch_token_attention_d<64>(dt, mfma, qkv, out, nsmp, N, C, s)
+                                 : launch_token_attention_d<128>(dt, mfma, qkv, out, nsmp, N, C, s);
+    if (e) return e;
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
+int launch_avg_pool2(int dt, const void* x, void* y, long long n, int H, int W, int C, hipStream_t s) {
+    const int vec = dt_vec(dt);
+    if (!x || !y || n <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % vec) return NOPE_ERR_ARG;
+    const dim3 grid(grid_for_ll(n * (H / 2) * (W / 2) * (C / vec)));
+    NOPE_DISPATCH_T(dt, T, hipLaunchKernelGGL((avg_pool2_kernel<T>), grid, dim3(NT), 0, s, (const T*)x, (T*)y, n, H / 2, W / 2, C));
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
+int launch_nearest2(int dt, const void* x, void* y, long long n, int H, int W, int C, hipStream_t s) {
+    const int vec = dt_vec(dt);
+    if (!x || !y || n <= 0 || H <= 0 || W <= 0 || C <= 0 || C % vec) return NOPE_ERR_ARG;
+    const dim3 grid(grid_for_ll(n * H * W * (C / vec)));
+    NOPE_DISPATCH_T(dt, T, hipLaunchKernelGGL((nearest2_kernel<T>), grid, dim3(NT), 0, s, (const T*)x, (T*)y, n, H, W, C));
     NOPE_CHECK_LAUNCH();
     return NOPE_OK;
 }

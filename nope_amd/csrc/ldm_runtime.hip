@@ -31,10 +31,14 @@ namespace {
 
 struct LConv { void* w = nullptr; float* bias = nullptr; int Cin = 0, Cout = 0, ntaps = 1, mode = NOPE_CONV_PLAIN; void* w_x2 = nullptr; int x2_id = -1; };   // w_x2 / x2_id: NOPE_F16X2, the 3x3 convs' second pack and its slot in the range table (x2_range.h)
 struct LNorm { float* gamma = nullptr; float* beta = nullptr; int C = 0; };
-struct LRes { LNorm n1, n2; LConv c1, c2, skip; bool has_skip = false; float *emb_w = nullptr, *emb_b = nullptr; int Cin = 0, Cout = 0; };
+struct LRes { LNorm n1, n2; LConv c1, c2, skip; bool has_skip = false; float *emb_w = nullptr, *emb_b = nullptr; int Cin = 0, Cout = 0;
+              int updown = 0; };      // updown: 0, RES_DOWN or RES_UP (resblock_updown, openaimodel.py:224-231)
+enum { RES_DOWN = 1, RES_UP = 2 };
 struct LTB { LNorm ln1, ln3; LConv qkv, out1, ff1, ff2; int u_off = 0; };         // one BasicTransformerBlock; u_off: its slice of nope_ldm::u_w
-struct LST { LNorm norm; LConv proj_in, proj_out; std::vector<LTB> blocks; int C = 0; };
-struct LBlock { bool has_res = false, has_st = false, has_resample = false; LRes res; LST st; LConv resample; };
+struct LST { LNorm norm; LConv proj_in, proj_out; std::vector<LTB> blocks; int C = 0, dh = 32; };      // dh: attention head width (dim_head)
+// has_resample: a Downsample / Upsample slot -- its conv (conv_resample), or with resample.w = null avg_pool 2x2 / nearest x2 alone; under
+// resblock_updown the input-block slot holds a ResBlock (res.updown = RES_DOWN), the output block's slot one in `up` (RES_UP)
+struct LBlock { bool has_res = false, has_st = false, has_resample = false; LRes res, up; LST st; LConv resample; };     // up: an output block's ResBlock(up=True)
 
 }  // namespace
 
@@ -159,11 +163,12 @@ struct Loader {
         n.beta = copy_f32(pfx + "bias", {C});
         return n;
     }
-    LRes res(const std::string& p, int Cin, int Cout) {
+    LRes res(const std::string& p, int Cin, int Cout, int updown = 0) {
         LRes r;
-        r.Cin = Cin; r.Cout = Cout;
+        r.Cin = Cin; r.Cout = Cout; r.updown = updown;
         r.n1 = norm(p + "in_layers.0.", Cin);
-        r.c1 = conv(p + "in_layers.2.", Cin, Cout, 3, NOPE_CONV_PLAIN, true);
+        // (up: GroupNorm + SiLU -> nearest x2 -> conv 3x3 is the phase conv of Upsample; down: the conv reads the pooled activation)
+        r.c1 = conv(p + "in_layers.2.", Cin, Cout, 3, updown == RES_UP ? NOPE_CONV_UP2P : NOPE_CONV_PLAIN, true);
         const int film = net->cfg.use_scale_shift_norm ? 2 : 1;          // emb_layers.1: Linear(emb, 2 C) for FiLM, openaimodel.py:233-239
         r.emb_w = copy_f32(p + "emb_layers.1.weight", {film * Cout, net->emb_dim});
         r.emb_b = copy_f32(p + "emb_layers.1.bias", {film * Cout});
@@ -175,9 +180,9 @@ struct Loader {
             chk(launch_add_rowvec(NOPE_F32, r.c1.bias, r.c1.bias, r.emb_b, 1, 1, Cout, s));
         return r;
     }
-    LST st(const std::string& p, int C) {
+    LST st(const std::string& p, int C, int dh) {
         LST T;
-        T.C = C;
+        T.C = C; T.dh = dh;
         const int ctx = net->cfg.context_dim;
         T.norm = norm(p + "norm.", C);
         T.proj_in = conv(p + "proj_in.", C, C, 1, NOPE_CONV_PLAIN, true);
@@ -304,16 +309,45 @@ struct Fwd {
         }
         chk(launch_gn_apply(net->sdt, ga, s));
     }
-    // ResBlock._forward, openaimodel.py:262-288 (no up/down)
-    void res(const LRes& R, const Act& x, void* out) {
-        const int HW = x.H * x.W;
-        const size_t M = (size_t)nhyp * HW;
+    // parameter-free resampling of an activation (storage dtype); the output's range is unknown to x2_range.h: a two-pass conv that
+    // reads it takes an absmax pass (the arena hands out addresses again -- a stale slot of an earlier tensor would misjudge it)
+    void pool(const Act& x, void* y) {
+        if (!live()) return;
+        if (tracking()) x2.overwritten(y);
+        chk(launch_avg_pool2(net->sdt, x.p, y, nhyp, x.H, x.W, x.C, s));
+    }
+    void up2(const Act& x, void* y) {
+        if (!live()) return;
+        if (tracking()) x2.overwritten(y);
+        chk(launch_nearest2(net->sdt, x.p, y, nhyp, x.H, x.W, x.C, s));
+    }
+    // ResBlock._forward, openaimodel.py:262-288; out is at the input's size, half of it (RES_DOWN) or twice it (RES_UP)
+    void res(const LRes& R, const Act& xin, void* out) {
         const size_t mark = ar.off;
         const bool film_on = net->cfg.use_scale_shift_norm != 0;
-        void* t = alloc_act(M * R.Cin);
+        const int Ho = R.updown == RES_DOWN ? xin.H / 2 : R.updown == RES_UP ? xin.H * 2 : xin.H;
+        const int Wo = R.updown == RES_DOWN ? xin.W / 2 : R.updown == RES_UP ? xin.W * 2 : xin.W;
+        const int HW = Ho * Wo;
+        const size_t M = (size_t)nhyp * HW;
+        void* t = alloc_act((size_t)nhyp * xin.H * xin.W * R.Cin);
         void* h = alloc_act(M * R.Cout);
-        gn(R.n1, x.p, t, HW, 1, 1e-5f);
-        conv(R.c1, Act{t, R.Cin, x.H, x.W}, h, x.H, x.W);
+        gn(R.n1, xin.p, t, xin.H * xin.W, 1, 1e-5f);
+        Act x = xin;
+        if (R.updown == RES_DOWN) {          // h = conv(avg_pool(silu(norm(x)))), x = avg_pool(x)
+            void* tp = alloc_act(M * R.Cin);
+            void* xp = alloc_act(M * R.Cin);
+            pool(Act{t, R.Cin, xin.H, xin.W}, tp);
+            pool(xin, xp);
+            x = Act{xp, R.Cin, Ho, Wo};
+            conv(R.c1, Act{tp, R.Cin, Ho, Wo}, h, Ho, Wo);
+        } else if (R.updown == RES_UP) {     // h = conv(nearest(silu(norm(x)))) as the phase conv, x = nearest(x)
+            void* xu = alloc_act(M * R.Cin);
+            up2(xin, xu);
+            x = Act{xu, R.Cin, Ho, Wo};
+            conv(R.c1, Act{t, R.Cin, xin.H, xin.W}, h, Ho, Wo);
+        } else {
+            conv(R.c1, Act{t, R.Cin, x.H, x.W}, h, x.H, x.W);
+        }
         const float* film = nullptr;                // FiLM rows [scale | shift]: emb == 0 -> the bias row, shared by every sample
         int film_stride = 0;
         if (film_on && !emb) film = R.emb_b;
@@ -356,7 +390,7 @@ struct Fwd {
             void* a = xn;                                    // reuse: LN1(tok)
             if (live()) chk(launch_layernorm(net->sdt, tok, a, B.ln1.gamma, B.ln1.beta, M, C, 1e-5f, s));
             conv(B.qkv, Act{a, C, x.H, x.W}, qkv, x.H, x.W);
-            if (live()) chk(launch_token_attention(net->dt, qkv, o, nhyp, HW, C, 32, s));
+            if (live()) chk(launch_token_attention(net->dt, qkv, o, nhyp, HW, C, T.dh, s));
             conv(B.out1, Act{o, C, x.H, x.W}, tok1, x.H, x.W, tok);
             // attn2 against the single pose token: + to_out(to_v(context)) for every token -- this block's slice of u_all
             if (live()) chk(launch_add_rowvec(net->sdt, tok1, tok1, u_all + B.u_off, M, HW, C, s, net->u_total));
@@ -427,9 +461,14 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
     for (size_t b = 1; b < net->input_blocks.size(); ++b) {
         const LBlock& B = net->input_blocks[b];
         Act nxt;
-        if (B.has_resample) {            // Downsample: conv 3x3, stride 2, pad 1 (openaimodel.py:143-174)
-            nxt = Act{f.alloc_act((size_t)n_hyp * (curH / 2) * (curW / 2) * B.resample.Cout), B.resample.Cout, curH / 2, curW / 2};
-            f.conv(B.resample, h, nxt.p, curH / 2, curW / 2);
+        if (B.has_resample) {            // Downsample: conv 3x3, stride 2, pad 1 (openaimodel.py:143-174), or (no conv_resample) avg_pool 2x2
+            nxt = Act{f.alloc_act((size_t)n_hyp * (curH / 2) * (curW / 2) * h.C), h.C, curH / 2, curW / 2};
+            if (B.resample.w) f.conv(B.resample, h, nxt.p, curH / 2, curW / 2);
+            else f.pool(h, nxt.p);
+            curH /= 2; curW /= 2;
+        } else if (B.res.updown == RES_DOWN) {      // resblock_updown: ResBlock(down=True) in the Downsample slot
+            nxt = Act{f.alloc_act((size_t)n_hyp * (curH / 2) * (curW / 2) * B.res.Cout), B.res.Cout, curH / 2, curW / 2};
+            f.res(B.res, h, nxt.p);
             curH /= 2; curW /= 2;
         } else {
             nxt = Act{f.alloc_act((size_t)n_hyp * curH * curW * B.res.Cout), B.res.Cout, curH, curW};
@@ -471,9 +510,11 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
             f.st(B.st, r, t.p);
             r = t;
         }
-        if (B.has_resample) {            // Upsample: nearest x2 + conv 3x3 (openaimodel.py:93-124) as four 2x2 phase convs
-            Act u{f.alloc_act((size_t)M * 4 * B.resample.Cout), B.resample.Cout, curH * 2, curW * 2};
-            f.conv(B.resample, r, u.p, curH * 2, curW * 2);
+        if (B.has_resample) {            // Upsample: nearest x2 + conv 3x3 (openaimodel.py:93-124) as four 2x2 phase convs; nearest x2 alone
+            Act u{f.alloc_act((size_t)M * 4 * r.C), r.C, curH * 2, curW * 2};      // without conv_resample; resblock_updown: ResBlock(up=True)
+            if (B.up.updown == RES_UP) f.res(B.up, r, u.p);
+            else if (B.resample.w) f.conv(B.resample, r, u.p, curH * 2, curW * 2);
+            else f.up2(r, u.p);
             curH *= 2; curW *= 2;
             r = u;
         }
@@ -504,7 +545,12 @@ extern "C" {
 
 int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors, int n_tensors, nope_stream_t stream, nope_ldm** out) {
     if (!cfg || !tensors || !out || n_tensors <= 0) return NOPE_ERR_ARG;
-    if (cfg->n_levels < 1 || cfg->n_levels > 8 || cfg->num_res_blocks < 1 || cfg->num_head_channels != 32) return NOPE_ERR_UNSUPPORTED;
+    if (cfg->n_levels < 1 || cfg->n_levels > 8 || cfg->num_res_blocks < 1) return NOPE_ERR_UNSUPPORTED;
+    for (int l = 0; l < cfg->n_levels; ++l) {          // attention head widths the kernels have (kernels_ldm.hip): heads * width = the level's channels
+        if (!cfg->attn_levels[l] && l != cfg->n_levels - 1) continue;          // (the middle block attends at the last level's width)
+        const int dh = cfg->num_head_channels > 0 ? cfg->num_head_channels : cfg->head_channels[l];
+        if ((dh != 32 && dh != 64 && dh != 128) || (cfg->channel_mult[l] * cfg->model_channels) % dh) return NOPE_ERR_UNSUPPORTED;
+    }
     if (!dt_is_compute(cfg->compute_dtype)) return NOPE_ERR_UNSUPPORTED;
     if (cfg->pose_mlp_layers != 1 && cfg->pose_mlp_layers != 2) return NOPE_ERR_UNSUPPORTED;
     if (cfg->model_channels % 32 || cfg->in_channels < 1 || cfg->context_dim <= 0 || cfg->transformer_depth < 0 || cfg->transformer_depth > 16) return NOPE_ERR_UNSUPPORTED;
@@ -516,6 +562,7 @@ int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors,
     net->sdt = dt_storage(net->dt);
     net->emb_dim = cfg->model_channels * 4;
     const int mc = cfg->model_channels;
+    auto dh = [&](int level) { return cfg->num_head_channels > 0 ? cfg->num_head_channels : cfg->head_channels[level]; };
     Loader ld;
     ld.net = net; ld.s = s;
     for (int i = 0; i < n_tensors; ++i)
@@ -543,15 +590,19 @@ int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors,
             B.has_res = true;
             B.res = ld.res(p + "0.", ch, cfg->channel_mult[level] * mc);
             ch = cfg->channel_mult[level] * mc;
-            if (cfg->attn_levels[level]) { B.has_st = true; B.st = ld.st(p + "1.", ch); }
+            if (cfg->attn_levels[level]) { B.has_st = true; B.st = ld.st(p + "1.", ch, dh(level)); }
             net->input_blocks.push_back(B);
             chans.push_back(ch);
             ++idx;
         }
         if (level != cfg->n_levels - 1) {
             LBlock B;
-            B.has_resample = true;
-            B.resample = ld.conv("input_blocks." + std::to_string(idx) + ".0.op.", ch, ch, 3, NOPE_CONV_STRIDE2, true);
+            const std::string p = "input_blocks." + std::to_string(idx) + ".0.";
+            if (cfg->resblock_updown) { B.has_res = true; B.res = ld.res(p, ch, ch, RES_DOWN); }
+            else {
+                B.has_resample = true;
+                if (cfg->conv_resample) B.resample = ld.conv(p + "op.", ch, ch, 3, NOPE_CONV_STRIDE2, true);
+            }
             net->input_blocks.push_back(B);
             chans.push_back(ch);
             ++idx;
@@ -559,7 +610,7 @@ int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors,
     }
     // :618-648 -- middle block
     net->mid1 = ld.res("middle_block.0.", ch, ch);
-    net->mid_st = ld.st("middle_block.1.", ch);
+    net->mid_st = ld.st("middle_block.1.", ch, dh(cfg->n_levels - 1));
     net->mid2 = ld.res("middle_block.2.", ch, ch);
     // :651-731 -- output blocks
     idx = 0;
@@ -573,10 +624,11 @@ int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors,
             B.res = ld.res(p + "0.", ch + ich, mc * cfg->channel_mult[level]);
             ch = mc * cfg->channel_mult[level];
             int sub = 1;
-            if (cfg->attn_levels[level]) { B.has_st = true; B.st = ld.st(p + std::to_string(sub++) + ".", ch); }
+            if (cfg->attn_levels[level]) { B.has_st = true; B.st = ld.st(p + std::to_string(sub++) + ".", ch, dh(level)); }
             if (level && i == cfg->num_res_blocks) {
                 B.has_resample = true;
-                B.resample = ld.conv(p + std::to_string(sub) + ".conv.", ch, ch, 3, NOPE_CONV_UP2P, true);
+                if (cfg->resblock_updown) B.up = ld.res(p + std::to_string(sub) + ".", ch, ch, RES_UP);
+                else if (cfg->conv_resample) B.resample = ld.conv(p + std::to_string(sub) + ".conv.", ch, ch, 3, NOPE_CONV_UP2P, true);
             }
             net->output_blocks.push_back(B);
             ++idx;

@@ -454,6 +454,9 @@ int launch_geglu(int dt, const void* in, void* out, long long M, int D, hipStrea
 int launch_add_rowvec(int dt, const void* x, void* y, const float* u, long long M, int tokens, int C, hipStream_t s, int u_stride = 0);   // (u_stride 0 = C)
 int launch_token_attention(int dt, const void* qkv, void* out, int nsmp, int N, int C, int dim_head, hipStream_t s);
 int launch_copy_cols(int dt, const void* x, void* y, long long M, int C, int C2, int off, hipStream_t s);
+// NHWC x (n, H, W, C) -> y (n, H/2, W/2, C): 2x2 average pooling (H, W even); -> y (n, 2H, 2W, C): nearest x2 (storage dtypes)
+int launch_avg_pool2(int dt, const void* x, void* y, long long n, int H, int W, int C, hipStream_t s);
+int launch_nearest2(int dt, const void* x, void* y, long long n, int H, int W, int C, hipStream_t s);
 
 int launch_similarity(const float* q, const void* bank, int bank_dt, float* scores, int B, int N, int C, int HW,
                       long long bank_stride_b, int score_ld, hipStream_t s);

@@ -14,7 +14,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 6                          # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 7                          # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2 = 0, 1, 2, 3, 4
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -39,7 +39,7 @@ class LdmConfig(C.Structure):
     _fields_ = [("in_channels", _i), ("model_channels", _i), ("out_channels", _i), ("num_res_blocks", _i), ("n_levels", _i),
                 ("channel_mult", _i * 8), ("attn_levels", _i * 8), ("num_head_channels", _i), ("context_dim", _i), ("pose_dim", _i),
                 ("pose_mlp_layers", _i), ("injecting_condition_twice", _i), ("compute_dtype", _i), ("use_scale_shift_norm", _i),
-                ("transformer_depth", _i)]
+                ("transformer_depth", _i), ("head_channels", _i * 8), ("resblock_updown", _i), ("conv_resample", _i)]
 
 
 class ConvLaunchInfo(C.Structure):
@@ -668,6 +668,11 @@ class LdmHandle(_X2RangeMixin):
         c.compute_dtype = dtype_code(compute_dtype)
         c.use_scale_shift_norm = int(cfg.get("use_scale_shift_norm", 0))
         c.transformer_depth = int(cfg.get("transformer_depth", 1))
+        heads = tuple(cfg.get("head_channels", ()))          # per level (num_head_channels = 0); else num_head_channels everywhere
+        for i, d in enumerate(heads):
+            c.head_channels[i] = int(d)
+        c.resblock_updown = int(cfg.get("resblock_updown", 0))
+        c.conv_resample = int(cfg.get("conv_resample", 1))
         self.in_channels, self.out_channels, self.pose_dim = c.in_channels, c.out_channels, c.pose_dim
         descs, keep, dev = _tensor_descs(state_dict)
         self.device = dev
@@ -685,7 +690,9 @@ class LdmHandle(_X2RangeMixin):
             self._l.dll.nope_ldm_destroy(h)
             self._h = None
 
-    def forward(self, x: torch.Tensor, pose: torch.Tensor, x_rep: int = 1, out: Optional[torch.Tensor] = None, out_dtype=F32) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, pose: torch.Tensor, x_rep: int = 1, out: Optional[torch.Tensor] = None, out_dtype=F32,
+                defer_range_check: bool = False) -> torch.Tensor:
+        """As UNetHandle.forward: defer_range_check (NOPE_F16X2): the caller calls finish_range_check() itself before it hands results out."""
         require_device(x)
         x, pose = _f32c(x), _f32c(pose)
         n_src, Cc, H, W = x.shape
@@ -712,7 +719,8 @@ class LdmHandle(_X2RangeMixin):
         launch()
         if self._x2_mode() == "repeat" and self.x2_enabled:
             self._pending.append((launch, _stream(x)))
-            self.finish_range_check()
+            if not defer_range_check:
+                self.finish_range_check()
         return out
 
 

@@ -8,9 +8,15 @@ Same constructor arguments as the reference class (the ones configs/model/vae_ci
 -- and the same call `u_net(x, pose) -> pred`, so it plugs into `nope_amd.PoseConditional` exactly as `nope_amd.UNet` does
 (`forward_hypotheses` is the batched form `generate_templates` uses).  The module tree only holds parameters.
 
-Supported configuration: `use_spatial_transformer=True`, `transformer_depth=1`, `num_head_channels=32`,
-`conv_resample=True`, `use_scale_shift_norm` (FiLM ResBlocks) on or off, no `resblock_updown`, `pose_mlp_name`
-"single_layer" / "two_layers", `injecting_condition_twice` on or off; anything else raises NotImplementedError.
+Supported configuration: `use_spatial_transformer=True` with any `transformer_depth`; attention heads set by
+`num_head_channels` or `num_heads` (and `legacy`) exactly as the reference derives them per level (openaimodel.py:560-580,
+622-630, 666-690), as long as every level's head width is 32, 64 or 128 channels and divides the level's channels (else the
+reference's `inner_dim = heads * dim_head` differs from the channels); `conv_resample` and `resblock_updown` on or off;
+`use_scale_shift_norm` (FiLM ResBlocks) on or off; `pose_mlp_name` "single_layer" / "two_layers";
+`injecting_condition_twice` on or off.  `num_heads_upsample` and `use_new_attention_order` only reach the reference's
+`AttentionBlock`, which the spatial transformer replaces: accepted and ignored, as there.  Anything else raises
+NotImplementedError -- among it `use_spatial_transformer=False`, which the reference class cannot be built with either
+(openaimodel.py:491-495 asserts it whenever `context_dim` is set, and `pose_mlp` needs `context_dim`).
 """
 from __future__ import annotations
 
@@ -62,6 +68,24 @@ def _transformer_params(ch, context_dim, depth=1):
     return m
 
 
+def level_head_channels(ch, num_heads, num_head_channels, legacy):
+    """The attention head width of a level with `ch` channels, as openaimodel.py:566-576 derives it under use_spatial_transformer;
+    NotImplementedError unless it is 32, 64 or 128 and heads * width = ch (attention.py:152: inner_dim = heads * dim_head)."""
+    if num_head_channels == -1:
+        if num_heads == -1:
+            raise ValueError("either num_heads or num_head_channels has to be set")
+        heads, dim_head = num_heads, ch // num_heads
+    else:
+        heads, dim_head = ch // num_head_channels, num_head_channels
+    if legacy:
+        if heads < 1:
+            raise NotImplementedError(f"num_head_channels={num_head_channels} > {ch} channels: no attention head")
+        dim_head = ch // heads
+    if dim_head not in (32, 64, 128) or heads * dim_head != ch:
+        raise NotImplementedError(f"{ch} channels as {heads} attention heads of {dim_head}: head widths 32 / 64 / 128 dividing the channels only")
+    return dim_head
+
+
 class UNetModelPose(nn.Module):
     def __init__(self, injecting_condition_twice, pose_mlp_name, rot_representation_dim, encoder, image_size, in_channels,
                  model_channels, out_channels, num_res_blocks, attention_resolutions, dropout=0, channel_mult=(1, 2, 4, 8),
@@ -73,8 +97,7 @@ class UNetModelPose(nn.Module):
         if not use_spatial_transformer or transformer_depth < 1 or context_dim is None:
             raise NotImplementedError("only use_spatial_transformer=True (configs/model/vae_cin_ldm.yaml), transformer_depth >= 1")
         self.transformer_depth = int(transformer_depth)
-        if num_head_channels != 32 or resblock_updown or not conv_resample or dims != 2 \
-                or num_classes is not None or n_embed is not None:
+        if dims != 2 or num_classes is not None or n_embed is not None:
             raise NotImplementedError("unsupported UNetModel option (see module docstring)")
         if pose_mlp_name not in ("single_layer", "two_layers"):
             raise NotImplementedError(f"pose_mlp_name={pose_mlp_name!r}")
@@ -88,6 +111,12 @@ class UNetModelPose(nn.Module):
         self.injecting_condition_twice = bool(injecting_condition_twice)
         self.use_scale_shift_norm = film = bool(use_scale_shift_norm)
         self.compute_dtype = compute_dtype
+        self.resblock_updown, self.conv_resample = bool(resblock_updown), bool(conv_resample)
+        # per level (the middle block: the last level's); num_heads_upsample only reaches AttentionBlock (not built here, nor there)
+        # (levels without attention: no width -- 32 is a placeholder the library does not read)
+        last = len(self.channel_mult) - 1
+        self.head_channels = tuple(level_head_channels(mult * model_channels, num_heads, num_head_channels, legacy)
+                                   if (1 << l) in self.attention_resolutions or l == last else 32 for l, mult in enumerate(self.channel_mult))
         emb = model_channels * 4
         self.time_embed_dim = emb
         self.time_embed = _slot(nn.Linear(model_channels, emb), None, nn.Linear(emb, emb))           # present, never evaluated (timesteps skipped)
@@ -102,8 +131,11 @@ class UNetModelPose(nn.Module):
                 self.input_blocks.append(_slot(*layers))
                 chans.append(ch)
             if level != len(self.channel_mult) - 1:
-                down = _Params()
-                down.op = nn.Conv2d(ch, ch, 3, stride=2, padding=1)
+                down = _Params()                                                                      # :597-609 (Downsample :143-174)
+                if self.resblock_updown:
+                    down = _res_params(ch, ch, emb, film)
+                elif self.conv_resample:
+                    down.op = nn.Conv2d(ch, ch, 3, stride=2, padding=1)
                 self.input_blocks.append(_slot(down))
                 chans.append(ch)
                 ds *= 2
@@ -117,8 +149,11 @@ class UNetModelPose(nn.Module):
                 if ds in self.attention_resolutions:
                     layers.append(_transformer_params(ch, context_dim, transformer_depth))
                 if level and i == num_res_blocks:
-                    up = _Params()
-                    up.conv = nn.Conv2d(ch, ch, 3, padding=1)
+                    up = _Params()                                                                    # :711-727 (Upsample :94-124)
+                    if self.resblock_updown:
+                        up = _res_params(ch, ch, emb, film)
+                    elif self.conv_resample:
+                        up.conv = nn.Conv2d(ch, ch, 3, padding=1)
                     layers.append(up)
                     ds //= 2
                 self.output_blocks.append(_slot(*layers))
@@ -160,7 +195,8 @@ class UNetModelPose(nn.Module):
             cfg = dict(in_channels=self.in_channels, model_channels=self.model_channels, out_channels=self.out_channels,
                        num_res_blocks=self.num_res_blocks, channel_mult=self.channel_mult,
                        attn_levels=tuple(int((1 << l) in self.attention_resolutions) for l in range(levels)),
-                       num_head_channels=32, context_dim=self.context_dim, pose_dim=self.rot_representation_dim,
+                       num_head_channels=0, head_channels=self.head_channels, resblock_updown=int(self.resblock_updown),
+                       conv_resample=int(self.conv_resample), context_dim=self.context_dim, pose_dim=self.rot_representation_dim,
                        pose_mlp_layers=self._pose_layers, injecting_condition_twice=int(self.injecting_condition_twice),
                        use_scale_shift_norm=int(self.use_scale_shift_norm), transformer_depth=self.transformer_depth)
             self._handle = hip.LdmHandle(cfg, sd, hip.dtype_code(self.compute_dtype))
@@ -173,10 +209,15 @@ class UNetModelPose(nn.Module):
         return self._get_handle(x.device).forward(x, pose, x_rep=1)
 
     @torch.no_grad()
-    def forward_hypotheses(self, x, poses, out=None, out_dtype="f32"):
-        """x (B,C,h,w) reference latents, poses (B,N,rot_dim) -> (B,N,C,h,w): the body of the template loop model.py:212-222."""
+    def forward_hypotheses(self, x, poses, out=None, out_dtype="f32", defer_range_check=False):
+        """x (B,C,h,w) reference latents, poses (B,N,rot_dim) -> (B,N,C,h,w): the body of the template loop model.py:212-222.
+        defer_range_check (f16x2): the caller calls finish_range_check() before it reads the output (as nope_amd.UNet)."""
         B, N = poses.shape[:2]
         flat = poses.reshape(B * N, poses.shape[-1])
         o = None if out is None else out.view(B * N, *out.shape[2:])
-        y = self._get_handle(x.device).forward(x, flat, x_rep=N, out=o, out_dtype=hip.dtype_code(out_dtype))
+        y = self._get_handle(x.device).forward(x, flat, x_rep=N, out=o, out_dtype=hip.dtype_code(out_dtype), defer_range_check=defer_range_check)
         return y.view(B, N, *y.shape[1:])
+
+    def finish_range_check(self) -> bool:
+        """f16x2: check (and if needed repeat) the forwards issued with defer_range_check; True when any was repeated (hip.LdmHandle)."""
+        return self._handle.finish_range_check() if self._handle is not None else False
