@@ -54,7 +54,10 @@ enum { NOPE_F32 = 0, NOPE_BF16 = 1,
  * 2x2 convolutions over the un-upsampled input, one per output-pixel parity, with the 3x3 weights that
  * fall on the same source pixel pre-summed at pack time: same function, 4/9 of the multiply-adds. */
 enum { NOPE_CONV_PLAIN = 0, NOPE_CONV_UP2 = 1, NOPE_CONV_DOWN2 = 2, NOPE_CONV_UP2P = 3,
-       NOPE_CONV_STRIDE2 = 4 /* stride 2: 3x3 pad 1 or 1x1 pad 0 (ResNet Bottleneck, encoder/resnet.py:64-65,122-123), 4x4 pad 1 (Downsample, model_utils.py:129-136) */ };
+       NOPE_CONV_STRIDE2 = 4 /* stride 2: 3x3 pad 1 or 1x1 pad 0 (ResNet Bottleneck, encoder/resnet.py:64-65,122-123), 4x4 pad 1 (Downsample, model_utils.py:129-136) */,
+       NOPE_CONV_STRIDE2_PAD01 = 5 /* (ABI 8) 3x3 stride 2 after a (0, 1, 0, 1) zero pad, no padding of its own: output (oy, ox) reads source rows / columns
+                                      2 oy .. 2 oy + 2 (the Stable Diffusion VAE's Downsample, u_net/ldm/model.py:57-74; diffusers' Downsample2D(padding=0)).
+                                      3x3 only, one source, even source size; weights packed as NOPE_CONV_STRIDE2's */ };
 enum {
     NOPE_OK = 0,
     NOPE_ERR_ARG = -1,        /* bad argument (null pointer, unsupported size/dtype) */
@@ -74,9 +77,10 @@ typedef void* nope_stream_t;
  * 4: nope_op_geodesic, nope_unet_graph_limit -- hipGraph replay became opt-in;
  * 5: NOPE_F16X2, nope_tuning_reload, nope_gather_topk, nope_topk_merge;
  * 6: nope_unet_x2_poll / _x2_range_check / _x2_enable / _x2_shifts, NOPE_ERR_RANGE*;
- * 7: nope_ldm_config.head_channels / resblock_updown / conv_resample, nope_op_token_attention dim_head 64 / 128).  Callers compare nope_abi_version() against the header they were
+ * 7: nope_ldm_config.head_channels / resblock_updown / conv_resample, nope_op_token_attention dim_head 64 / 128;
+ * 8: NOPE_CONV_STRIDE2_PAD01, nope_op_wide_attention, nope_vae_*).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 7
+#define NOPE_ABI_VERSION 8
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -360,6 +364,50 @@ int nope_op_warp_perspective(const void* src, int src_is_u8, int Hs, int Ws, int
 int nope_op_layer_norm(int dtype, const void* x, void* y, const float* gamma, const float* beta, int64_t M, int C, float eps, nope_stream_t s);
 int nope_op_geglu(int dtype, const void* in, void* out, int64_t M, int D, nope_stream_t s);
 int nope_op_token_attention(int dtype, const void* qkv, void* out, int n, int N, int C, int dim_head, nope_stream_t s);
+/* (ABI 8) ONE attention head as wide as the channels, C = 256 or 512, on the same fused [n][N][3C] q|k|v layout, scale C^-1/2: the mid-block
+ * AttnBlock of the Stable Diffusion VAE (u_net/ldm/model.py:144-187; diffusers 0.14 AttentionBlock with one head).  dtype as
+ * nope_op_token_attention.  Every mode runs the all-f32 VALU kernel of nope_op_token_attention with the head split over 8 / 16 lanes, on
+ * the mode's storage type: the 16-bit modes read bf16 / f16 q, k, v and compute in f32 (more accurate than their matrix-core kernels, slower).
+ * Other C: NOPE_ERR_ARG. */
+int nope_op_wide_attention(int dtype, const void* qkv, void* out, int n, int N, int C, nope_stream_t s);
+
+/* ------------------------------------------------------------------------------------------
+ * Stable Diffusion VAE (ABI 8).  Replaces VAE_StableDiffusion.encode_image / decode_latent, src/model/encoder/AutoencoderKL.py:28-47, over
+ * diffusers' AutoencoderKL (the CompVis Encoder / Decoder, src/model/u_net/ldm/model.py:77-448: ResnetBlock, AttnBlock, Downsample,
+ * Upsample).  Tensor names are AutoencoderKL's own state-dict keys in the diffusers 0.14 spelling ("encoder.down_blocks.0.resnets.0.conv1.weight",
+ * "encoder.mid_block.attentions.0.query.weight" [C][C], "quant_conv.weight", "decoder.up_blocks.0.upsamplers.0.conv.weight", ...).
+ * Supported: every down block DownEncoderBlock2D, every up block UpDecoderBlock2D, act_fn silu, one mid-block attention head as wide as the
+ * last level's channels (32 / 64 / 128: nope_op_token_attention's kernels; 256 / 512: nope_op_wide_attention).
+ * NHWC activations; GroupNorm + SiLU and the 3x3 / 1x1 convolutions on the kernels of the U-Nets; Downsample as NOPE_CONV_STRIDE2_PAD01,
+ * Upsample as the NOPE_CONV_UP2P phase conv; 0.18215 and its inverse folded into quant_conv / post_quant_conv at create time. */
+typedef struct nope_vae nope_vae;
+typedef struct {
+    int in_channels;            /* 3 (any count: the input convs' K axis is zero-padded to a multiple of 8 at pack time) */
+    int out_channels;           /* 3 */
+    int n_levels;               /* len(block_out_channels) = 4 */
+    int block_out_channels[8];  /* (128, 256, 512, 512); multiples of 32 */
+    int layers_per_block;       /* 2: ResnetBlock2Ds per down block (an up block has one more) */
+    int latent_channels;        /* 4 */
+    int norm_num_groups;        /* 32 */
+    int compute_dtype;          /* NOPE_F32 | NOPE_BF16 | NOPE_F16 | NOPE_BF16X3 | NOPE_F16X2 (= NOPE_BF16X3 here: no second weight pack, no range tracking) */
+    float gn_eps;               /* GroupNorm eps; <= 0 selects 1e-6 (model.py:35-38) */
+} nope_vae_config;
+
+int nope_vae_create(const nope_vae_config* cfg, const nope_tensor_desc* tensors, int n_tensors, nope_stream_t stream, nope_vae** out);
+void nope_vae_destroy(nope_vae* vae);
+/* Workspace of ONE chunk of n_img samples: decode = 0 -> encode of (n_img, in_channels, H, W) images; decode = 1 -> decode of (n_img,
+ * latent_channels, H, W) latents.  0 for an unsupported size. */
+size_t nope_vae_workspace_bytes(const nope_vae* vae, int decode, int n_img, int H, int W);
+/* image (n_img, in_channels, H, W) f32 NCHW, H and W multiples of 2^(n_levels - 1) -> latent (n_img, latent_channels, H / f, W / f) f32 NCHW:
+ * quant_conv(Encoder(image))[:, :latent_channels] * 0.18215 (the mode of the latent distribution, AutoencoderKL.py:33-34).
+ * The batch runs in chunks of the largest sample count whose workspace fits workspace_bytes (NOPE_ERR_WORKSPACE if one sample does not). */
+int nope_vae_encode(const nope_vae* vae, const float* image, int n_img, int H, int W, float* latent, void* workspace, size_t workspace_bytes,
+                    nope_stream_t stream);
+/* latent (n_img, latent_channels, h, w) f32 NCHW -> image (n_img, out_channels, f h, f w) f32 NCHW: Decoder(post_quant_conv(latent / 0.18215))
+ * (AutoencoderKL.py:44-47); unnormalize = 1: (image + 1) / 2 (unnormalize_to_zero_to_one, PoseConditional.sample), folded into the output
+ * conv's weights and bias.  Chunked as nope_vae_encode. */
+int nope_vae_decode(const nope_vae* vae, const float* latent, int n_img, int h, int w, float* image, int unnormalize, void* workspace,
+                    size_t workspace_bytes, nope_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -85,7 +85,7 @@ static void fill_conv_args(ConvArgs& a, const void* src1, int C1, int rep1, cons
     a.src1 = src1; a.C1 = C1; a.rep1 = rep1; a.src2 = src2; a.C2 = C2; a.rep2 = rep2 > 0 ? rep2 : 1;
     a.Hs = Hs; a.Ws = Ws; a.mode = mode; a.ntaps = ntaps;
     const bool up = mode == NOPE_CONV_UP2 || mode == NOPE_CONV_UP2P;
-    const bool half = mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2;
+    const bool half = mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2 || mode == NOPE_CONV_STRIDE2_PAD01;
     a.Ho = up ? 2 * Hs : (half ? Hs / 2 : Hs);
     a.Wo = up ? 2 * Ws : (half ? Ws / 2 : Ws);
     a.act = act_relu ? 1 : 0;
@@ -98,7 +98,7 @@ int nope_op_conv_ws(int dtype, const void* src1, int C1, int rep1, const void* s
                     int out_nchw, int out_dtype, int act_relu, void* splitk_ws, size_t splitk_bytes, nope_stream_t s) {
     ConvArgs a;
     fill_conv_args(a, src1, C1, rep1, src2, C2, rep2, Hs, Ws, mode, ntaps, w_packed, bias, resid, out, Cout, n_hyp, out_nchw, out_dtype, act_relu);
-    if ((mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2) && ((Hs | Ws) & 1)) return NOPE_ERR_ARG;
+    if ((mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2 || mode == NOPE_CONV_STRIDE2_PAD01) && ((Hs | Ws) & 1)) return NOPE_ERR_ARG;
     a.splitk_ws = splitk_ws; a.splitk_bytes = splitk_ws ? splitk_bytes : 0;
     return launch_conv(dtype, a, (hipStream_t)s);
 }
@@ -153,6 +153,9 @@ int nope_op_geglu(int dtype, const void* in, void* out, int64_t M, int D, nope_s
 }
 int nope_op_token_attention(int dtype, const void* qkv, void* out, int n, int N, int C, int dim_head, nope_stream_t s) {
     return launch_token_attention(dtype, qkv, out, n, N, C, dim_head, (hipStream_t)s);
+}
+int nope_op_wide_attention(int dtype, const void* qkv, void* out, int n, int N, int C, nope_stream_t s) {
+    return launch_wide_attention(dtype, qkv, out, n, N, C, (hipStream_t)s);
 }
 int nope_op_warp_perspective(const void* src, int src_is_u8, int Hs, int Ws, int C, const float* minv9_host, float* dst_chw, int Hd, int Wd,
                              float scale, float shift, nope_stream_t s) {

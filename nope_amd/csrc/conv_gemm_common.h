@@ -77,6 +77,7 @@ struct ConvParams {
     int x2_t_zero;                     // NOPE_F16X2: the caller vouches that the layer's range shift (tail word 3) is 0: the tap-resident kernel skips the a * 2^-t multiplies
     int lean;                          // 1: f32 storage, every wave tile of the launch whole and in NHWC row order (see epilogue_wide, LEANM): the kernels' LEAN instantiations
     unsigned* out_amax;                // f32-storage launches with a wide NHWC epilogue: optional range slot (amax_publish) for max |out| of what the launch writes
+    int s2_off;                        // STRIDE2: 0 = centre tap at (2 oy, 2 ox) (pad 1), 1 = at (2 oy + 1, 2 ox + 1) (NOPE_CONV_STRIDE2_PAD01: pad (0, 1, 0, 1))
 };
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;

@@ -131,10 +131,11 @@ __global__ __launch_bounds__(BMT * 2, 2) void conv_gemm_dma_kernel(ConvParams p)
             a_b1[i] = (((s1 * p.Hs + 2 * oy) * p.Ws + 2 * ox) * p.C1 + cs) * ES;
             a_b2[i] = 0;
             mask = 0xfu;
-        } else if (MODE == NOPE_CONV_STRIDE2) {   // centre tap at source pixel (2 oy, 2 ox)
-            a_b1[i] = (((s1 * p.Hs + 2 * oy) * p.Ws + 2 * ox) * p.C1 + cs) * ES;
+        } else if (MODE == NOPE_CONV_STRIDE2) {   // centre tap at source pixel (2 oy + s2_off, 2 ox + s2_off)
+            const int cy = 2 * oy + p.s2_off, cx = 2 * ox + p.s2_off;
+            a_b1[i] = (((s1 * p.Hs + cy) * p.Ws + cx) * p.C1 + cs) * ES;
             a_b2[i] = 0;
-            mask = p.ntaps == 9 ? mask3x3(2 * oy, 2 * ox, p.Hs, p.Ws) : 1u;
+            mask = p.ntaps == 9 ? mask3x3(cy, cx, p.Hs, p.Ws) : 1u;
         } else {   // UP2: source row/col of the 3 vertical / horizontal taps in the upsampled image
 #pragma unroll
             for (int d = 0; d < 3; ++d) {

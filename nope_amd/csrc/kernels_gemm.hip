@@ -110,8 +110,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* _
 // Source pixel of output pixel (oy, ox) under tap (dy, dx); false = zero padding / beyond M.
 __device__ __forceinline__ bool tap_pixel(const ConvParams& p, int oy, int ox, int dy, int dx, int& iy, int& ix) {
     if (p.mode == NOPE_CONV_DOWN2) { iy = 2 * oy + dy; ix = 2 * ox + dx; return oy >= 0; }
-    if (p.mode == NOPE_CONV_STRIDE2) {   // stride 2, pad 1 (3x3) / pad 0 (1x1)
-        iy = 2 * oy + dy; ix = 2 * ox + dx;
+    if (p.mode == NOPE_CONV_STRIDE2) {   // stride 2, pad 1 (3x3) / pad 0 (1x1); s2_off = 1: 3x3 with pad (0, 1, 0, 1) (NOPE_CONV_STRIDE2_PAD01)
+        iy = 2 * oy + dy + p.s2_off; ix = 2 * ox + dx + p.s2_off;
         return oy >= 0 && iy >= 0 && iy < p.Hs && ix >= 0 && ix < p.Ws;
     }
     if (p.mode == NOPE_CONV_UP2P) {   // rows are source pixels; (dy, dx) already include the phase shift
@@ -507,6 +507,14 @@ int conv_splitk_factor(int dt, const ConvArgs& a) {
 }
 
 int launch_conv(int dt, const ConvArgs& a, hipStream_t s) {
+    if (a.mode == NOPE_CONV_STRIDE2_PAD01) {      // Downsample2D(padding=0) / CompVis Downsample: pad (0, 1, 0, 1), 3x3, stride 2, no padding --
+        // the STRIDE2 tiles with the centre tap one source pixel down and right; the bottom / right taps of the last row / column read the padding
+        if (a.ntaps != 9 || a.C2 != 0 || a.s2_off != 0) return NOPE_ERR_ARG;
+        ConvArgs b = a;
+        b.mode = NOPE_CONV_STRIDE2; b.s2_off = 1;
+        return launch_conv(dt, b, s);
+    }
+    if (a.s2_off && (a.mode != NOPE_CONV_STRIDE2 || a.ntaps != 9 || a.s2_off != 1)) return NOPE_ERR_ARG;
     if (dt == NOPE_F16X2) {      // as an element type (nope_op_conv): `w` is in the NOPE_F16X2 layout, which only the ping-pong kernels read
         if (a.w_x2) return NOPE_ERR_ARG;
         ConvArgs b = a;
@@ -541,7 +549,7 @@ int launch_conv(int dt, const ConvArgs& a, hipStream_t s) {
     p.C1 = a.C1; p.C2 = a.C2; p.rep1 = a.rep1; p.rep2 = a.rep2;
     p.Hs = a.Hs; p.Ws = a.Ws; p.Ho = a.Ho; p.Wo = a.Wo;
     p.Hm = phased ? a.Hs : a.Ho; p.Wm = phased ? a.Ws : a.Wo;
-    p.mode = a.mode; p.ntaps = a.ntaps;
+    p.mode = a.mode; p.ntaps = a.ntaps; p.s2_off = a.s2_off;
     p.w = (const unsigned char*)a.w; p.bias = a.bias; p.resid = (const unsigned char*)a.resid;
     p.out = (unsigned char*)a.out; p.Cout = a.Cout; p.M = (int)M;
     p.out_nchw = a.out_nchw; p.out_dt = a.out_dt;

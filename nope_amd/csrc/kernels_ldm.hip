@@ -625,6 +625,20 @@ int launch_token_attention(int dt, const void* qkv, void* out, int nsmp, int N, 
     return NOPE_OK;
 }
 
+// ONE head as wide as the channels, C = 256 / 512 (the Stable Diffusion VAE's mid-block AttnBlock, u_net/ldm/model.py:144-187): the VALU kernel above
+// with the head split over C / 32 = 8 / 16 lanes (q and the output accumulator stay 64 VGPRs per lane; 16 / 8 keys per LDS chunk, 32 KiB).  Every
+// compute mode runs it on its storage type, f32 arithmetic: the op is ~2.1 GFLOP per 1 024-token sample, under 1 % of the VAE decoder's work.
+int launch_wide_attention(int dt, const void* qkv, void* out, int nsmp, int N, int C, hipStream_t s) {
+    if (!qkv || !out || nsmp <= 0 || N <= 0 || (C != 256 && C != 512) || !dt_is_compute(dt)) return NOPE_ERR_ARG;
+    const int sdt = dt_storage(dt);
+    const float scale = 1.0f / sqrtf((float)C);
+    const dim3 grid((unsigned)cdiv(N, NT / (C / AD)), 1u, (unsigned)nsmp);
+    if (C == 256) { NOPE_DISPATCH_T(sdt, T, hipLaunchKernelGGL((token_attn_kernel<T, 256>), grid, dim3(NT), 0, s, (const T*)qkv, (T*)out, N, C, scale)); }
+    else { NOPE_DISPATCH_T(sdt, T, hipLaunchKernelGGL((token_attn_kernel<T, 512>), grid, dim3(NT), 0, s, (const T*)qkv, (T*)out, N, C, scale)); }
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
 int launch_avg_pool2(int dt, const void* x, void* y, long long n, int H, int W, int C, hipStream_t s) {
     const int vec = dt_vec(dt);
     if (!x || !y || n <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % vec) return NOPE_ERR_ARG;

@@ -338,7 +338,7 @@ struct ConvArgs {
     int rep1 = 1, rep2 = 1;      // source sample = hypothesis / rep  (broadcast of shared tensors)
     int Hs = 1, Ws = 1;          // source spatial size
     int Ho = 1, Wo = 1;          // output spatial size
-    int mode = NOPE_CONV_PLAIN;  // NOPE_CONV_PLAIN | UP2 | DOWN2 | UP2P | STRIDE2
+    int mode = NOPE_CONV_PLAIN;  // NOPE_CONV_PLAIN | UP2 | DOWN2 | UP2P | STRIDE2 | STRIDE2_PAD01 (launch_conv runs the last as STRIDE2 with s2_off = 1)
     int ntaps = 1;               // 1 or 9 (PLAIN, STRIDE2), 9 (UP2), 4 (DOWN2, UP2P)
     const void* w = nullptr;     // packed [Cout][ntaps][Cin]
     const void* w_x2 = nullptr;  // NOPE_BF16X3 launches only: the same weights in the NOPE_F16X2 layout (launch_pack_conv_w_x2) -- taken, with
@@ -369,6 +369,7 @@ struct ConvArgs {
     // the caller interleaved the weight rows -- and out is [M][Cout / 2] = x_j * gelu(gate_j).  16-bit types, 1x1, 128 x 192 kernel only
     // (conv_geglu_fusable); same operands (rounded to the storage type) and same formula as geglu_kernel: bit-identical to conv + geglu.
     int geglu = 0;
+    int s2_off = 0;              // STRIDE2 3x3: centre tap at source pixel (2 oy + s2_off, 2 ox + s2_off) -- set by launch_conv for NOPE_CONV_STRIDE2_PAD01
 };
 int launch_conv(int dt, const ConvArgs& a, hipStream_t s);
 bool conv_geglu_fusable(int dt, const ConvArgs& a);   // would launch_conv take this conv with geglu = 1?
@@ -453,6 +454,7 @@ int launch_layernorm(int dt, const void* x, void* y, const float* gamma, const f
 int launch_geglu(int dt, const void* in, void* out, long long M, int D, hipStream_t s, int interleaved = 0);   // interleaved: in = (x_j, gate_j) pairs
 int launch_add_rowvec(int dt, const void* x, void* y, const float* u, long long M, int tokens, int C, hipStream_t s, int u_stride = 0);   // (u_stride 0 = C)
 int launch_token_attention(int dt, const void* qkv, void* out, int nsmp, int N, int C, int dim_head, hipStream_t s);
+int launch_wide_attention(int dt, const void* qkv, void* out, int nsmp, int N, int C, hipStream_t s);      // one head of C = 256 / 512 channels
 int launch_copy_cols(int dt, const void* x, void* y, long long M, int C, int C2, int off, hipStream_t s);
 // NHWC x (n, H, W, C) -> y (n, H/2, W/2, C): 2x2 average pooling (H, W even); -> y (n, 2H, 2W, C): nearest x2 (storage dtypes)
 int launch_avg_pool2(int dt, const void* x, void* y, long long n, int H, int W, int C, hipStream_t s);

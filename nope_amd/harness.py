@@ -90,14 +90,22 @@ def synthetic_batch(batch: int, n_templates: int, size: int, seed: int = 2022, d
 
 
 def build_model(seed: int = 2022, compute_dtype="f32", bank_dtype="f32", device="cuda", u_net_dim: Optional[int] = None,
-                save_dir: Optional[str] = None, template_parallel: bool = False, max_hypotheses_per_launch: int = 512):
+                save_dir: Optional[str] = None, template_parallel: bool = False, max_hypotheses_per_launch: int = 512, encoder: str = "template"):
+    """encoder: "template" (template_base.yaml's FeatureExtractor) or "vae" (vae_base.yaml's VAE_StableDiffusion at the SD-1.5 shapes,
+    synthetic weights: images -> 4-channel latents -> the U-Net -> retrieval on the latents)."""
     from .encoder import FeatureExtractor
     from .model import PoseConditional
     from .u_net import UNet
     from .weights import synth_init_
     cfg = TEMPLATE_BASE
-    enc = FeatureExtractor(**cfg["u_net"]["encoder"], compute_dtype=compute_dtype)
-    synth_init_(enc, seed, prefix="encoder.")
+    if encoder == "vae":
+        from .vae import SD15_CONFIG, VAE_StableDiffusion
+        enc = VAE_StableDiffusion(None, latent_dim=4, config=SD15_CONFIG, compute_dtype=compute_dtype).synth_init_(seed)
+    elif encoder == "template":
+        enc = FeatureExtractor(**cfg["u_net"]["encoder"], compute_dtype=compute_dtype)
+        synth_init_(enc, seed, prefix="encoder.")
+    else:
+        raise ValueError(f"encoder {encoder!r}: 'template' or 'vae'")
     unet = UNet(u_net_dim=u_net_dim or cfg["u_net"]["u_net_dim"], rot_representation_dim=6, encoder=enc,
                 pose_mlp_name=cfg["u_net"]["pose_mlp_name"], compute_dtype=compute_dtype)
     # U-Net tensors are keyed without the "encoder." prefix; the encoder was initialised above
@@ -149,10 +157,12 @@ def main(argv=None):
     ap.add_argument("--pose-level", type=int, default=None, choices=[0, 1, 2, 3],
                     help="use the upper-hemisphere icosphere grid (26/91/341/1321 templates) instead of --templates random poses")
     ap.add_argument("--pose-root", default=None, help="directory with the reference's predefined_poses/*.npy")
+    ap.add_argument("--encoder", default="template", choices=["template", "vae"],
+                    help="vae: the Stable Diffusion VAE at the SD-1.5 shapes (synthetic weights) in place of the template encoder")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("nope_amd.harness needs an MI355X (no CPU fallback)")
-    model = build_model(a.seed, a.dtype, a.bank_dtype, "cuda", save_dir=a.save_dir)
+    model = build_model(a.seed, a.dtype, a.bank_dtype, "cuda", save_dir=a.save_dir, encoder=a.encoder)
     batches = {f"shapeNet_{a.category}": synthetic_batch(a.batch, a.templates, a.size, a.seed, "cuda", pose_level=a.pose_level,
                                                                   pose_root=a.pose_root)}
     for name, batch in batches.items():                         # test_step, model.py:550-565

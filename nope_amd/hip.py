@@ -14,8 +14,8 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 7                          # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
-CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2 = 0, 1, 2, 3, 4
+ABI_VERSION = 8                          # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +40,11 @@ class LdmConfig(C.Structure):
                 ("channel_mult", _i * 8), ("attn_levels", _i * 8), ("num_head_channels", _i), ("context_dim", _i), ("pose_dim", _i),
                 ("pose_mlp_layers", _i), ("injecting_condition_twice", _i), ("compute_dtype", _i), ("use_scale_shift_norm", _i),
                 ("transformer_depth", _i), ("head_channels", _i * 8), ("resblock_updown", _i), ("conv_resample", _i)]
+
+
+class VaeConfig(C.Structure):
+    _fields_ = [("in_channels", _i), ("out_channels", _i), ("n_levels", _i), ("block_out_channels", _i * 8), ("layers_per_block", _i),
+                ("latent_channels", _i), ("norm_num_groups", _i), ("compute_dtype", _i), ("gn_eps", C.c_float)]
 
 
 class ConvLaunchInfo(C.Structure):
@@ -103,6 +108,12 @@ _PROTOS = {
     "nope_op_layer_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, _vp]),
     "nope_op_geglu": (_i, [_i, _vp, _vp, _i64, _i, _vp]),
     "nope_op_token_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "nope_op_wide_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
+    "nope_vae_create": (_i, [C.POINTER(VaeConfig), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)]),
+    "nope_vae_destroy": (None, [_vp]),
+    "nope_vae_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "nope_vae_encode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "nope_vae_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -767,6 +778,109 @@ def op_token_attention(dt: int, qkv: torch.Tensor, dim_head: int = 32) -> torch.
     return out
 
 
+def op_wide_attention(dt: int, qkv: torch.Tensor) -> torch.Tensor:
+    """qkv (n, N, 3C), C = 256 / 512 -> softmax(q k^T / sqrt(C)) v with ONE head of all C channels, (n, N, C)."""
+    n, N, c3 = qkv.shape
+    out = torch.empty((n, N, c3 // 3), dtype=qkv.dtype, device=qkv.device)
+    l = lib()
+    l.check(l.dll.nope_op_wide_attention(dt, _ptr(qkv), _ptr(out), n, N, c3 // 3, _stream(qkv)), "nope_op_wide_attention")
+    return out
+
+
+# --------------------------------------------------------------------------------------------
+# Stable Diffusion VAE handle
+# --------------------------------------------------------------------------------------------
+class VaeHandle:
+    """Owns a `nope_vae*` built from an AutoencoderKL state dict (diffusers 0.14 keys, without the wrapper's `encoder.` prefix)."""
+
+    def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], compute_dtype=F32, max_workspace_bytes: int = 4 << 30):
+        l = lib()
+        self._l = l
+        c = VaeConfig()
+        boc = tuple(int(v) for v in cfg["block_out_channels"])
+        c.in_channels, c.out_channels = int(cfg["in_channels"]), int(cfg["out_channels"])
+        c.n_levels = len(boc)
+        for i, v in enumerate(boc):
+            c.block_out_channels[i] = v
+        c.layers_per_block, c.latent_channels = int(cfg["layers_per_block"]), int(cfg["latent_channels"])
+        c.norm_num_groups = int(cfg["norm_num_groups"])
+        c.compute_dtype = dtype_code(compute_dtype)
+        c.gn_eps = 1e-6
+        self.in_channels, self.out_channels, self.latent_channels = c.in_channels, c.out_channels, c.latent_channels
+        self.factor = 2 ** (c.n_levels - 1)
+        self.compute_dtype = c.compute_dtype
+        self.max_workspace_bytes = int(max_workspace_bytes)
+        descs, keep, dev = _tensor_descs(state_dict)
+        self.device = dev
+        h = _vp()
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else 0
+        l.check(l.dll.nope_vae_create(C.byref(c), descs, len(state_dict), stream, C.byref(h)), "nope_vae_create")
+        self._h = h
+        self._ws: Dict[tuple, torch.Tensor] = {}
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._l.dll.nope_vae_destroy(h)
+            self._h = None
+
+    def _workspace(self, x: torch.Tensor, decode: int, n: int, H: int, W: int) -> torch.Tensor:
+        """The workspace of the largest chunk of at most n samples within max_workspace_bytes (the library runs the batch chunk by chunk)."""
+        one = int(self._l.dll.nope_vae_workspace_bytes(self._h, decode, 1, H, W))
+        if one == 0:
+            raise NopeError(f"unsupported VAE {'latent' if decode else 'image'} size {H}x{W}")
+        need = one
+        lo, hi = 1, n
+        while lo < hi:          # (the library picks the same chunk from the bytes it is given)
+            mid = (lo + hi + 1) // 2
+            b = int(self._l.dll.nope_vae_workspace_bytes(self._h, decode, mid, H, W))
+            if b and b <= self.max_workspace_bytes:
+                lo, need = mid, b
+            else:
+                hi = mid - 1
+        if lo == 1:
+            need = one
+        key = (str(x.device), _stream(x))
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            self._ws.pop(key, None)
+            ws = None
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
+        return ws
+
+    def encode(self, image: torch.Tensor) -> torch.Tensor:
+        """image (B, in_channels, H, W) f32 -> latent (B, latent_channels, H/f, W/f) f32 (x 0.18215)."""
+        require_device(image)
+        image = _f32c(image)
+        B, Cc, H, W = image.shape
+        if Cc != self.in_channels or H % self.factor or W % self.factor:
+            raise NopeError(f"VAE encode: image {tuple(image.shape)} (needs {self.in_channels} channels, sides multiples of {self.factor})")
+        out = torch.empty((B, self.latent_channels, H // self.factor, W // self.factor), dtype=torch.float32, device=image.device)
+        if B == 0:
+            return out
+        ws = self._workspace(image, 0, B, H, W)
+        self._l.check(self._l.dll.nope_vae_encode(self._h, _ptr(image), B, H, W, _ptr(out), _ptr(ws), ws.numel(), _stream(image)), "nope_vae_encode")
+        return out
+
+    def decode(self, latent: torch.Tensor, unnormalize: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """latent (B, latent_channels, h, w) f32 -> image (B, out_channels, f h, f w) f32; unnormalize: (image + 1) / 2."""
+        require_device(latent)
+        latent = _f32c(latent)
+        B, Cc, h, w = latent.shape
+        if Cc != self.latent_channels:
+            raise NopeError(f"VAE decode: latent {tuple(latent.shape)} (needs {self.latent_channels} channels)")
+        shape = (B, self.out_channels, h * self.factor, w * self.factor)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=latent.device)
+        assert out.is_contiguous() and tuple(out.shape) == shape and out.dtype == torch.float32
+        if B == 0:
+            return out
+        ws = self._workspace(latent, 1, B, h, w)
+        self._l.check(self._l.dll.nope_vae_decode(self._h, _ptr(latent), B, h, w, _ptr(out), int(unnormalize), _ptr(ws), ws.numel(),
+                                                  _stream(latent)), "nope_vae_decode")
+        return out
+
+
 # --------------------------------------------------------------------------------------------
 # operator-level wrappers (parity tests of single blocks; NCHW f32 in/out at the boundary)
 # --------------------------------------------------------------------------------------------
@@ -820,7 +934,7 @@ def op_conv(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
     c2 = 0 if src2 is None else src2.shape[3]
     assert c1 + c2 == cin
     n_hyp = n_hyp if n_hyp is not None else n1 * rep1
-    ho, wo = (2 * hs, 2 * ws) if mode in (CONV_UP2, CONV_UP2P) else ((hs // 2, ws // 2) if mode in (CONV_DOWN2, CONV_STRIDE2) else (hs, ws))
+    ho, wo = (2 * hs, 2 * ws) if mode in (CONV_UP2, CONV_UP2P) else ((hs // 2, ws // 2) if mode in (CONV_DOWN2, CONV_STRIDE2, CONV_STRIDE2_PAD01) else (hs, ws))
     cout = w.shape[0]
     if out_nchw:
         out = torch.empty((n_hyp, cout, ho, wo), dtype=torch_dtype(out_dtype), device=src1.device)

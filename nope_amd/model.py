@@ -16,6 +16,7 @@ scope and are not provided.
 """
 from __future__ import annotations
 
+import inspect
 import os
 from typing import Optional
 
@@ -82,19 +83,42 @@ class PoseConditional(nn.Module):
         return self.compute_loss(pred_query_feat, query_feat)
 
     # ---- model.py:113-124 -------------------------------------------------------------------
+    def _decoder(self):
+        """The encoder's `decode_latent` (the VAE, nope_amd/vae.py), or None (the template encoder has none, model.py:117-123)."""
+        dec = getattr(self.u_net.encoder, "decode_latent", None)
+        return dec if callable(dec) else None
+
     @torch.no_grad()
     def sample(self, reference, relativeR):
         reference_feat = self.u_net.encoder.encode_image(reference, mode="mode")
         pred_query_feat = self.u_net(reference_feat, relativeR)
-        return pred_query_feat, None      # template encoder has no decode_latent (model.py:117-123)
+        dec = self._decoder()
+        if dec is None:
+            return pred_query_feat, None
+        # unnormalize_to_zero_to_one(decode_latent(pred)), model.py:117-123
+        if "unnormalize" in inspect.signature(dec).parameters:      # nope_amd's VAE: (x + 1) / 2 folded into its output conv
+            return pred_query_feat, dec(pred_query_feat, unnormalize=True)
+        return pred_query_feat, (dec(pred_query_feat) + 1) / 2      # another encoder's decode_latent, as the reference applies it
 
     # ---- model.py:193-252 -----------------------------------------------------------------------
     @torch.no_grad()
     def generate_templates(self, reference, all_relativeR, gt_templates=None, visualize=False):
         """reference (B,3,S,S); all_relativeR (B,N,6) -> (pred_feat_templates (B,N',C,S/8,S/8),
-        None, None).  N' = N, or this rank's slice of N under `template_parallel`."""
+        pred_templates, None).  N' = N, or this rank's slice of N under `template_parallel`.  pred_templates: with an encoder that has
+        `decode_latent` (the VAE), the decoded templates (B,N',3,S,S) f32 (model.py:199-206,221-224), decoded on the device in chunks of
+        bounded workspace; else None.  (The PNG / video output of visualize=True is not provided.)"""
         reference_feat = self.u_net.encoder.encode_image(reference, mode="mode")   # hoisted: once, not N times
-        return self.generate_templates_from_feat(reference_feat, all_relativeR), None, None
+        bank = self.generate_templates_from_feat(reference_feat, all_relativeR)
+        dec = self._decoder()
+        if dec is None:
+            return bank, None, None
+        B, n = bank.shape[:2]
+        lat = torch.Tensor._make_subclass(torch.Tensor, bank, False) if isinstance(bank, ndist.ShardedBank) else bank
+        lat = lat.reshape(B * n, *bank.shape[2:])
+        if lat.dtype != torch.float32:
+            lat = lat.float()         # (16-bit banks: the decoder reads f32 latents)
+        rgb = dec(lat)                # (an empty bank decodes to (0, 3, S, S))
+        return bank, rgb.reshape(B, n, *rgb.shape[1:]), None
 
     @torch.no_grad()
     def generate_templates_from_feat(self, reference_feat, all_relativeR, defer_range_check=False):
@@ -156,7 +180,8 @@ class PoseConditional(nn.Module):
     @torch.no_grad()
     def generate_and_retrieve(self, query, reference, all_relativeR):
         """`generate_templates(reference, all_relativeR)` followed by `retrieval(query, bank)` as one call,
-        returning (similarity, nearest_idx, bank) -- the same arithmetic in the same order, bit-identical results.  The query does not depend on
+        returning (similarity, nearest_idx, bank) -- the same arithmetic in the same order, bit-identical results.  It never decodes the
+        bank, with a VAE encoder either: retrieval needs the latents only (generate_templates returns the decoded templates).  The query does not depend on
         the bank, so its encoder pass (launch-latency bound, a few CUs wide) is issued on a second HIP
         stream and runs underneath the reference encoder and the first U-Net kernels."""
         if self.similarity_metric != "l2":
