@@ -78,9 +78,10 @@ typedef void* nope_stream_t;
  * 5: NOPE_F16X2, nope_tuning_reload, nope_gather_topk, nope_topk_merge;
  * 6: nope_unet_x2_poll / _x2_range_check / _x2_enable / _x2_shifts, NOPE_ERR_RANGE*;
  * 7: nope_ldm_config.head_channels / resblock_updown / conv_resample, nope_op_token_attention dim_head 64 / 128;
- * 8: NOPE_CONV_STRIDE2_PAD01, nope_op_wide_attention, nope_vae_*).  Callers compare nope_abi_version() against the header they were
+ * 8: NOPE_CONV_STRIDE2_PAD01, nope_op_wide_attention, nope_vae_*;
+ * 9: nope_op_render_depth, nope_op_vsd, NOPE_VSD_* / NOPE_VISIB_*).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 8
+#define NOPE_ABI_VERSION 9
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -135,6 +136,37 @@ int nope_topk_merge(const float* cand_vals, const int64_t* cand_idx, int64_t* id
  *             bit 1 = an index outside [0, N). */
 int nope_op_geodesic(const double* poses, int64_t pose_stride_b, int N, const int64_t* idx, const double* gt, const int* symmetry,
                      double* err_rad, int* status, int B, int k, nope_stream_t stream);
+
+/* (ABI 9) Depth rendering of object meshes for the VSD evaluation.  Replaces pyrenderer, src/poses/vsd.py:25-54 (pyrender's OpenGL
+ * OffscreenRenderer with an IntrinsicsCamera, znear 0.05, zfar 100000, DEPTH_ONLY), as called by vsd_obj, vsd.py:79-90.
+ *   verts     (V, 3) f32, all meshes concatenated (mm);  faces (F, 3) int32 indices into verts
+ *   face_off, face_cnt  (P) int32: pose p draws faces [face_off[p], face_off[p] + face_cnt[p]); max_faces >= every face_cnt[p]
+ *   poses     (P, 4, 4) f64 object-to-camera, OpenCV axes (x right, y down, z forward);  K (P, 3, 3) f64 (fx, fy, cx, cy are read)
+ *   depth     (P, H, W) f32: camera-frame Z of the nearest surface at the image point (x + 0.5, y + 0.5), 1/Z interpolated in screen
+ *             space; 0 where nothing is hit.  No face culling; deterministic.
+ *   skipped   (P) uint32: triangles of each pose with a vertex at Z <= znear (not clipped: skipped; the caller reports a non-zero count)
+ *   workspace nope_op_render_depth_workspace_bytes(P, max_faces) bytes.
+ * Bad sizes, null pointers: NOPE_ERR_ARG; a short workspace: NOPE_ERR_WORKSPACE. */
+size_t nope_op_render_depth_workspace_bytes(int P, int max_faces);
+int nope_op_render_depth(const float* verts, int V, const int* faces, int F, const int* face_off, const int* face_cnt, int max_faces,
+                         const double* poses, const double* K, int P, int H, int W, float* depth, uint32_t* skipped, void* workspace,
+                         size_t workspace_bytes, nope_stream_t stream);
+
+/* (ABI 9) Visible Surface Discrepancy of k estimated poses per query.  Replaces vsd_obj's per-pose loop, src/poses/vsd.py:91-132, with
+ * depth_im_to_dist_im_fast, _estimate_visib_mask and estimate_visib_mask_gt / _est of src/poses/vsd_utils.py:41-134 (bop_toolkit).
+ *   depth_test (B, H, W), depth_gt (B, H, W), depth_est (B, k, H, W) f32 in mm (0 = no depth);  K (B, 3, 3) f64;  1 <= k <= 16
+ *   delta, tau  the misalignment / visibility tolerances (vsd.py:59-60: 15, 20);  cost_type NOPE_VSD_STEP | NOPE_VSD_TLINEAR;
+ *   visib_mode  NOPE_VISIB_BOP19 | NOPE_VISIB_BOP18
+ *   err        (B, k) f64: (cost + |union| - |intersection|) / |union|, 1.0 for an empty union
+ * Arithmetic of the reference: distance images in f64 from integer pixel coordinates, the visibility test f32(d_model) - f32(d_test)
+ * <= delta in f32, integer counts; the tlinear sum in a fixed order (the same bits on every run, not numpy's pairwise order).
+ * Test and gt pixels are read once for all k.  workspace: nope_op_vsd_workspace_bytes(B, k, H, W) bytes. */
+enum { NOPE_VSD_STEP = 0, NOPE_VSD_TLINEAR = 1 };
+enum { NOPE_VISIB_BOP19 = 0, NOPE_VISIB_BOP18 = 1 };
+size_t nope_op_vsd_workspace_bytes(int B, int k, int H, int W);
+int nope_op_vsd(const float* depth_test, const float* depth_gt, const float* depth_est, const double* K, int B, int k, int H, int W,
+                double delta, double tau, int cost_type, int visib_mode, double* err, void* workspace, size_t workspace_bytes,
+                nope_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Pose-conditioned U-Net.  Replaces UNet.__init__/forward,

@@ -69,6 +69,24 @@ int nope_op_geodesic(const double* poses, int64_t pose_stride_b, int N, const in
     return launch_geodesic(poses, (long long)pose_stride_b, N, (const long long*)idx, gt, symmetry, err_rad, status, B, k, (hipStream_t)stream);
 }
 
+size_t nope_op_render_depth_workspace_bytes(int P, int max_faces) { return render_depth_workspace_bytes(P, max_faces); }
+
+int nope_op_render_depth(const float* verts, int V, const int* faces, int F, const int* face_off, const int* face_cnt, int max_faces,
+                         const double* poses, const double* K, int P, int H, int W, float* depth, uint32_t* skipped, void* workspace,
+                         size_t workspace_bytes, nope_stream_t stream) {
+    return launch_render_depth(verts, V, faces, F, face_off, face_cnt, max_faces, poses, K, P, H, W, depth, skipped, workspace, workspace_bytes,
+                               (hipStream_t)stream);
+}
+
+size_t nope_op_vsd_workspace_bytes(int B, int k, int H, int W) { return vsd_workspace_bytes(B, k, H, W); }
+
+int nope_op_vsd(const float* depth_test, const float* depth_gt, const float* depth_est, const double* K, int B, int k, int H, int W,
+                double delta, double tau, int cost_type, int visib_mode, double* err, void* workspace, size_t workspace_bytes,
+                nope_stream_t stream) {
+    return launch_vsd(depth_test, depth_gt, depth_est, K, B, k, H, W, delta, tau, cost_type, visib_mode, err, workspace, workspace_bytes,
+                      (hipStream_t)stream);
+}
+
 int nope_op_nchw_to_nhwc(int dtype, const float* x, void* y, int n, int C, int HW, nope_stream_t s) {
     return launch_nchw_to_nhwc(dtype, x, y, n, C, HW, (hipStream_t)s);
 }

@@ -466,5 +466,12 @@ int launch_topk(const float* scores, long long* idx, float* vals, int B, int N, 
 int launch_gather_topk(const float* gathered, int G, int B, int N, float* scores, long long* idx, float* vals, int k, hipStream_t s);
 int launch_geodesic(const double* poses, long long stride_b, int N, const long long* idx, const double* gt, const int* symmetry,
                     double* err, int* status, int B, int k, hipStream_t s);
+size_t render_depth_workspace_bytes(int P, int max_faces);
+int launch_render_depth(const float* verts, int V, const int* faces, int F, const int* face_off, const int* face_cnt, int max_faces,
+                        const double* poses, const double* K, int P, int H, int W, float* depth, unsigned* skipped, void* ws,
+                        size_t ws_bytes, hipStream_t s);
+size_t vsd_workspace_bytes(int B, int k, int H, int W);
+int launch_vsd(const float* dtest, const float* dgt, const float* dest, const double* K, int B, int k, int H, int W, double delta, double tau,
+               int cost_type, int visib_mode, double* err, void* ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace nope

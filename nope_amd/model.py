@@ -11,8 +11,9 @@ Differences in *schedule*, none in arithmetic:
     unspecified; SURVEY.md §8 c3);
   * with `template_parallel=True` under torch.distributed each rank generates and scores only
     its slice of the template axis and the scores are all-gathered (nope_amd/dist.py).
-Lightning-specific members (optimizers, wandb logging, VSD/pyrender evaluation) are out of
-scope and are not provided.
+Lightning-specific members (optimizers, wandb logging, visualisation) are out of scope and are not provided.
+The evaluation entry points -- `eval_geodesic`, `eval_vsd` (T-LESS, on the device: nope_amd/vsd.py), `load_mesh`,
+`validation_step`, `test_step` -- return their scores instead of logging them.
 """
 from __future__ import annotations
 
@@ -256,3 +257,82 @@ class PoseConditional(nn.Module):
             similarity = hip.similarity(query_feat, template_feat)
         _, nearest_idx = hip.topk(similarity, k)
         return similarity, nearest_idx
+
+    # ---- evaluation, model.py:268-565 --------------------------------------------------------------------------------------------------
+    def load_mesh(self, cad_dir, obj_ids=range(1, 31)):
+        """obj_000001.ply ... obj_000030.ply of cad_dir into one device mesh bank (model.py:378-389), read without trimesh."""
+        from . import vsd
+        self.tless_cad = vsd.load_mesh_bank(cad_dir, obj_ids, device=next(self.parameters()).device)
+        return self.tless_cad
+
+    @torch.no_grad()
+    def eval_vsd(self, batch, data_name, save_path=None):
+        """The T-LESS evaluation (model.py:391-541) without visualisation or logging.  Returns {f"loss/val_{data_name}": the training loss
+        under the ground-truth pose, and the six `final_scores` of model.py:530-537}; saves vsd_error[:, 0] to save_path (np.save) if given.
+        batch: query, reference (B,3,S,S); gt_relativeR (B,6); all_relativeR (B,N,6); template_poses (B,N,3,3); query_pose (B,3,3);
+        query_translation (B,3,1) mm; intrinsic (B,3,3); obj_id (B,); and depth (B,H,W) mm, or depth_path (B PNG paths, read with
+        nope_amd.vsd.load_depth).  Predictions are template_poses[b, nearest_idx[b]] with the ground-truth translation (model.py:470-500);
+        errors by nope_amd.vsd.vsd_error with the reference's defaults (delta 15, tau 20, step cost, bop19)."""
+        import numpy as np
+        from . import vsd
+        if getattr(self, "tless_cad", None) is None:
+            raise RuntimeError("eval_vsd: no meshes: call load_mesh(cad_dir) first (model.py:378)")
+        query, reference = batch["query"], batch["reference"]
+        loss = self.forward(query=query, relativeR=batch["gt_relativeR"], reference=reference)
+        pred_feat, _, _ = self.generate_templates(reference=reference, all_relativeR=batch["all_relativeR"])
+        out = self.retrieval(query=query, template_feat=pred_feat)
+        if out is None:
+            raise NotImplementedError(f"eval_vsd: similarity_metric {self.similarity_metric!r} (the reference implements 'l2' only)")
+        _, nearest_idx = out
+        B = query.shape[0]
+        template_poses = batch["template_poses"]
+        rows = torch.arange(B, device=template_poses.device)[:, None].expand(-1, nearest_idx.shape[1])
+        retrieved_R = template_poses[rows, nearest_idx.to(template_poses.device)]
+        if "depth" in batch:
+            depth_test = batch["depth"]
+        else:
+            depth_test = np.stack([vsd.load_depth(p) for p in batch["depth_path"]])
+        err = vsd.vsd_error(depth_test, self.tless_cad, batch["obj_id"], retrieved_R, batch["query_pose"], batch["query_translation"],
+                            batch["intrinsic"])
+        scores = {f"loss/val_{data_name}": float(loss)}
+        scores.update(vsd.vsd_scores(err))
+        if save_path is not None:
+            np.save(save_path, err[:, 0].cpu().numpy())
+        return scores
+
+    @torch.no_grad()
+    def eval_geodesic(self, batch, data_name, visualize=False, save_prediction=False):
+        """model.py:268-376 through nope_amd.harness.eval_geodesic: {"loss", geodesic / accuracy scores}.  save_prediction writes
+        predictions/pred_step{global_step}_rank{global_rank}.npz (with save_dir).  visualize is accepted and ignored."""
+        from .harness import eval_geodesic
+        save = None
+        if save_prediction and self.save_dir is not None:
+            save = os.path.join(self.save_dir, "predictions", f"pred_step{self.global_step}_rank{self.global_rank}")
+        _, _, res = eval_geodesic(self, batch, save_path=save)
+        return res
+
+    def validation_step(self, batch, idx):
+        """model.py:543-548: "tless" -> eval_vsd, every other dataloader -> eval_geodesic.  Returns {data_name: scores}."""
+        out = {}
+        for data_name in batch.keys():
+            if data_name in ["tless"]:
+                out[data_name] = self.eval_vsd(batch[data_name], data_name)
+            else:
+                out[data_name] = self.eval_geodesic(batch[data_name], data_name)
+        return out
+
+    def test_step(self, batch, idx_batch):
+        """model.py:550-565: dataloaders keyed "<data>_<category>"; tless -> eval_vsd (errors saved to
+        predictions/vsd_{category}_batch{idx_batch}_rank_{global_rank}.npy with save_dir), otherwise eval_geodesic with saved predictions.
+        Returns {dataloader_name: scores}."""
+        out = {}
+        for dataloader_name in batch.keys():
+            data_name, category = dataloader_name.split("_", 1)
+            if data_name in ["tless"]:
+                save_path = None
+                if self.save_dir is not None:
+                    save_path = os.path.join(self.log_dir, f"vsd_{category}_batch{idx_batch}_rank_{self.global_rank}.npy")
+                out[dataloader_name] = self.eval_vsd(batch[dataloader_name], category, save_path=save_path)
+            else:
+                out[dataloader_name] = self.eval_geodesic(batch[dataloader_name], category, visualize=True, save_prediction=True)
+        return out
