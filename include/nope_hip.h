@@ -79,9 +79,10 @@ typedef void* nope_stream_t;
  * 6: nope_unet_x2_poll / _x2_range_check / _x2_enable / _x2_shifts, NOPE_ERR_RANGE*;
  * 7: nope_ldm_config.head_channels / resblock_updown / conv_resample, nope_op_token_attention dim_head 64 / 128;
  * 8: NOPE_CONV_STRIDE2_PAD01, nope_op_wide_attention, nope_vae_*;
- * 9: nope_op_render_depth, nope_op_vsd, NOPE_VSD_* / NOPE_VISIB_*).  Callers compare nope_abi_version() against the header they were
+ * 9: nope_op_render_depth, nope_op_vsd, NOPE_VSD_* / NOPE_VISIB_*;
+ * 10: nope_gd_config, nope_gd_*).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 9
+#define NOPE_ABI_VERSION 10
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -311,6 +312,50 @@ int nope_ldm_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, 
 int nope_ldm_x2_poll(nope_ldm* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs);
 int nope_ldm_x2_range_check(nope_ldm* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs);
 int nope_ldm_x2_enable(nope_ldm* net, int on);
+
+/* ------------------------------------------------------------------------------------------
+ * (ABI 10) Guided-diffusion U-Net variant.  Replaces UNetModelPose.__init__/forward, src/model/u_net/guided_diffusion/adapt_u_net.py:13-97
+ * (over UNetModel, guided_diffusion/u_net.py:389-; ResBlock :141-253, AttentionBlock :255-300, QKVAttentionLegacy / QKVAttention
+ * :323-386, Downsample / Upsample :78-138): the variant whose pose conditioning is emb = pose_mlp(pose) in place of the timestep
+ * embedding, read by every ResBlock's emb_layers.  The reference's forward calls module(h, emb, emb), which TimestepEmbedSequential
+ * does not accept; this runs the one reading that type-checks, module(h, emb).  Tensor names are UNetModelPose's own state-dict keys
+ * ("input_blocks.4.1.qkv.weight" [3C][C][1], "middle_block.1.proj_out.weight" [C][C][1], "output_blocks.2.2.in_layers.2.weight", ...);
+ * time_embed.* is never read.  AttentionBlock = GroupNorm(32) -> qkv 1x1 -> softmax attention over the H*W tokens of a sample
+ * (nope_op_token_attention: heads 32 / 64 / 128 channels wide; the legacy (head, q|k|v, ch) rows of qkv are permuted to [q | k | v] at
+ * create time) -> proj_out 1x1 + x.  Supported: conv_resample, resblock_updown and use_scale_shift_norm on or off; pose_mlp
+ * "single_layer" / "two_layers" / "posEncoding". */
+typedef struct nope_gd nope_gd;
+enum { NOPE_GD_POSE_SINGLE = 1, NOPE_GD_POSE_TWO_LAYERS = 2, NOPE_GD_POSE_ENCODING = 3 };
+typedef struct {
+    int in_channels;        /* 4 in vae_guidedDiffusion.yaml (any count: the input conv's K axis is zero-padded to a multiple of 8) */
+    int model_channels;     /* 256; a multiple of 32 */
+    int out_channels;       /* 4 */
+    int num_res_blocks;     /* 2 */
+    int n_levels;           /* len(channel_mult) = 6 */
+    int channel_mult[8];    /* (1,1,2,2,4,4) */
+    int attn_levels[8];     /* 1 where the level's downsampling factor is in attention_resolutions: (0,0,0,1,1,1) */
+    int head_channels_in[8];   /* head width of level l's input-side AttentionBlocks (num_heads / num_head_channels, u_net.py:444-445, 474-482) */
+    int head_channels_out[8];  /* ... of its output-side ones (num_heads_upsample, :580) */
+    int head_channels_mid;     /* ... of the middle block's (num_heads at the last level's channels) */
+    int pose_dim;           /* rot_representation_dim, 6 */
+    int pose_mlp;           /* NOPE_GD_POSE_*: Linear; Linear, GELU (erf), Linear; SinusoidalPosEmb(emb / 6) (pose_dim 6) */
+    int new_attention_order;   /* 0: QKVAttentionLegacy, qkv rows (head, q|k|v, ch); 1: QKVAttention, rows (q|k|v, head, ch) */
+    int resblock_updown;    /* 1 (the yaml): the resampling slots are ResBlocks with down / up (avg_pool 2x2 / nearest x2 on h and x) */
+    int conv_resample;      /* 1: Downsample = conv 3x3 stride 2, Upsample = nearest x2 + conv 3x3; 0: avg_pool 2x2 / nearest x2 alone. Ignored under resblock_updown */
+    int use_scale_shift_norm;  /* 1 (the yaml): ResBlocks apply out_norm(h) * (1 + scale) + shift with (scale, shift) = emb_layers(emb) */
+    int compute_dtype;      /* NOPE_F32 | NOPE_BF16 | NOPE_F16 | NOPE_BF16X3 | NOPE_F16X2, as nope_ldm_config */
+} nope_gd_config;
+
+int nope_gd_create(const nope_gd_config* cfg, const nope_tensor_desc* tensors, int n_tensors, nope_stream_t stream, nope_gd** out);
+void nope_gd_destroy(nope_gd* net);
+size_t nope_gd_workspace_bytes(const nope_gd* net, int n_hyp, int n_src, int H, int W);
+/* out[j] = UNetModelPose(x[j / x_rep], pose[j]); arguments as nope_ldm_forward; H and W multiples of 2^(n_levels - 1). */
+int nope_gd_forward(const nope_gd* net, const float* x, int n_src, int x_rep, const float* pose, int n_hyp, int H, int W,
+                    void* out, int out_dtype, void* workspace, size_t workspace_bytes, nope_stream_t stream);
+/* NOPE_F16X2: the 3x3 convolutions on the two-pass tile, everything else as NOPE_BF16X3; activation ranges as nope_ldm_x2_*. */
+int nope_gd_x2_poll(nope_gd* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs);
+int nope_gd_x2_range_check(nope_gd* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs);
+int nope_gd_x2_enable(nope_gd* net, int on);
 
 /* ------------------------------------------------------------------------------------------
  * Template encoder.  Replaces FeatureExtractor.encode_image, src/model/encoder/template.py:47-53

@@ -22,18 +22,13 @@
 #include <string>
 #include <vector>
 
-#include "nope_common.h"
-#include "x2_range.h"
+#include "resblock_runtime.h"
 
 using namespace nope;
+using namespace nope::rb;
 
 namespace {
 
-struct LConv { void* w = nullptr; float* bias = nullptr; int Cin = 0, Cout = 0, ntaps = 1, mode = NOPE_CONV_PLAIN; void* w_x2 = nullptr; int x2_id = -1; };   // w_x2 / x2_id: NOPE_F16X2, the 3x3 convs' second pack and its slot in the range table (x2_range.h)
-struct LNorm { float* gamma = nullptr; float* beta = nullptr; int C = 0; };
-struct LRes { LNorm n1, n2; LConv c1, c2, skip; bool has_skip = false; float *emb_w = nullptr, *emb_b = nullptr; int Cin = 0, Cout = 0;
-              int updown = 0; };      // updown: 0, RES_DOWN or RES_UP (resblock_updown, openaimodel.py:224-231)
-enum { RES_DOWN = 1, RES_UP = 2 };
 struct LTB { LNorm ln1, ln3; LConv qkv, out1, ff1, ff2; int u_off = 0; };         // one BasicTransformerBlock; u_off: its slice of nope_ldm::u_w
 struct LST { LNorm norm; LConv proj_in, proj_out; std::vector<LTB> blocks; int C = 0, dh = 32; };      // dh: attention head width (dim_head)
 // has_resample: a Downsample / Upsample slot -- its conv (conv_resample), or with resample.w = null avg_pool 2x2 / nearest x2 alone; under
@@ -42,14 +37,8 @@ struct LBlock { bool has_res = false, has_st = false, has_resample = false; LRes
 
 }  // namespace
 
-struct nope_ldm {
+struct nope_ldm : RtNet {      // (dt / sdt / x2 / x2r / allocs / emb_dim: RtNet, resblock_runtime.h)
     nope_ldm_config cfg;
-    int dt = NOPE_F32;      // compute dtype (conv kernels, weight packing)
-    int sdt = NOPE_F32;     // storage dtype of the activations (every other kernel)
-    bool x2 = false;        // NOPE_F16X2: dt = NOPE_BF16X3 everywhere, plus a second weight pack per 3x3 conv (ResBlock convs, nearest-x2 up-sampling) for the
-                            // ping-pong kernels' f16 + MX-fp8 tile; the 1x1 convs / linears of the transformer blocks stay three-pass
-    mutable X2Range x2r;    // ... and the activation-range tracking that keeps the tile inside its accurate window (x2_range.h)
-    std::vector<void*> allocs;
     LConv conv_in, conv_out;
     LNorm norm_out;
     std::vector<LBlock> input_blocks, output_blocks;     // input_blocks[0] is conv_in
@@ -60,48 +49,15 @@ struct nope_ldm {
     float *tw = nullptr, *tb = nullptr;                  // pose_mlp_timesteps (injecting_condition_twice)
     float *u_w = nullptr, *u_b = nullptr;                // stacked attn2 maps to_out.0 o to_v of every transformer block: [u_total][context_dim], [u_total]
     int u_total = 0;
-    int emb_dim = 0;
 };
 
 namespace {
 
-struct Loader {
-    nope_ldm* net;
-    hipStream_t s;
-    std::map<std::string, const nope_tensor_desc*> tab;
-    int err = NOPE_OK;
-    std::string missing;
+struct Loader : LoaderBase {
+    nope_ldm* ldm;
     struct UPart { float* comb; float* bias; int C, off; };
     std::vector<UPart> u_parts;
     int u_total = 0;
-    void fail(const std::string& n) { if (err == NOPE_OK) { err = NOPE_ERR_WEIGHT; missing = n; } }
-    // device-to-device copy of a state-dict tensor at create time; a refused copy (bad pointer, wrong device) fails the create call itself,
-    // not just the stream synchronisation that ends it
-    void copy_d2d(void* dst, const void* src, size_t bytes) {
-        if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess && err == NOPE_OK) err = NOPE_ERR_LAUNCH;
-    }
-    void chk(int e) { if (e && err == NOPE_OK) err = e; }
-    const nope_tensor_desc* get(const std::string& name, std::initializer_list<int64_t> shape) {
-        auto it = tab.find(name);
-        if (it == tab.end() || !it->second->data || it->second->ndim != (int)shape.size()) { fail(name); return nullptr; }
-        int i = 0;
-        for (int64_t v : shape) if (it->second->shape[i++] != v) { fail(name); return nullptr; }
-        return it->second;
-    }
-    void* dmalloc(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err == NOPE_OK) err = NOPE_ERR_ALLOC; return nullptr; }
-        net->allocs.push_back(p);
-        return p;
-    }
-    std::vector<void*> temps;                  // staging buffers of create time, freed after its final synchronize
-    void* tmalloc(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err == NOPE_OK) err = NOPE_ERR_ALLOC; return nullptr; }
-        temps.push_back(p);
-        return p;
-    }
-    void free_temps() { for (void* p : temps) hipFree(p); temps.clear(); }
     // GEGLU's projection (attention.py:37-44: `x, gate = proj(x).chunk(2, dim=-1)`): rows (x_j, gate_j) interleaved, so that a lane of the conv
     // epilogue holds whole pairs (ConvArgs::geglu); the unfused path reads the same layout (launch_geglu(..., interleaved))
     LConv conv_geglu(const std::string& pfx, int Cin, int D) {
@@ -125,68 +81,13 @@ struct Loader {
         chk(launch_pack_conv_w(net->dt, wi, c.w, 2 * D, Cin, 1, NOPE_CONV_PLAIN, s));
         return c;
     }
-    float* copy_f32(const std::string& name, std::initializer_list<int64_t> shape) {
-        const nope_tensor_desc* d = get(name, shape);
-        if (!d) return nullptr;
-        size_t n = 1;
-        for (int64_t v : shape) n *= (size_t)v;
-        float* p = (float*)dmalloc(n * 4);
-        if (p) copy_d2d(p, d->data, n * 4);
-        return p;
-    }
-    // conv (4-d weight) or linear (2-d weight) packed for the implicit-GEMM kernel
-    // (Cin_pad > Cin: the kernel sees Cin_pad input channels, the last ones zero -- the 4-channel latent of vae_cin_ldm.yaml padded
-    //  to one 16-byte vector of the 16-bit modes)
-    LConv conv(const std::string& pfx, int Cin, int Cout, int ksz, int mode, bool has_bias, bool linear = false, int Cin_pad = 0) {
-        LConv c;
-        const int Ck = Cin_pad > Cin ? Cin_pad : Cin;
-        c.Cin = Ck; c.Cout = Cout; c.mode = mode;
-        c.ntaps = mode == NOPE_CONV_UP2P ? 4 : ksz * ksz;
-        const nope_tensor_desc* d = linear ? get(pfx + "weight", {Cout, Cin}) : get(pfx + "weight", {Cout, Cin, ksz, ksz});
-        if (d) {
-            const size_t es = (size_t)dt_es(net->dt);
-            c.w = dmalloc((size_t)Cout * c.ntaps * Ck * es * (mode == NOPE_CONV_UP2P ? 4 : 1));
-            if (c.w) chk(launch_pack_conv_w(net->dt, d->data, c.w, Cout, Ck, c.ntaps, mode, s, nullptr, nullptr, Cin));
-            if (net->x2 && !linear && ksz == 3 && (mode == NOPE_CONV_PLAIN || mode == NOPE_CONV_UP2P) && Ck == Cin && Cin % 32 == 0) {
-                const size_t x2b = conv_w_x2_bytes(Cout, Cin, c.ntaps, mode);
-                c.w_x2 = dmalloc(x2b);
-                if (c.w_x2) { chk(launch_pack_conv_w_x2((const float*)d->data, c.w_x2, Cout, Cin, s, c.ntaps, mode)); c.x2_id = net->x2r.add_layer(c.w_x2, x2b); }
-            }
-        }
-        if (has_bias) c.bias = copy_f32(pfx + "bias", {Cout});
-        return c;
-    }
-    LNorm norm(const std::string& pfx, int C) {
-        LNorm n;
-        n.C = C;
-        n.gamma = copy_f32(pfx + "weight", {C});
-        n.beta = copy_f32(pfx + "bias", {C});
-        return n;
-    }
-    LRes res(const std::string& p, int Cin, int Cout, int updown = 0) {
-        LRes r;
-        r.Cin = Cin; r.Cout = Cout; r.updown = updown;
-        r.n1 = norm(p + "in_layers.0.", Cin);
-        // (up: GroupNorm + SiLU -> nearest x2 -> conv 3x3 is the phase conv of Upsample; down: the conv reads the pooled activation)
-        r.c1 = conv(p + "in_layers.2.", Cin, Cout, 3, updown == RES_UP ? NOPE_CONV_UP2P : NOPE_CONV_PLAIN, true);
-        const int film = net->cfg.use_scale_shift_norm ? 2 : 1;          // emb_layers.1: Linear(emb, 2 C) for FiLM, openaimodel.py:233-239
-        r.emb_w = copy_f32(p + "emb_layers.1.weight", {film * Cout, net->emb_dim});
-        r.emb_b = copy_f32(p + "emb_layers.1.bias", {film * Cout});
-        r.n2 = norm(p + "out_layers.0.", Cout);
-        r.c2 = conv(p + "out_layers.3.", Cout, Cout, 3, NOPE_CONV_PLAIN, true);
-        r.has_skip = Cin != Cout;
-        if (r.has_skip) r.skip = conv(p + "skip_connection.", Cin, Cout, 1, NOPE_CONV_PLAIN, true);
-        if (!net->cfg.injecting_condition_twice && !net->cfg.use_scale_shift_norm && r.c1.bias && r.emb_b)     // emb == 0: emb_layers(emb) = its bias, folded into conv1's
-            chk(launch_add_rowvec(NOPE_F32, r.c1.bias, r.c1.bias, r.emb_b, 1, 1, Cout, s));
-        return r;
-    }
     LST st(const std::string& p, int C, int dh) {
         LST T;
         T.C = C; T.dh = dh;
-        const int ctx = net->cfg.context_dim;
+        const int ctx = ldm->cfg.context_dim;
         T.norm = norm(p + "norm.", C);
         T.proj_in = conv(p + "proj_in.", C, C, 1, NOPE_CONV_PLAIN, true);
-        const int depth = net->cfg.transformer_depth > 0 ? net->cfg.transformer_depth : 1;
+        const int depth = ldm->cfg.transformer_depth > 0 ? ldm->cfg.transformer_depth : 1;
         for (int d = 0; d < depth; ++d) {                      // attention.py:251-258: `depth` blocks in sequence
         LTB t;
         const std::string b = p + "transformer_blocks." + std::to_string(d) + ".";
@@ -234,143 +135,10 @@ struct Loader {
     }
 };
 
-struct Arena {
-    unsigned char* base = nullptr;
-    size_t cap = 0, off = 0, peak = 0;
-    bool dry = false;
-    void* alloc(size_t bytes) {
-        const size_t o = align_up(off, 256);
-        off = o + bytes;
-        if (off > peak) peak = off;
-        if (dry) return (void*)(uintptr_t)(0x1000 + o);
-        if (off > cap) return nullptr;
-        return base + o;
-    }
-};
-
-struct Act { void* p = nullptr; int C = 0, H = 0, W = 0; };
-
-struct Fwd {
-    const nope_ldm* net;
-    hipStream_t s;
-    Arena ar;
-    int nhyp = 0, err = NOPE_OK;
-    size_t es = 4;
-    float* gn_partial = nullptr;
+struct Fwd : FwdBase {
+    const nope_ldm* ldm;
     const float* ctx = nullptr;       // (nhyp, context_dim)
-    const float* emb = nullptr;       // (nhyp, emb_dim) or null (zeros)
     const float* u_all = nullptr;     // (nhyp, u_total): every transformer block's to_out(to_v(context)) row
-    X2Fwd x2;                         // NOPE_F16X2 range tracking of this forward (x2_range.h)
-    bool tracking() const { return x2.on && err == NOPE_OK; }
-
-    void chk(int e) { if (e != NOPE_OK && err == NOPE_OK) err = e; }
-    bool live() const { return !ar.dry && err == NOPE_OK; }
-    void* alloc_act(size_t elems) {
-        void* p = ar.alloc(elems * es);
-        if (!p && err == NOPE_OK) err = NOPE_ERR_WORKSPACE;
-        return p;
-    }
-    float* alloc_f32(size_t n) {
-        float* p = (float*)ar.alloc(n * 4);
-        if (!p && err == NOPE_OK) err = NOPE_ERR_WORKSPACE;
-        return p;
-    }
-    void conv(const LConv& c, const Act& a, void* out, int Ho, int Wo, const void* resid = nullptr, int out_nchw = 0, int out_dt = NOPE_F32,
-              int rep = 1, int n = -1) {
-        if (!live()) return;
-        ConvArgs ca;
-        ca.src1 = a.p; ca.C1 = a.C; ca.rep1 = rep; ca.Hs = a.H; ca.Ws = a.W; ca.Ho = Ho; ca.Wo = Wo;
-        ca.mode = c.mode; ca.ntaps = c.ntaps; ca.w = c.w; ca.bias = c.bias; ca.resid = resid; ca.out = out; ca.Cout = c.Cout;
-        ca.nhyp = n < 0 ? nhyp : n; ca.out_nchw = out_nchw; ca.out_dt = out_dt;
-        if (a.C != c.Cin) { chk(NOPE_ERR_ARG); return; }
-        if (c.w_x2 && !net->x2r.off) { ca.w_x2 = c.w_x2; ca.x2_t_zero = net->x2r.t_zero(c.x2_id) ? 1 : 0; }
-        if (tracking()) {
-            if (ca.w_x2 && conv_takes_x2(net->dt, ca)) {      // the two-pass tile: the layer's range shift follows its input's maximum
-                x2.consumes(c.x2_id, x2.slot_for(a.p, (size_t)(ca.nhyp / rep) * a.H * a.W * a.C));
-                chk(x2.err);
-            }
-            x2.overwritten(out);           // (conv epilogues record no maximum here: a two-pass consumer of `out` takes an absmax pass)
-        }
-        chk(launch_conv(net->dt, ca, s));
-    }
-    // y = [silu](GroupNorm(32, eps)(x))
-    void gn(const LNorm& nm, const void* x, void* y, int HW, int act, float eps, const float* film = nullptr, int film_stride = 0) {
-        if (!live()) return;
-        const int nch = gn_stats_chunks(HW, nm.C, net->sdt);
-        chk(launch_gn_stats(net->sdt, x, gn_partial, nhyp, HW, nm.C, 32, nch, s));
-        GnApplyArgs ga;
-        ga.x = x; ga.y = y; ga.partial = gn_partial; ga.nchunk = nch; ga.gamma = nm.gamma; ga.beta = nm.beta;
-        ga.nhyp = nhyp; ga.HW = HW; ga.C = nm.C; ga.G = 32; ga.act = act; ga.eps = eps;
-        ga.film = film; ga.film_stride = film_stride;
-        ga.fast_silu = net->dt != NOPE_F32 ? 1 : 0;      // (f32 storage of the split-precision modes: hardware exp / rcp; the f32 mode keeps expf and the division)
-        if (tracking()) {                                // (the FiLM instantiation records no maximum: its consumer takes an absmax pass)
-            if (!film) { const int sl = x2.produce(y); if (sl >= 0) ga.amax_out = x2.slot_ptr(sl); }
-            else x2.overwritten(y);
-        }
-        chk(launch_gn_apply(net->sdt, ga, s));
-    }
-    // parameter-free resampling of an activation (storage dtype); the output's range is unknown to x2_range.h: a two-pass conv that
-    // reads it takes an absmax pass (the arena hands out addresses again -- a stale slot of an earlier tensor would misjudge it)
-    void pool(const Act& x, void* y) {
-        if (!live()) return;
-        if (tracking()) x2.overwritten(y);
-        chk(launch_avg_pool2(net->sdt, x.p, y, nhyp, x.H, x.W, x.C, s));
-    }
-    void up2(const Act& x, void* y) {
-        if (!live()) return;
-        if (tracking()) x2.overwritten(y);
-        chk(launch_nearest2(net->sdt, x.p, y, nhyp, x.H, x.W, x.C, s));
-    }
-    // ResBlock._forward, openaimodel.py:262-288; out is at the input's size, half of it (RES_DOWN) or twice it (RES_UP)
-    void res(const LRes& R, const Act& xin, void* out) {
-        const size_t mark = ar.off;
-        const bool film_on = net->cfg.use_scale_shift_norm != 0;
-        const int Ho = R.updown == RES_DOWN ? xin.H / 2 : R.updown == RES_UP ? xin.H * 2 : xin.H;
-        const int Wo = R.updown == RES_DOWN ? xin.W / 2 : R.updown == RES_UP ? xin.W * 2 : xin.W;
-        const int HW = Ho * Wo;
-        const size_t M = (size_t)nhyp * HW;
-        void* t = alloc_act((size_t)nhyp * xin.H * xin.W * R.Cin);
-        void* h = alloc_act(M * R.Cout);
-        gn(R.n1, xin.p, t, xin.H * xin.W, 1, 1e-5f);
-        Act x = xin;
-        if (R.updown == RES_DOWN) {          // h = conv(avg_pool(silu(norm(x)))), x = avg_pool(x)
-            void* tp = alloc_act(M * R.Cin);
-            void* xp = alloc_act(M * R.Cin);
-            pool(Act{t, R.Cin, xin.H, xin.W}, tp);
-            pool(xin, xp);
-            x = Act{xp, R.Cin, Ho, Wo};
-            conv(R.c1, Act{tp, R.Cin, Ho, Wo}, h, Ho, Wo);
-        } else if (R.updown == RES_UP) {     // h = conv(nearest(silu(norm(x)))) as the phase conv, x = nearest(x)
-            void* xu = alloc_act(M * R.Cin);
-            up2(xin, xu);
-            x = Act{xu, R.Cin, Ho, Wo};
-            conv(R.c1, Act{t, R.Cin, xin.H, xin.W}, h, Ho, Wo);
-        } else {
-            conv(R.c1, Act{t, R.Cin, x.H, x.W}, h, x.H, x.W);
-        }
-        const float* film = nullptr;                // FiLM rows [scale | shift]: emb == 0 -> the bias row, shared by every sample
-        int film_stride = 0;
-        if (film_on && !emb) film = R.emb_b;
-        if (emb) {                                  // emb_layers(emb): added to h, or (FiLM) applied by the GroupNorm below
-            const int ne = film_on ? 2 * R.Cout : R.Cout;
-            float* e = alloc_f32((size_t)nhyp * ne);
-            if (live()) {
-                chk(launch_linear_naive(emb, R.emb_w, R.emb_b, e, nhyp, ne, net->emb_dim, 1, ne, s));
-                if (!film_on) chk(launch_add_rowvec(net->sdt, h, h, e, (long long)M, HW, R.Cout, s));
-            }
-            if (film_on) { film = e; film_stride = ne; }
-        }
-        void* t2 = alloc_act(M * R.Cout);
-        gn(R.n2, h, t2, HW, 1, 1e-5f, film, film_stride);
-        const void* resid = x.p;
-        if (R.has_skip) {
-            void* sk = alloc_act(M * R.Cout);
-            conv(R.skip, x, sk, x.H, x.W);
-            resid = sk;
-        }
-        conv(R.c2, Act{t2, R.Cout, x.H, x.W}, out, x.H, x.W, resid);
-        ar.off = mark;
-    }
     // SpatialTransformer.forward, attention.py:264-277: GroupNorm, proj_in, `depth` BasicTransformerBlocks (:192-212), proj_out + x
     void st(const LST& T, const Act& x, void* out) {
         const int HW = x.H * x.W, C = T.C;
@@ -393,7 +161,7 @@ struct Fwd {
             if (live()) chk(launch_token_attention(net->dt, qkv, o, nhyp, HW, C, T.dh, s));
             conv(B.out1, Act{o, C, x.H, x.W}, tok1, x.H, x.W, tok);
             // attn2 against the single pose token: + to_out(to_v(context)) for every token -- this block's slice of u_all
-            if (live()) chk(launch_add_rowvec(net->sdt, tok1, tok1, u_all + B.u_off, M, HW, C, s, net->u_total));
+            if (live()) chk(launch_add_rowvec(net->sdt, tok1, tok1, u_all + B.u_off, M, HW, C, s, ldm->u_total));
             // feed-forward (GEGLU) + residual
             void* f = o;                                     // reuse: LN3(tok1)
             if (live()) chk(launch_layernorm(net->sdt, tok1, f, B.ln3.gamma, B.ln3.beta, M, C, 1e-5f, s));
@@ -422,7 +190,7 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
                 int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak) {
     const nope_ldm_config& cfg = net->cfg;
     Fwd f;
-    f.net = net; f.s = s; f.nhyp = n_hyp; f.es = (size_t)dt_es(net->dt);
+    f.net = net; f.ldm = net; f.s = s; f.nhyp = n_hyp; f.es = (size_t)dt_es(net->dt);
     f.ar.base = (unsigned char*)ws; f.ar.cap = ws_bytes; f.ar.dry = dry;
     f.x2.r = &net->x2r; f.x2.s = s; f.x2.on = net->x2 && net->x2r.active() && !dry;
     const int HW = H * W;
@@ -561,10 +329,12 @@ int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors,
     net->dt = dt_base(cfg->compute_dtype);
     net->sdt = dt_storage(net->dt);
     net->emb_dim = cfg->model_channels * 4;
+    net->film = cfg->use_scale_shift_norm != 0;
+    net->emb_zero = !cfg->injecting_condition_twice;
     const int mc = cfg->model_channels;
     auto dh = [&](int level) { return cfg->num_head_channels > 0 ? cfg->num_head_channels : cfg->head_channels[level]; };
     Loader ld;
-    ld.net = net; ld.s = s;
+    ld.net = net; ld.ldm = net; ld.s = s;
     for (int i = 0; i < n_tensors; ++i)
         if (tensors[i].name) ld.tab[tensors[i].name] = &tensors[i];
 

@@ -14,7 +14,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 9                          # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 10                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -40,6 +40,13 @@ class LdmConfig(C.Structure):
                 ("channel_mult", _i * 8), ("attn_levels", _i * 8), ("num_head_channels", _i), ("context_dim", _i), ("pose_dim", _i),
                 ("pose_mlp_layers", _i), ("injecting_condition_twice", _i), ("compute_dtype", _i), ("use_scale_shift_norm", _i),
                 ("transformer_depth", _i), ("head_channels", _i * 8), ("resblock_updown", _i), ("conv_resample", _i)]
+
+
+class GdConfig(C.Structure):
+    _fields_ = [("in_channels", _i), ("model_channels", _i), ("out_channels", _i), ("num_res_blocks", _i), ("n_levels", _i),
+                ("channel_mult", _i * 8), ("attn_levels", _i * 8), ("head_channels_in", _i * 8), ("head_channels_out", _i * 8),
+                ("head_channels_mid", _i), ("pose_dim", _i), ("pose_mlp", _i), ("new_attention_order", _i), ("resblock_updown", _i),
+                ("conv_resample", _i), ("use_scale_shift_norm", _i), ("compute_dtype", _i)]
 
 
 class VaeConfig(C.Structure):
@@ -85,6 +92,13 @@ _PROTOS = {
     "nope_ldm_x2_range_check": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
     "nope_ldm_x2_poll": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
     "nope_ldm_x2_enable": (_i, [_vp, _i]),
+    "nope_gd_create": (_i, [C.POINTER(GdConfig), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)]),
+    "nope_gd_destroy": (None, [_vp]),
+    "nope_gd_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "nope_gd_forward": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
+    "nope_gd_x2_range_check": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
+    "nope_gd_x2_poll": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
+    "nope_gd_x2_enable": (_i, [_vp, _i]),
     "nope_unet_profile": (_i, [_vp, _i]),
     "nope_unet_profile_read": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nope_unet_profile_launches": (_i, [_vp, C.POINTER(ConvLaunchInfo), _i, C.POINTER(_i)]),
@@ -702,7 +716,7 @@ class LdmHandle(_X2RangeMixin):
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            self._l.dll.nope_ldm_destroy(h)
+            getattr(self._l.dll, f"nope_{self._x2_prefix}_destroy")(h)
             self._h = None
 
     def forward(self, x: torch.Tensor, pose: torch.Tensor, x_rep: int = 1, out: Optional[torch.Tensor] = None, out_dtype=F32,
@@ -718,9 +732,10 @@ class LdmHandle(_X2RangeMixin):
         if out is None:
             out = torch.empty((n_hyp, self.out_channels, H, W), dtype=torch_dtype(odt), device=x.device)
         assert out.is_contiguous() and out.numel() == n_hyp * self.out_channels * H * W and out.dtype == torch_dtype(odt)
-        need = int(self._l.dll.nope_ldm_workspace_bytes(self._h, n_hyp, n_src, H, W))
+        pfx = self._x2_prefix
+        need = int(getattr(self._l.dll, f"nope_{pfx}_workspace_bytes")(self._h, n_hyp, n_src, H, W))
         if need == 0:
-            raise NopeError(f"unsupported LDM U-Net problem size n_hyp={n_hyp} H={H} W={W}")
+            raise NopeError(f"unsupported {pfx.upper()} U-Net problem size n_hyp={n_hyp} H={H} W={W}")
         key = (str(x.device), _stream(x))
         ws = self._ws.get(key)
         if ws is None or ws.numel() < need:
@@ -728,8 +743,8 @@ class LdmHandle(_X2RangeMixin):
             ws = None
             ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
         def launch():
-            self._l.check(self._l.dll.nope_ldm_forward(self._h, _ptr(x), n_src, x_rep, _ptr(pose), n_hyp, H, W, _ptr(out), odt,
-                                                       _ptr(ws), ws.numel(), _stream(x)), "nope_ldm_forward")
+            self._l.check(getattr(self._l.dll, f"nope_{pfx}_forward")(self._h, _ptr(x), n_src, x_rep, _ptr(pose), n_hyp, H, W, _ptr(out), odt,
+                                                                      _ptr(ws), ws.numel(), _stream(x)), f"nope_{pfx}_forward")
         self._x2_before_forward(_stream(x))          # NOPE_F16X2: verdicts of earlier forwards (no waiting), _X2RangeMixin
         launch()
         if self._x2_mode() == "repeat" and self.x2_enabled:
@@ -737,6 +752,41 @@ class LdmHandle(_X2RangeMixin):
             if not defer_range_check:
                 self.finish_range_check()
         return out
+
+
+# --------------------------------------------------------------------------------------------
+# Guided-diffusion U-Net handle (forward / range checks as LdmHandle, on nope_gd_*)
+# --------------------------------------------------------------------------------------------
+class GdHandle(LdmHandle):
+    _x2_prefix = "gd"
+
+    """Owns a `nope_gd*` built from a guided-diffusion UNetModelPose state dict (reference keys)."""
+
+    def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], compute_dtype=F32):
+        l = lib()
+        self._l = l
+        c = GdConfig()
+        for k in ("in_channels", "model_channels", "out_channels", "num_res_blocks", "head_channels_mid", "pose_dim", "pose_mlp",
+                  "new_attention_order", "resblock_updown", "conv_resample", "use_scale_shift_norm"):
+            setattr(c, k, int(cfg[k]))
+        mult = tuple(cfg["channel_mult"])
+        c.n_levels = len(mult)
+        for i, m in enumerate(mult):
+            c.channel_mult[i] = m
+            c.attn_levels[i] = int(cfg["attn_levels"][i])
+            c.head_channels_in[i] = int(cfg["head_channels_in"][i])
+            c.head_channels_out[i] = int(cfg["head_channels_out"][i])
+        c.compute_dtype = dtype_code(compute_dtype)
+        self.in_channels, self.out_channels, self.pose_dim = c.in_channels, c.out_channels, c.pose_dim
+        descs, keep, dev = _tensor_descs(state_dict)
+        self.device = dev
+        h = _vp()
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else 0
+        l.check(l.dll.nope_gd_create(C.byref(c), descs, len(state_dict), stream, C.byref(h)), "nope_gd_create")
+        self._h = h
+        self._ws: Dict[tuple, torch.Tensor] = {}
+        self.compute_dtype = c.compute_dtype
+        self._x2_init()
 
 
 def op_warp_perspective(img: torch.Tensor, minv, size: int, scale: float = 1.0, shift: float = 0.0, round_u8: bool = False) -> torch.Tensor:
