@@ -80,9 +80,11 @@ typedef void* nope_stream_t;
  * 7: nope_ldm_config.head_channels / resblock_updown / conv_resample, nope_op_token_attention dim_head 64 / 128;
  * 8: NOPE_CONV_STRIDE2_PAD01, nope_op_wide_attention, nope_vae_*;
  * 9: nope_op_render_depth, nope_op_vsd, NOPE_VSD_* / NOPE_VISIB_*;
- * 10: nope_gd_config, nope_gd_*).  Callers compare nope_abi_version() against the header they were
+ * 10: nope_gd_config, nope_gd_*;
+ * 11: nope_op_conv_stat_rows, nope_op_conv_ex, nope_op_group_norm_ex, nope_op_gn_apply_blocks, nope_op_gn_finalize, nope_op_absmax_f32,
+ *     nope_op_amax_slot_words -- the fused GroupNorm statistics / PreNorm / range-slot plumbing at operator level).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 10
+#define NOPE_ABI_VERSION 11
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -415,6 +417,46 @@ int nope_op_gn_chunks(int dtype, int HW, int C);
 int nope_op_group_norm(int dtype, const void* x, void* y, float* partial, const float* gamma, const float* beta,
                        int n_hyp, int HW, int C, int G, int act_silu, const float* emb, int emb_stride,
                        const void* resid, nope_stream_t s);
+/* (ABI 11) The fusion plumbing around GroupNorm that the network runtimes use in place of the plain pair above, one launcher per entry
+ * (no reference counterpart: the reference runs Conv2d, GroupNorm and PreNorm as separate torch ops, model_utils.py:226-252).  Every entry
+ * returns whatever its launcher returns: a combination the launcher refuses is refused here.
+ *   RANGE SLOTS.  `amax_slot` is a scratch of nope_op_amax_slot_words() 32-bit words (the entries clear it), `amax_out` one device float
+ *   that receives max |.| of what the launch wrote, folded from the slot; both NULL = no request.
+ * nope_op_conv_stat_rows: rows per block of the column statistics a conv of this shape can emit (64; 16 / 32 on 16- / 32-pixel maps from
+ *   the kernels that have that form; 0 = none: residual, NCHW output, ReLU, NOPE_CONV_UP2P, Cout not in whole 16-byte vectors or > 2048).
+ *   Follows the launch policy in force (NOPE_* tuning variables), as the launch itself does.
+ * nope_op_conv_ex: nope_op_conv_ws plus
+ *   colstats [M / stat_rows][Cout][2] f32 (sum, sum of squares) of the f32 results (accumulator + bias) per block of stat_rows output rows, or
+ *            NULL; stat_rows must be nope_op_conv_stat_rows' answer (NOPE_ERR_ARG otherwise, and for a shape whose kernel has no such form);
+ *   pn_ms [n_hyp][2] (mean, rstd), pn_c0 / pn_c1 [Cout]: fused PreNorm of a 1x1 NOPE_CONV_PLAIN conv whose packed weights carry gamma,
+ *            out[m, n] = rstd[b] (acc[m, n] - mean[b] c1[n]) + c0[n] + bias[n], c0 = W beta, c1 = the row sums of the packed W gamma; or NULL;
+ *   amax_recorded (host int, may be NULL): 1 when this launch's kernel records max |out| (f32 storage, the wide NHWC epilogue of the
+ *            128 x 192 / ping-pong / tap-resident kernels, no split-K), else 0: amax_out is then 0. */
+int nope_op_amax_slot_words(void);
+int nope_op_conv_stat_rows(int dtype, int C1, int C2, int rep1, int Hs, int Ws, int mode, int ntaps, int Cout, int n_hyp, int has_resid,
+                           int out_nchw, int act_relu);
+int nope_op_conv_ex(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws, int mode,
+                    int ntaps, const void* w_packed, const float* bias, const void* resid, void* out, int Cout, int n_hyp,
+                    int out_nchw, int out_dtype, int act_relu, void* splitk_ws, size_t splitk_bytes, float* colstats, int stat_rows,
+                    const float* pn_ms, const float* pn_c0, const float* pn_c1, uint32_t* amax_slot, float* amax_out, int* amax_recorded,
+                    nope_stream_t s);
+/* nope_op_group_norm_ex: y[j] = act(GN(x[j / x_rep]) (1 + scale[j]) + shift[j]) + emb[j] + resid[j / resid_rep], j in [0, n_hyp).
+ *   Statistics: colstats = NULL: a pass over x (as nope_op_group_norm; `partial`: (n_hyp / x_rep) * nope_op_gn_chunks() * G * 2 floats);
+ *   else colstats [n_hyp / x_rep][stat_blocks][C][2], a conv's column statistics, folded by every workgroup itself (fold_launch = 0;
+ *   C <= 2048, no FiLM) or by a fold launch into `partial` ((n_hyp / x_rep) * G * 2 floats) first (fold_launch = 1): same bits either way.
+ *   film [scale (C) | shift (C)] rows, film_stride floats apart per hypothesis (0: one row for all), or NULL;
+ *   out_stats [n_hyp][nope_op_gn_apply_blocks()][2]: (sum, sum of squares) of the values each workgroup wrote, or NULL (not with FiLM);
+ *   fast_silu: f32 storage only, SiLU on the hardware exp / rcp (what the split-precision modes run; the 16-bit types always do) -- the
+ *   only form that records a range maximum: with the libm SiLU or FiLM amax_out stays 0.
+ * nope_op_gn_finalize: (mean, rstd) [n_hyp][2] of whole samples from nchunk (sum, sum of squares) pairs each (out_stats), count = HW * C. */
+int nope_op_gn_apply_blocks(int dtype, int HW, int C, int n_hyp);
+int nope_op_group_norm_ex(int dtype, const void* x, void* y, float* partial, const float* colstats, int stat_blocks, int fold_launch,
+                          const float* gamma, const float* beta, int n_hyp, int HW, int C, int G, int act_silu, const float* emb,
+                          int emb_stride, const float* film, int film_stride, const void* resid, int x_rep, int resid_rep, float* out_stats,
+                          float eps, int fast_silu, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
+int nope_op_gn_finalize(const float* partial, float* ms, int n_hyp, int nchunk, float count, float eps, nope_stream_t s);
+/* max |x[i]| over n f32 values (NaNs ignored; 0 for n = 0 or all zeros): what the runtimes run over conv-produced tensors in NOPE_F16X2. */
+int nope_op_absmax_f32(const float* x, size_t n, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
 /* LinearAttention core (model_utils.py:403-416) and Attention core (:376-389) on a fused
  * qkv tensor [n_hyp][HW][3*heads*dim_head]; out [n_hyp][HW][heads*dim_head]. */
 int nope_op_linear_attention(int dtype, const void* qkv, void* out, int n_hyp, int HW, int heads, int dim_head,

@@ -157,6 +157,79 @@ int nope_op_group_norm(int dtype, const void* x, void* y, float* partial, const 
     return launch_gn_apply(dtype, a, (hipStream_t)s);
 }
 
+// ---- (ABI 11) the fused GroupNorm statistics plumbing, one launcher each: nothing below computes, refuses or repairs anything itself ----
+int nope_op_amax_slot_words(void) { return kX2SlotWords; }
+
+// the range slot of a launch -> one float: fold the slot's lines (launch_amax_reduce zeroes them again); the word IS the bit pattern of max |.|
+static int amax_decode(uint32_t* slot, float* amax_out, hipStream_t s) { return launch_amax_reduce(slot, 1, reinterpret_cast<unsigned*>(amax_out), s); }
+
+int nope_op_absmax_f32(const float* x, size_t n, uint32_t* amax_slot, float* amax_out, nope_stream_t s) {
+    if (!amax_slot || !amax_out) return NOPE_ERR_ARG;
+    if (hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
+    if (const int e = launch_absmax_f32(x, n, amax_slot, (hipStream_t)s)) return e;
+    return amax_decode(amax_slot, amax_out, (hipStream_t)s);
+}
+
+int nope_op_conv_stat_rows(int dtype, int C1, int C2, int rep1, int Hs, int Ws, int mode, int ntaps, int Cout, int n_hyp, int has_resid,
+                           int out_nchw, int act_relu) {
+    ConvArgs a;
+    static const int dummy = 0;
+    fill_conv_args(a, &dummy, C1, rep1, C2 ? &dummy : nullptr, C2, 1, Hs, Ws, mode, ntaps, &dummy, nullptr, has_resid ? &dummy : nullptr, (void*)&dummy,
+                   Cout, n_hyp, out_nchw, NOPE_F32, act_relu);
+    if (!dt_is_compute(dtype) || act_relu) return 0;      // (launch_conv refuses statistics behind an activation)
+    return conv_stat_rows(dtype, a);
+}
+
+int nope_op_conv_ex(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws, int mode,
+                    int ntaps, const void* w_packed, const float* bias, const void* resid, void* out, int Cout, int n_hyp,
+                    int out_nchw, int out_dtype, int act_relu, void* splitk_ws, size_t splitk_bytes, float* colstats, int stat_rows,
+                    const float* pn_ms, const float* pn_c0, const float* pn_c1, uint32_t* amax_slot, float* amax_out, int* amax_recorded,
+                    nope_stream_t s) {
+    ConvArgs a;
+    fill_conv_args(a, src1, C1, rep1, src2, C2, rep2, Hs, Ws, mode, ntaps, w_packed, bias, resid, out, Cout, n_hyp, out_nchw, out_dtype, act_relu);
+    if ((mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2 || mode == NOPE_CONV_STRIDE2_PAD01) && ((Hs | Ws) & 1)) return NOPE_ERR_ARG;
+    if ((amax_slot != nullptr) != (amax_out != nullptr)) return NOPE_ERR_ARG;
+    a.splitk_ws = splitk_ws; a.splitk_bytes = splitk_ws ? splitk_bytes : 0;
+    a.colstats = colstats;
+    if (colstats) a.stat_rows = stat_rows;
+    a.pn_ms = pn_ms; a.pn_c0 = pn_c0; a.pn_c1 = pn_c1;
+    a.out_amax = amax_slot;
+    if (amax_recorded) *amax_recorded = conv_records_out_amax(dtype, a) ? 1 : 0;
+    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
+    if (const int e = launch_conv(dtype, a, (hipStream_t)s)) return e;
+    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
+}
+
+int nope_op_gn_apply_blocks(int dtype, int HW, int C, int n_hyp) { return gn_apply_blocks(HW, C, dtype, n_hyp); }
+
+int nope_op_gn_finalize(const float* partial, float* ms, int n_hyp, int nchunk, float count, float eps, nope_stream_t s) {
+    return launch_gn_finalize(partial, ms, n_hyp, nchunk, count, eps, (hipStream_t)s);
+}
+
+int nope_op_group_norm_ex(int dtype, const void* x, void* y, float* partial, const float* colstats, int stat_blocks, int fold_launch,
+                          const float* gamma, const float* beta, int n_hyp, int HW, int C, int G, int act_silu, const float* emb,
+                          int emb_stride, const float* film, int film_stride, const void* resid, int x_rep, int resid_rep, float* out_stats,
+                          float eps, int fast_silu, uint32_t* amax_slot, float* amax_out, nope_stream_t s) {
+    if (x_rep < 1 || n_hyp <= 0 || n_hyp % x_rep || (amax_slot != nullptr) != (amax_out != nullptr)) return NOPE_ERR_ARG;
+    GnApplyArgs a;
+    a.partial = partial;
+    if (colstats && fold_launch) {           // the separate fold launch + the partial path (what the runtimes do under NOPE_GN_FOLD_INLINE)
+        if (const int e = launch_gn_fold(colstats, partial, n_hyp / x_rep, stat_blocks, C, G, (hipStream_t)s)) return e;
+    } else if (colstats) {                   // every gn_apply workgroup folds its sample's column statistics itself
+        a.colstats = colstats; a.stat_blocks = stat_blocks;
+    } else {
+        a.nchunk = gn_stats_chunks(HW, C, dtype);
+        if (const int e = launch_gn_stats(dtype, x, partial, n_hyp / x_rep, HW, C, G, a.nchunk, (hipStream_t)s)) return e;
+    }
+    a.x = x; a.y = y; a.gamma = gamma; a.beta = beta;
+    a.nhyp = n_hyp; a.HW = HW; a.C = C; a.G = G; a.act = act_silu; a.emb = emb; a.emb_stride = emb_stride;
+    a.film = film; a.film_stride = film_stride; a.resid = resid; a.x_rep = x_rep; a.resid_rep = resid_rep;
+    a.out_stats = out_stats; a.eps = eps; a.fast_silu = fast_silu; a.amax_out = amax_slot;
+    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
+    if (const int e = launch_gn_apply(dtype, a, (hipStream_t)s)) return e;
+    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
+}
+
 int nope_op_linear_attention(int dtype, const void* qkv, void* out, int n_hyp, int HW, int heads, int dim_head, nope_stream_t s) {
     return launch_linattn(dtype, qkv, out, n_hyp, HW, heads, dim_head, (hipStream_t)s);
 }

@@ -14,7 +14,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 10                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 11                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -115,6 +115,15 @@ _PROTOS = {
     "nope_op_stem_conv": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_gn_chunks": (_i, [_i, _i, _i]),
     "nope_op_group_norm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "nope_op_amax_slot_words": (_i, []),
+    "nope_op_conv_stat_rows": (_i, [_i] * 13),
+    "nope_op_conv_ex": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp,
+                             _vp, _vp, C.POINTER(_i), _vp]),
+    "nope_op_gn_apply_blocks": (_i, [_i, _i, _i, _i]),
+    "nope_op_group_norm_ex": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, C.c_float, _i,
+                                   _vp, _vp, _vp]),
+    "nope_op_gn_finalize": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp]),
+    "nope_op_absmax_f32": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "nope_op_linear_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_linear": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -1021,6 +1030,148 @@ def op_group_norm(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Ten
                                      int(act_silu), _ptr(e), 0 if e is None else e.shape[1], _ptr(resid), _stream(x)),
             "nope_op_group_norm")
     return y
+
+
+def _amax_scratch(dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(range slot, one float) for an entry that reports max |.| of what it wrote (include/nope_hip.h: RANGE SLOTS; the entry clears the slot)."""
+    return (torch.empty(lib().dll.nope_op_amax_slot_words(), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+
+
+def op_conv_stat_rows(dt: int, c1: int, c2: int, rep1: int, hs: int, ws: int, mode: int, ntaps: int, cout: int, n_hyp: int,
+                      resid: bool = False, out_nchw: bool = False, act_relu: bool = False) -> int:
+    """Rows per block of the fused column statistics a conv of this shape emits under the launch policy in force (0: none)."""
+    return int(lib().dll.nope_op_conv_stat_rows(dt, c1, c2, rep1, hs, ws, mode, ntaps, cout, n_hyp, int(resid), int(out_nchw), int(act_relu)))
+
+
+def prenorm_fold(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, dt: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A GroupNorm(1, C) in front of a 1x1 conv, folded for ConvArgs::pn_*: (W', c0, c1) with W'[n, c] = W[n, c] gamma[c], c0[n] =
+    sum_c W[n, c] beta[c], c1[n] = sum_c W'[n, c], in float64, then cast to f32.  This is what unet_runtime.hip builds at create time
+    (prenorm_qkv: gamma as the packer's per-input-channel scale, c0 = W beta by nope_op_linear's kernel, c1 = launch_rowsum over the PACKED
+    rows): c1 is the row sum of W' AS STORED -- rounded to bf16 / f16, or the bf16 (hi, lo) pair of the split-precision modes -- so that the
+    mean of a sample cancels against the very weights the matrix cores multiply; the sum here runs over the same rounded values."""
+    w64 = w.double().reshape(w.shape[0], w.shape[1], -1)         # (a k x k weight folds the same way; the launcher takes 1x1 only)
+    wg = (w64 * gamma.double()[None, :, None]).float().reshape(w.shape[0], -1)
+    c0 = (w64 * beta.double()[None, :, None]).sum((1, 2)).float()
+    if dt in (BF16, F16):
+        stored = wg.to(torch_dtype(dt)).double()
+    elif dt in (BF16X3, F16X2):
+        hi = wg.to(torch.bfloat16)
+        stored = hi.double() + (wg - hi.float()).to(torch.bfloat16).double()
+    else:
+        stored = wg.double()
+    return wg.reshape(w.shape).contiguous(), c0.contiguous(), stored.sum(1).float().contiguous()
+
+
+def op_conv_ex(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+               src2: Optional[torch.Tensor] = None, mode: int = CONV_PLAIN, rep1: int = 1, rep2: int = 1,
+               resid: Optional[torch.Tensor] = None, n_hyp: Optional[int] = None, out_nchw: bool = False,
+               out_dtype: int = F32, act_relu: bool = False, split_k: bool = False, colstats: Optional[torch.Tensor] = None,
+               stat_rows: int = 0, prenorm: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, want_amax: bool = False):
+    """op_conv through nope_op_conv_ex: `colstats` (an f32 tensor of at least [M / stat_rows][Cout][2] values, written in place) with
+    `stat_rows` as op_conv_stat_rows answered; prenorm = (ms [n_hyp][2], gamma, beta): the conv reads the UN-normalised tensor and applies
+    GroupNorm(1) in its epilogue (prenorm_fold); want_amax: returns (out, max |out| as the launch recorded it, whether it did record).
+    A combination the launcher refuses raises NopeError."""
+    pn = None
+    if prenorm is not None:
+        ms, gamma, beta = prenorm
+        w, c0, c1 = prenorm_fold(w.cpu(), gamma.cpu(), beta.cpu(), dt)
+        pn = (_f32c(ms), c0.to(src1.device), c1.to(src1.device))
+        w = w.to(src1.device)
+    pw, cin, ntaps = pack_conv_weight(w, dt, mode)
+    n1, hs, ws, c1_ = src1.shape
+    c2 = 0 if src2 is None else src2.shape[3]
+    assert c1_ + c2 == cin
+    n_hyp = n_hyp if n_hyp is not None else n1 * rep1
+    ho, wo = (2 * hs, 2 * ws) if mode in (CONV_UP2, CONV_UP2P) else ((hs // 2, ws // 2) if mode in (CONV_DOWN2, CONV_STRIDE2, CONV_STRIDE2_PAD01) else (hs, ws))
+    cout = w.shape[0]
+    if out_nchw:
+        out = torch.empty((n_hyp, cout, ho, wo), dtype=torch_dtype(out_dtype), device=src1.device)
+    else:
+        out = torch.empty((n_hyp, ho, wo, cout), dtype=torch_dtype(dt), device=src1.device)
+    b = None if bias is None else _f32c(bias)
+    l = lib()
+    scratch, sk = None, 0
+    if split_k:
+        sk = int(l.dll.nope_op_conv_splitk_bytes(dt, c1_, c2, rep1, hs, ws, mode, ntaps, cout, n_hyp))
+        if sk:
+            scratch = torch.empty(sk, dtype=torch.uint8, device=src1.device)
+    if colstats is not None:
+        assert colstats.dtype == torch.float32 and colstats.is_contiguous()
+        assert stat_rows <= 0 or colstats.numel() >= (n_hyp * ho * wo // stat_rows) * cout * 2
+    slot, amax = _amax_scratch(src1.device) if want_amax else (None, None)
+    rec = _i(0)
+    l.check(l.dll.nope_op_conv_ex(dt, _ptr(src1), c1_, rep1, _ptr(src2), c2, rep2, hs, ws, mode, ntaps, _ptr(pw), _ptr(b),
+                                  _ptr(resid), _ptr(out), cout, n_hyp, int(out_nchw), out_dtype, int(act_relu), _ptr(scratch), sk,
+                                  _ptr(colstats), int(stat_rows), _ptr(pn[0]) if pn else None, _ptr(pn[1]) if pn else None,
+                                  _ptr(pn[2]) if pn else None, _ptr(slot), _ptr(amax), C.byref(rec), _stream(src1)), "nope_op_conv_ex")
+    if want_amax:
+        return out, float(amax.item()), bool(rec.value)
+    return out
+
+
+def op_gn_apply_blocks(dt: int, hw: int, c: int, n_hyp: int) -> int:
+    """Workgroups per hypothesis of a GroupNorm apply launch = chunks per hypothesis of its out_stats."""
+    return int(lib().dll.nope_op_gn_apply_blocks(storage_code(dt), hw, c, n_hyp))
+
+
+def op_group_norm_ex(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, act_silu: bool = False,
+                     emb: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, film: Optional[torch.Tensor] = None,
+                     colstats: Optional[torch.Tensor] = None, fold_launch: bool = False, x_rep: int = 1, resid_rep: int = 1,
+                     out_stats: bool = False, eps: float = 1e-5, fast_silu: bool = False, want_amax: bool = False):
+    """op_group_norm through nope_op_group_norm_ex (include/nope_hip.h).  x NHWC [n_x][h][w][C], n_hyp = n_x * x_rep; emb (n_hyp, C);
+    resid NHWC of n_hyp / resid_rep samples; film (n_hyp, 2 C) = one [scale | shift] row per hypothesis, or (2 C,) = one row for all;
+    colstats [n_x][blocks][C][2] f32 column statistics instead of a statistics pass (fold_launch: folded by its own launch).
+    Returns y, or (y, extras) with extras["out_stats"] [n_hyp][op_gn_apply_blocks][2] / extras["amax"] when asked for."""
+    nx, h, w, c = x.shape
+    n = nx * x_rep
+    l = lib()
+    dt = storage_code(dt)
+    g, b = _f32c(gamma), _f32c(beta)
+    e = None if emb is None else _f32c(emb)
+    f = None if film is None else _f32c(film)
+    fstride = 0 if f is None or f.dim() == 1 else f.shape[1]
+    if colstats is not None:
+        assert colstats.dtype == torch.float32 and colstats.is_contiguous() and tuple(colstats.shape[::3]) == (nx, 2) and colstats.shape[2] == c
+        partial = torch.empty((nx, groups, 2), dtype=torch.float32, device=x.device) if fold_launch else None
+        blocks = colstats.shape[1]
+    else:
+        partial = torch.empty((nx, l.dll.nope_op_gn_chunks(dt, h * w, c), groups, 2), dtype=torch.float32, device=x.device)
+        blocks = 0
+    y = torch.empty((n, h, w, c), dtype=x.dtype, device=x.device)
+    os_ = torch.empty((n, op_gn_apply_blocks(dt, h * w, c, n), 2), dtype=torch.float32, device=x.device) if out_stats else None
+    slot, amax = _amax_scratch(x.device) if want_amax else (None, None)
+    l.check(l.dll.nope_op_group_norm_ex(dt, _ptr(x), _ptr(y), _ptr(partial), _ptr(colstats), blocks, int(fold_launch), _ptr(g), _ptr(b),
+                                        n, h * w, c, groups, int(act_silu), _ptr(e), 0 if e is None else e.shape[1], _ptr(f), fstride,
+                                        _ptr(resid), x_rep, resid_rep, _ptr(os_), float(eps), int(fast_silu), _ptr(slot), _ptr(amax),
+                                        _stream(x)), "nope_op_group_norm_ex")
+    if not (out_stats or want_amax):
+        return y
+    extras = {}
+    if out_stats:
+        extras["out_stats"] = os_
+    if want_amax:
+        extras["amax"] = float(amax.item())
+    return y, extras
+
+
+def op_gn_finalize(partial: torch.Tensor, count: float, eps: float = 1e-5) -> torch.Tensor:
+    """partial [n][chunks][2] (sum, sum of squares) pairs of whole samples -> [n][2] (mean, rstd) of GroupNorm(1) over `count` values."""
+    partial = _f32c(partial)
+    n, nch, _ = partial.shape
+    ms = torch.empty((n, 2), dtype=torch.float32, device=partial.device)
+    l = lib()
+    l.check(l.dll.nope_op_gn_finalize(_ptr(partial), _ptr(ms), n, nch, float(count), float(eps), _stream(partial)), "nope_op_gn_finalize")
+    return ms
+
+
+def op_absmax(x: torch.Tensor) -> float:
+    """max |x| of an f32 tensor as the range tracking computes it (NaNs ignored)."""
+    require_device(x)
+    x = _f32c(x).reshape(-1)
+    slot, amax = _amax_scratch(x.device)
+    l = lib()
+    l.check(l.dll.nope_op_absmax_f32(_ptr(x), x.numel(), _ptr(slot), _ptr(amax), _stream(x)), "nope_op_absmax_f32")
+    return float(amax.item())
 
 
 def op_linear_attention(dt: int, qkv: torch.Tensor, heads: int = 4, dim_head: int = 32, full: bool = False) -> torch.Tensor:
