@@ -8,6 +8,7 @@ nope_amd/csrc/libnope_hip.so (git-ignored; travels to the GPU box with the snaps
 from __future__ import annotations
 
 import concurrent.futures
+import glob
 import os
 import shutil
 import subprocess
@@ -65,7 +66,7 @@ def build(force: bool = False, verbose: bool = False, variant: str = "", defines
     objdir = os.path.join(ROOT, "build", "hip" + ("_" + variant if variant else ""))
     os.makedirs(objdir, exist_ok=True)
     LIB = os.path.join(HERE, f"libnope_hip{'_' + variant if variant else ''}.so")
-    headers = [os.path.join(HERE, "nope_common.h"), os.path.join(HERE, "conv_gemm_common.h"), os.path.join(HERE, "conv_gemm_dma.h"), os.path.join(HERE, "x2_range.h"), os.path.join(HERE, "resblock_runtime.h"), os.path.join(ROOT, "include", "nope_hip.h")]
+    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + [os.path.join(ROOT, "include", "nope_hip.h")]      # every source is rebuilt when any header changes
     flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + list(defines)
 
     def compile_one(src: str) -> str:

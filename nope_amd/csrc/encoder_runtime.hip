@@ -11,22 +11,21 @@
 // layers have only 8-32 output tiles for 256 CUs, so those launches are split along K (deterministic: f32 partials +
 // a fixed-order reduce that also applies bias / residual / ReLU).  Activations live in five ping-pong buffers of a
 // caller-provided workspace: no allocation, no host sync, one stream.
-#include <cstdio>
+//
+// The create-time loader and the arena are the shared ones (runtime_common.h: LoaderCore bound to this handle's `allocs`, Arena); the
+// BatchNorm fold goes through the conv-packing skeleton's per-output-channel scale.  The workspace is used from the pointer given: the
+// entry points do not move the base (nope_encoder_workspace_bytes has no spare bytes for it).
 #include <cstdlib>
-#include <initializer_list>
-#include <map>
 #include <mutex>
-#include <string>
-#include <vector>
 
-#include "nope_common.h"
+#include "runtime_common.h"
 
 using namespace nope;
+using namespace nope::rt;
 
 namespace {
 
-struct EConv { void* w = nullptr; float* bias = nullptr; int Cin = 0, Cout = 0, ntaps = 1, mode = NOPE_CONV_PLAIN; };
-struct Bottleneck { EConv c1, c2, c3, ds; bool has_ds = false; };
+struct Bottleneck { PackedConv c1, c2, c3, ds; bool has_ds = false; };
 
 constexpr int LAYERS[4] = {3, 4, 6, 3};       // resnet.py:179-185 (resnet50)
 constexpr int STRIDES[4] = {1, 2, 2, 1};      // resnet.py:102-105
@@ -49,35 +48,14 @@ struct nope_encoder {
     float* stem_shift = nullptr;  // [64]
     std::vector<Bottleneck> blocks;
     std::vector<int> block_stride;
-    EConv proj0, proj1;
+    PackedConv proj0, proj1;
 };
 
 namespace {
 
-struct ELoader {
+struct ELoader : LoaderCore {      // (the handle is no rt::Net: the loader core is bound to its `allocs` alone)
     nope_encoder* enc;
-    hipStream_t s;
-    std::map<std::string, const nope_tensor_desc*> tab;
-    int err = NOPE_OK;
-    std::string missing;
-
-    void fail(const std::string& n) { if (err == NOPE_OK) { err = NOPE_ERR_WEIGHT; missing = n; } }
-    const nope_tensor_desc* get(const std::string& name, std::initializer_list<int64_t> shape) {
-        auto it = tab.find(name);
-        if (it == tab.end() || !it->second->data) { fail(name); return nullptr; }
-        const nope_tensor_desc* d = it->second;
-        if (d->ndim != (int)shape.size()) { fail(name); return nullptr; }
-        int i = 0;
-        for (int64_t v : shape) if (d->shape[i++] != v) { fail(name); return nullptr; }
-        return d;
-    }
-    void* dmalloc(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err == NOPE_OK) err = NOPE_ERR_ALLOC; return nullptr; }
-        enc->allocs.push_back(p);
-        return p;
-    }
-    void chk(int e) { if (e != NOPE_OK && err == NOPE_OK) err = e; }
+    ELoader(nope_encoder* e, hipStream_t s_, const nope_tensor_desc* tensors, int n_tensors) : LoaderCore(e->allocs, e->dt, s_, tensors, n_tensors), enc(e) {}
     // (scale, shift) of the eval-mode BatchNorm2d `pfx` over C channels
     bool bn(const std::string& pfx, int C, float*& scale, float*& shift) {
         const nope_tensor_desc* g = get(pfx + "weight", {C});
@@ -91,31 +69,14 @@ struct ELoader {
         return true;
     }
     // conv `wname` (bias-free in the reference) followed by BatchNorm `bnpfx` -> packed weights * scale, bias = shift
-    EConv conv_bn(const std::string& wname, const std::string& bnpfx, int Cin, int Cout, int ksz, int stride) {
-        EConv c;
-        c.Cin = Cin; c.Cout = Cout; c.ntaps = ksz * ksz; c.mode = stride == 2 ? NOPE_CONV_STRIDE2 : NOPE_CONV_PLAIN;
+    PackedConv conv_bn(const std::string& wname, const std::string& bnpfx, int Cin, int Cout, int ksz, int stride) {
         const nope_tensor_desc* d = get(wname, {Cout, Cin, ksz, ksz});
-        float* scale = nullptr;
-        if (!bnpfx.empty()) { if (!bn(bnpfx, Cout, scale, c.bias)) return c; }
-        if (d) {
-            const size_t es = (size_t)dt_es(enc->dt);
-            c.w = dmalloc((size_t)Cout * c.ntaps * Cin * es);
-            if (c.w) chk(launch_pack_conv_w(enc->dt, d->data, c.w, Cout, Cin, c.ntaps, NOPE_CONV_PLAIN, s, nullptr, scale));
-        }
+        float *scale = nullptr, *shift = nullptr;
+        if (!bnpfx.empty() && !bn(bnpfx, Cout, scale, shift)) d = nullptr;      // (reported: nothing to pack)
+        // (the stride is the launch's geometry: the weights are packed as a plain conv's, the BatchNorm scale folded into their rows)
+        PackedConv c = pack_conv(d, wname, Cin, Cin, Cout, ksz * ksz, stride == 2 ? NOPE_CONV_STRIDE2 : NOPE_CONV_PLAIN, false, false, 0, NOPE_CONV_PLAIN, nullptr, scale);
+        c.bias = shift;
         return c;
-    }
-};
-
-struct EArena {
-    unsigned char* base = nullptr;
-    size_t cap = 0, off = 0;
-    bool dry = false;
-    void* alloc(size_t bytes) {
-        const size_t o = align_up(off, 256);
-        off = o + bytes;
-        if (dry) return (void*)(uintptr_t)(0x1000 + o);
-        if (off > cap) return nullptr;
-        return base + o;
     }
 };
 
@@ -143,7 +104,7 @@ Plan plan_for(int H, int W) {
     return p;
 }
 
-int run_encoder(const nope_encoder* enc, const float* image, int n_img, int H, int W, float* out, EArena& ar, hipStream_t s) {
+int run_encoder(const nope_encoder* enc, const float* image, int n_img, int H, int W, float* out, Arena& ar, hipStream_t s) {
     const size_t es = (size_t)dt_es(enc->dt);
     const Plan pl = plan_for(H, W);
     void* X[3] = {nullptr, nullptr, nullptr};
@@ -152,7 +113,7 @@ int run_encoder(const nope_encoder* enc, const float* image, int n_img, int H, i
     bool measure = true;
 
     // One conv launch; in the measuring pass it only records the split-K scratch the launch would like.
-    auto conv = [&](const EConv& c, const void* src, int Hs, int Ws, void* dst, int act, const void* resid, int out_nchw) -> int {
+    auto conv = [&](const PackedConv& c, const void* src, int Hs, int Ws, void* dst, int act, const void* resid, int out_nchw) -> int {
         ConvArgs a;
         a.src1 = src; a.C1 = c.Cin; a.Hs = Hs; a.Ws = Ws;
         a.Ho = c.mode == NOPE_CONV_STRIDE2 ? Hs / 2 : Hs; a.Wo = c.mode == NOPE_CONV_STRIDE2 ? Ws / 2 : Ws;
@@ -217,8 +178,7 @@ int nope_encoder_create(const nope_encoder_config* cfg, const nope_tensor_desc* 
     enc->cfg = *cfg;
     if (enc->cfg.bn_eps <= 0.f) enc->cfg.bn_eps = 1e-5f;      // nn.BatchNorm2d default
     enc->dt = dt_base(cfg->compute_dtype);      // (NOPE_F16X2 = NOPE_BF16X3 here: the encoder has no tap-resident launches worth a second weight pack)
-    ELoader L{enc, (hipStream_t)stream};
-    for (int i = 0; i < n_tensors; ++i) if (tensors[i].name) L.tab[tensors[i].name] = &tensors[i];
+    ELoader L(enc, (hipStream_t)stream, tensors, n_tensors);
 
     {   // conv1 + bn1 (resnet.py:98-99)
         float* scale = nullptr;
@@ -247,20 +207,13 @@ int nope_encoder_create(const nope_encoder_config* cfg, const nope_tensor_desc* 
     }
     enc->proj0 = L.conv_bn("projector.1.weight", "", cin, 256, 1, 1);
     enc->proj1 = L.conv_bn("projector.3.weight", "", 256, D, 1, 1);
-    if (hipStreamSynchronize(L.s) != hipSuccess && L.err == NOPE_OK) L.err = NOPE_ERR_LAUNCH;   // the sources may be freed by the caller
-    if (L.err != NOPE_OK) {
-        if (L.err == NOPE_ERR_WEIGHT) fprintf(stderr, "nope_encoder_create: missing or mis-shaped tensor '%s'\n", L.missing.c_str());
-        nope_encoder_destroy(enc);
-        return L.err;
-    }
-    *out = enc;
-    return NOPE_OK;
+    return finish_create(L, "nope_encoder_create", enc, nope_encoder_destroy, out);
 }
 
 void nope_encoder_destroy(nope_encoder* enc) {
     if (!enc) return;
     for (const EGraph& g : enc->graphs) hipGraphExecDestroy(g.exec);
-    for (void* p : enc->allocs) hipFree(p);
+    free_device(enc->allocs);
     delete enc;
 }
 
@@ -273,7 +226,7 @@ static size_t stage_bytes(const nope_encoder* enc, int n_img, int H, int W, size
 
 size_t nope_encoder_workspace_bytes(const nope_encoder* enc, int n_img, int H, int W) {
     if (!enc || n_img <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return 0;
-    EArena ar;
+    Arena ar;
     ar.dry = true;
     if (run_encoder(enc, nullptr, n_img, H, W, nullptr, ar, nullptr) != NOPE_OK) return 0;
     size_t ib, ob;
@@ -292,7 +245,7 @@ int nope_encoder_forward(const nope_encoder* enc, const float* image, int n_img,
     float* img_s = (float*)base;
     float* out_s = (float*)(base + ib);
     auto direct = [&](const float* src, float* dst) {
-        EArena ar;
+        Arena ar;
         ar.base = base + sb; ar.cap = workspace_bytes - sb;
         return run_encoder(enc, src, n_img, H, W, dst, ar, s);
     };
@@ -309,7 +262,7 @@ int nope_encoder_forward(const nope_encoder* enc, const float* image, int n_img,
     if (!hit) {
         // First call for this (workspace, shape): record the launch sequence once.
         {   // dry pass: fail on a too-small arena BEFORE a capture is open
-            EArena chk; chk.dry = true;
+            Arena chk; chk.dry = true;
             int e = run_encoder(enc, nullptr, n_img, H, W, nullptr, chk, nullptr);
             if (e) return e;
             if (align_up(chk.off, 256) > workspace_bytes - sb) return NOPE_ERR_WORKSPACE;

@@ -7,7 +7,8 @@
 // raises TypeError); the one reading that type-checks is `module(h, emb)`, and that is what runs here: emb feeds every ResBlock's
 // emb_layers (SiLU -> Linear), added to h or, with use_scale_shift_norm, applied as FiLM by the out_layers GroupNorm.
 //
-// ResBlocks, resampling, the arena and the NOPE_F16X2 range tracking are the LDM runtime's (resblock_runtime.h).  What is new:
+// ResBlocks and resampling are the LDM runtime's (resblock_runtime.h); the loader core, the arena, the conv / GroupNorm launches with the
+// NOPE_F16X2 range tracking and the entry-point bodies are every network runtime's (runtime_common.h).  What is new:
 //   * AttentionBlock: GroupNorm(32, eps 1e-5) -> qkv (a 1x1 conv over the NHWC tokens) -> softmax attention over the H*W tokens of a
 //     sample on the LDM token-attention kernels -> proj_out (1x1 conv) with the residual x in its epilogue.  The legacy order's qkv rows
 //     (head, q|k|v, ch) are permuted to [q | k | v] (head-major inside each) at create time, which is QKVAttention's order already;
@@ -15,11 +16,6 @@
 //   * the embedding is never zero: no emb_layers bias is folded; the pose MLP (Linear; Linear, GELU, Linear; or the sinusoidal
 //     encoding) runs once per forward, each ResBlock's emb_layers once per ResBlock, on all hypotheses at once;
 //   * time_embed.* is never evaluated (the reference does not call it either) and is not read.
-#include <cstdio>
-#include <map>
-#include <string>
-#include <vector>
-
 #include "resblock_runtime.h"
 
 using namespace nope;
@@ -27,17 +23,17 @@ using namespace nope::rb;
 
 namespace {
 
-struct LAttn { LNorm norm; LConv qkv, proj; int C = 0, dh = 32; };             // AttentionBlock; dh: head width
+struct LAttn { NormW norm; PackedConv qkv, proj; int C = 0, dh = 32; };             // AttentionBlock; dh: head width
 // has_resample: a Downsample / Upsample slot -- its conv (conv_resample), or with resample.w = null avg_pool 2x2 / nearest x2 alone; under
 // resblock_updown the input-block slot holds a ResBlock (res.updown = RES_DOWN), the output block's slot one in `up` (RES_UP)
-struct GBlock { bool has_res = false, has_attn = false, has_resample = false; LRes res, up; LAttn attn; LConv resample; };
+struct GBlock { bool has_res = false, has_attn = false, has_resample = false; LRes res, up; LAttn attn; PackedConv resample; };
 
 }  // namespace
 
 struct nope_gd : RtNet {       // (dt / sdt / x2 / x2r / allocs / emb_dim: RtNet, resblock_runtime.h)
     nope_gd_config cfg;
-    LConv conv_in, conv_out;
-    LNorm norm_out;
+    PackedConv conv_in, conv_out;
+    NormW norm_out;
     std::vector<GBlock> input_blocks, output_blocks;     // input_blocks[0] is conv_in
     LRes mid1, mid2;
     LAttn mid_attn;
@@ -48,10 +44,11 @@ namespace {
 
 struct Loader : LoaderBase {
     nope_gd* gd;
+    Loader(nope_gd* n, hipStream_t s_, const nope_tensor_desc* tensors, int n_tensors) : LoaderBase(n, s_, tensors, n_tensors), gd(n) {}
     // conv_nd(1, Cin, Cout, 1) (weight [Cout][Cin][1]) as a 1x1 conv over the NHWC tokens; perm_heads > 0: the legacy qkv order, rows
     // (head, q|k|v, ch) with ch = Cout / 3 / perm_heads, reordered to (q|k|v, head, ch) -- weights and bias
-    LConv conv1d(const std::string& pfx, int Cin, int Cout, int perm_heads = 0) {
-        LConv c;
+    PackedConv conv1d(const std::string& pfx, int Cin, int Cout, int perm_heads = 0) {
+        PackedConv c;
         c.Cin = Cin; c.Cout = Cout; c.mode = NOPE_CONV_PLAIN; c.ntaps = 1;
         const nope_tensor_desc* d = get(pfx + "weight", {Cout, Cin, 1});
         const nope_tensor_desc* bd = get(pfx + "bias", {Cout});
@@ -97,7 +94,7 @@ struct Fwd : FwdBase {
         void* xn = alloc_act(M * C);
         void* qkv = alloc_act(M * 3 * C);
         void* o = alloc_act(M * C);
-        gn(A.norm, x.p, xn, HW, 0, 1e-5f);
+        gn(A.norm, 32, x.p, xn, HW, 0, 1e-5f);
         conv(A.qkv, Act{xn, C, x.H, x.W}, qkv, x.H, x.W);
         if (live()) chk(launch_token_attention(net->dt, qkv, o, nhyp, HW, C, A.dh, s));
         if (tracking()) x2.overwritten(o);
@@ -110,9 +107,7 @@ int run_forward(const nope_gd* net, const float* x, int n_src, int x_rep, const 
                 int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak) {
     const nope_gd_config& cfg = net->cfg;
     Fwd f;
-    f.net = net; f.s = s; f.nhyp = n_hyp; f.es = (size_t)dt_es(net->dt);
-    f.ar.base = (unsigned char*)ws; f.ar.cap = ws_bytes; f.ar.dry = dry;
-    f.x2.r = &net->x2r; f.x2.s = s; f.x2.on = net->x2 && net->x2r.active() && !dry;
+    f.begin(net, n_hyp, ws, ws_bytes, s, dry);
     const int HW = H * W;
     const int cin_k = net->conv_in.Cin;          // in_channels rounded up to a whole 16-byte vector
     const int E = net->emb_dim;
@@ -204,7 +199,7 @@ int run_forward(const nope_gd* net, const float* x, int n_src, int x_rep, const 
     // out: GroupNorm32 + SiLU + conv 3x3 straight into the NCHW output
     {
         void* t = f.alloc_act((size_t)n_hyp * HW * h.C);
-        f.gn(net->norm_out, h.p, t, HW, 1, 1e-5f);
+        f.gn(net->norm_out, 32, h.p, t, HW, 1, 1e-5f);
         f.conv(net->conv_out, Act{t, h.C, H, W}, out, H, W, nullptr, 1, out_dtype);
     }
     if (f.tracking())      // the forward's verdict; NaNs over the output of a forward whose layers left their windows (x2_range.h)
@@ -249,10 +244,7 @@ int nope_gd_create(const nope_gd_config* cfg, const nope_tensor_desc* tensors, i
     net->emb_dim = mc * 4;
     net->film = cfg->use_scale_shift_norm != 0;
     net->emb_zero = false;
-    Loader ld;
-    ld.net = net; ld.gd = net; ld.s = s;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name) ld.tab[tensors[i].name] = &tensors[i];
+    Loader ld(net, s, tensors, n_tensors);
 
     const int E = net->emb_dim;
     if (cfg->pose_mlp != NOPE_GD_POSE_ENCODING) {       // adapt_u_net.py:62-73
@@ -325,44 +317,20 @@ int nope_gd_create(const nope_gd_config* cfg, const nope_tensor_desc* tensors, i
     net->conv_out = ld.conv("out.2.", ch0, cfg->out_channels, 3, NOPE_CONV_PLAIN, true);
     if (ch != ch0) ld.fail("out.2.weight");
 
-    if (ld.err == NOPE_OK) { const int e = net->x2r.init([&](size_t bytes) { return ld.dmalloc(bytes); }, s); if (e) ld.err = e; }
-    if (hipStreamSynchronize(s) != hipSuccess && ld.err == NOPE_OK) ld.err = NOPE_ERR_LAUNCH;
-    ld.free_temps();
-    if (ld.err != NOPE_OK) {
-        if (!ld.missing.empty()) fprintf(stderr, "nope_gd_create: missing or mis-shaped tensor '%s'\n", ld.missing.c_str());
-        nope_gd_destroy(net);
-        return ld.err;
-    }
-    *out = net;
-    return NOPE_OK;
+    ld.init_x2();
+    return finish_create(ld, "nope_gd_create", net, nope_gd_destroy, out);
 }
 
 void nope_gd_destroy(nope_gd* net) {
     if (!net) return;
-    for (void* p : net->allocs) hipFree(p);
-    net->x2r.destroy();
+    free_device(net->allocs, &net->x2r);
     delete net;
 }
 
 // NOPE_F16X2 activation ranges of the guided-diffusion variant: as nope_ldm_x2_poll / _x2_range_check / _x2_enable
-int nope_gd_x2_poll(nope_gd* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) {
-    if (n_out_of_range) *n_out_of_range = 0;
-    if (n_adjusted) *n_adjusted = 0;
-    if (max_abs) *max_abs = 0.f;
-    if (!net) return NOPE_ERR_ARG;
-    if (!net->x2) return NOPE_OK;
-    return net->x2r.poll((hipStream_t)stream, n_out_of_range, n_adjusted, max_abs);
-}
-int nope_gd_x2_range_check(nope_gd* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) {
-    if (!net) return NOPE_ERR_ARG;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NOPE_ERR_LAUNCH;
-    return nope_gd_x2_poll(net, stream, n_out_of_range, n_adjusted, max_abs);
-}
-int nope_gd_x2_enable(nope_gd* net, int on) {
-    if (!net) return NOPE_ERR_ARG;
-    net->x2r.off = on == 0;
-    return NOPE_OK;
-}
+int nope_gd_x2_poll(nope_gd* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) { return x2_poll(net, stream, n_out_of_range, n_adjusted, max_abs); }
+int nope_gd_x2_range_check(nope_gd* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) { return x2_range_check(net, stream, n_out_of_range, n_adjusted, max_abs); }
+int nope_gd_x2_enable(nope_gd* net, int on) { return x2_enable(net, on); }
 
 size_t nope_gd_workspace_bytes(const nope_gd* net, int n_hyp, int n_src, int H, int W) {
     if (!net || n_src <= 0 || n_hyp % n_src) return 0;
@@ -378,11 +346,11 @@ int nope_gd_forward(const nope_gd* net, const float* x, int n_src, int x_rep, co
     if (e) return e;
     if (!x || !pose || !out || !workspace) return NOPE_ERR_ARG;
     if (out_dtype != NOPE_F32 && out_dtype != NOPE_BF16 && out_dtype != NOPE_F16) return NOPE_ERR_UNSUPPORTED;
-    unsigned char* base = (unsigned char*)(((uintptr_t)workspace + 255) / 256 * 256);
-    const size_t lost = (size_t)(base - (unsigned char*)workspace);
-    if (workspace_bytes < lost) return NOPE_ERR_WORKSPACE;
-    if (net->x2 && net->x2r.active()) (void)net->x2r.poll((hipStream_t)stream, nullptr, nullptr, nullptr);      // verdicts that have arrived: re-centre first
-    return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, workspace_bytes - lost, (hipStream_t)stream, false, nullptr);
+    unsigned char* base;
+    size_t cap;
+    if (!workspace_base(workspace, workspace_bytes, base, cap)) return NOPE_ERR_WORKSPACE;
+    x2_poll_before_forward(net, stream);
+    return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, cap, (hipStream_t)stream, false, nullptr);
 }
 
 }  // extern "C"

@@ -17,11 +17,8 @@
 //   * FiLM (use_scale_shift_norm) costs no pass: out_norm(h) * (1 + scale) + shift is folded into the per-channel affine the
 //     GroupNorm-apply kernel evaluates anyway (kernels_norm.hip);
 //   * th.cat((h, skip)) is materialised (GroupNorm(32) groups of the following ResBlock can straddle the two halves).
-#include <cstdio>
-#include <map>
-#include <string>
-#include <vector>
-
+//
+// Loader core, arena, conv / GroupNorm launches and the entry-point bodies: runtime_common.h; ResBlocks and resampling: resblock_runtime.h.
 #include "resblock_runtime.h"
 
 using namespace nope;
@@ -29,18 +26,18 @@ using namespace nope::rb;
 
 namespace {
 
-struct LTB { LNorm ln1, ln3; LConv qkv, out1, ff1, ff2; int u_off = 0; };         // one BasicTransformerBlock; u_off: its slice of nope_ldm::u_w
-struct LST { LNorm norm; LConv proj_in, proj_out; std::vector<LTB> blocks; int C = 0, dh = 32; };      // dh: attention head width (dim_head)
+struct LTB { NormW ln1, ln3; PackedConv qkv, out1, ff1, ff2; int u_off = 0; };         // one BasicTransformerBlock; u_off: its slice of nope_ldm::u_w
+struct LST { NormW norm; PackedConv proj_in, proj_out; std::vector<LTB> blocks; int C = 0, dh = 32; };      // dh: attention head width (dim_head)
 // has_resample: a Downsample / Upsample slot -- its conv (conv_resample), or with resample.w = null avg_pool 2x2 / nearest x2 alone; under
 // resblock_updown the input-block slot holds a ResBlock (res.updown = RES_DOWN), the output block's slot one in `up` (RES_UP)
-struct LBlock { bool has_res = false, has_st = false, has_resample = false; LRes res, up; LST st; LConv resample; };     // up: an output block's ResBlock(up=True)
+struct LBlock { bool has_res = false, has_st = false, has_resample = false; LRes res, up; LST st; PackedConv resample; };     // up: an output block's ResBlock(up=True)
 
 }  // namespace
 
 struct nope_ldm : RtNet {      // (dt / sdt / x2 / x2r / allocs / emb_dim: RtNet, resblock_runtime.h)
     nope_ldm_config cfg;
-    LConv conv_in, conv_out;
-    LNorm norm_out;
+    PackedConv conv_in, conv_out;
+    NormW norm_out;
     std::vector<LBlock> input_blocks, output_blocks;     // input_blocks[0] is conv_in
     LRes mid1, mid2;
     LST mid_st;
@@ -55,13 +52,14 @@ namespace {
 
 struct Loader : LoaderBase {
     nope_ldm* ldm;
+    Loader(nope_ldm* n, hipStream_t s_, const nope_tensor_desc* tensors, int n_tensors) : LoaderBase(n, s_, tensors, n_tensors), ldm(n) {}
     struct UPart { float* comb; float* bias; int C, off; };
     std::vector<UPart> u_parts;
     int u_total = 0;
     // GEGLU's projection (attention.py:37-44: `x, gate = proj(x).chunk(2, dim=-1)`): rows (x_j, gate_j) interleaved, so that a lane of the conv
     // epilogue holds whole pairs (ConvArgs::geglu); the unfused path reads the same layout (launch_geglu(..., interleaved))
-    LConv conv_geglu(const std::string& pfx, int Cin, int D) {
-        LConv c;
+    PackedConv conv_geglu(const std::string& pfx, int Cin, int D) {
+        PackedConv c;
         c.Cin = Cin; c.Cout = 2 * D; c.mode = NOPE_CONV_PLAIN; c.ntaps = 1;
         const nope_tensor_desc* d = get(pfx + "weight", {2 * D, Cin});
         const nope_tensor_desc* bd = get(pfx + "bias", {2 * D});
@@ -151,7 +149,7 @@ struct Fwd : FwdBase {
         void* tok1 = alloc_act((size_t)M * C);
         void* g = alloc_act((size_t)M * 8 * C);
         void* gg = alloc_act((size_t)M * 4 * C);
-        gn(T.norm, x.p, xn, HW, 0, 1e-6f);
+        gn(T.norm, 32, x.p, xn, HW, 0, 1e-6f);
         conv(T.proj_in, Act{xn, C, x.H, x.W}, tok, x.H, x.W);
         for (const LTB& B : T.blocks) {
             // attn1 (self-attention) + residual
@@ -190,9 +188,8 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
                 int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak) {
     const nope_ldm_config& cfg = net->cfg;
     Fwd f;
-    f.net = net; f.ldm = net; f.s = s; f.nhyp = n_hyp; f.es = (size_t)dt_es(net->dt);
-    f.ar.base = (unsigned char*)ws; f.ar.cap = ws_bytes; f.ar.dry = dry;
-    f.x2.r = &net->x2r; f.x2.s = s; f.x2.on = net->x2 && net->x2r.active() && !dry;
+    f.begin(net, n_hyp, ws, ws_bytes, s, dry);
+    f.ldm = net;
     const int HW = H * W;
     const int cin_k = net->conv_in.Cin;          // in_channels rounded up to a whole 16-byte vector
     void* x_in = f.alloc_act((size_t)n_src * HW * cin_k);
@@ -291,7 +288,7 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
     // out: GroupNorm32 + SiLU + conv 3x3 (openaimodel.py:733-737) straight into the NCHW output
     {
         void* t = f.alloc_act((size_t)n_hyp * HW * h.C);
-        f.gn(net->norm_out, h.p, t, HW, 1, 1e-5f);
+        f.gn(net->norm_out, 32, h.p, t, HW, 1, 1e-5f);
         f.conv(net->conv_out, Act{t, h.C, H, W}, out, H, W, nullptr, 1, out_dtype);
     }
     if (f.tracking())      // the forward's verdict; NaNs over the output of a forward whose layers left their windows (x2_range.h)
@@ -333,10 +330,7 @@ int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors,
     net->emb_zero = !cfg->injecting_condition_twice;
     const int mc = cfg->model_channels;
     auto dh = [&](int level) { return cfg->num_head_channels > 0 ? cfg->num_head_channels : cfg->head_channels[level]; };
-    Loader ld;
-    ld.net = net; ld.ldm = net; ld.s = s;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name) ld.tab[tensors[i].name] = &tensors[i];
+    Loader ld(net, s, tensors, n_tensors);
 
     net->pose_w0 = ld.copy_f32("pose_mlp.0.weight", {cfg->context_dim, cfg->pose_dim});
     net->pose_b0 = ld.copy_f32("pose_mlp.0.bias", {cfg->context_dim});
@@ -421,44 +415,20 @@ int nope_ldm_create(const nope_ldm_config* cfg, const nope_tensor_desc* tensors,
                 ld.copy_d2d(net->u_b + up.off, up.bias, (size_t)up.C * 4);
             }
     }
-    if (ld.err == NOPE_OK) { const int e = net->x2r.init([&](size_t bytes) { return ld.dmalloc(bytes); }, s); if (e) ld.err = e; }
-    if (hipStreamSynchronize(s) != hipSuccess && ld.err == NOPE_OK) ld.err = NOPE_ERR_LAUNCH;
-    ld.free_temps();
-    if (ld.err != NOPE_OK) {
-        if (!ld.missing.empty()) fprintf(stderr, "nope_ldm_create: missing or mis-shaped tensor '%s'\n", ld.missing.c_str());
-        nope_ldm_destroy(net);
-        return ld.err;
-    }
-    *out = net;
-    return NOPE_OK;
+    ld.init_x2();
+    return finish_create(ld, "nope_ldm_create", net, nope_ldm_destroy, out);
 }
 
 void nope_ldm_destroy(nope_ldm* net) {
     if (!net) return;
-    for (void* p : net->allocs) hipFree(p);
-    net->x2r.destroy();
+    free_device(net->allocs, &net->x2r);
     delete net;
 }
 
 // NOPE_F16X2 activation ranges of the LDM variant: as nope_unet_x2_poll / _x2_range_check / _x2_enable (include/nope_hip.h)
-int nope_ldm_x2_poll(nope_ldm* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) {
-    if (n_out_of_range) *n_out_of_range = 0;
-    if (n_adjusted) *n_adjusted = 0;
-    if (max_abs) *max_abs = 0.f;
-    if (!net) return NOPE_ERR_ARG;
-    if (!net->x2) return NOPE_OK;
-    return net->x2r.poll((hipStream_t)stream, n_out_of_range, n_adjusted, max_abs);
-}
-int nope_ldm_x2_range_check(nope_ldm* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) {
-    if (!net) return NOPE_ERR_ARG;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NOPE_ERR_LAUNCH;
-    return nope_ldm_x2_poll(net, stream, n_out_of_range, n_adjusted, max_abs);
-}
-int nope_ldm_x2_enable(nope_ldm* net, int on) {
-    if (!net) return NOPE_ERR_ARG;
-    net->x2r.off = on == 0;
-    return NOPE_OK;
-}
+int nope_ldm_x2_poll(nope_ldm* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) { return x2_poll(net, stream, n_out_of_range, n_adjusted, max_abs); }
+int nope_ldm_x2_range_check(nope_ldm* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) { return x2_range_check(net, stream, n_out_of_range, n_adjusted, max_abs); }
+int nope_ldm_x2_enable(nope_ldm* net, int on) { return x2_enable(net, on); }
 
 size_t nope_ldm_workspace_bytes(const nope_ldm* net, int n_hyp, int n_src, int H, int W) {
     if (!net || n_src <= 0 || n_hyp % n_src) return 0;
@@ -474,11 +444,11 @@ int nope_ldm_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, 
     if (e) return e;
     if (!x || !pose || !out || !workspace) return NOPE_ERR_ARG;
     if (out_dtype != NOPE_F32 && out_dtype != NOPE_BF16 && out_dtype != NOPE_F16) return NOPE_ERR_UNSUPPORTED;
-    unsigned char* base = (unsigned char*)(((uintptr_t)workspace + 255) / 256 * 256);
-    const size_t lost = (size_t)(base - (unsigned char*)workspace);
-    if (workspace_bytes < lost) return NOPE_ERR_WORKSPACE;
-    if (net->x2 && net->x2r.active()) (void)net->x2r.poll((hipStream_t)stream, nullptr, nullptr, nullptr);      // verdicts that have arrived: re-centre first
-    return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, workspace_bytes - lost, (hipStream_t)stream, false, nullptr);
+    unsigned char* base;
+    size_t cap;
+    if (!workspace_base(workspace, workspace_bytes, base, cap)) return NOPE_ERR_WORKSPACE;
+    x2_poll_before_forward(net, stream);
+    return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, cap, (hipStream_t)stream, false, nullptr);
 }
 
 }  // extern "C"

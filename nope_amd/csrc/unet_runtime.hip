@@ -16,34 +16,32 @@
 //   * the 19 per-block `Linear(SiLU(c))` embeddings (model_utils.py:261-265,274-275) are one
 //     f32 GEMM against the row-concatenated weights;
 //   * a bump arena over caller-provided workspace: no allocation, no host sync, one stream.
-#include <cstdio>
+//
+// The loader core, the arena, the forward's bookkeeping and the bodies of the entry points are the ones every network runtime uses
+// (runtime_common.h); the conv shape rule (space-to-depth, ConvTranspose2d, cin_scale, which layers take the NOPE_F16X2 pack) and the
+// launch schedule (fused statistics, PreNorm, the tail fusion) are this file's.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
-#include <map>
 #include <mutex>
-#include <string>
-#include <vector>
 
-#include "nope_common.h"
-#include "x2_range.h"
+#include "runtime_common.h"
 
 using namespace nope;
+using rt::NormW;
+using rt::PackedConv;
 
 namespace {
 
-struct Conv { void* w = nullptr; float* bias = nullptr; int Cin = 0, Cout = 0, ntaps = 1, mode = NOPE_CONV_PLAIN; void* w_x2 = nullptr; int x2_id = -1; };   // w_x2: NOPE_F16X2 only: the same weights in the f16 + MX-fp8 tile's layout; x2_id: its slot in the net's range table
-struct Norm { float* gamma = nullptr; float* beta = nullptr; int C = 0; };
-struct Res { Conv c1, c2, res; Norm n1, n2; bool has_res = false; int emb_off = -1; };
+struct Res { PackedConv c1, c2, res; NormW n1, n2; bool has_res = false; int emb_off = -1; };
 // PreNorm's GroupNorm(1) is folded into the qkv conv: gamma into the packed weights, c0 = W beta, c1 = W gamma
 // (f32 [3*heads*dim_head]); mean / rstd enter in the conv epilogue.
-struct LinAttn { Norm pre, post; Conv qkv, out; float *c0 = nullptr, *c1 = nullptr; };
-struct Attn { Norm pre; Conv qkv, out; float *c0 = nullptr, *c1 = nullptr; };
-struct Level { Res r0, r1; LinAttn attn; Conv resample; };
+struct LinAttn { NormW pre, post; PackedConv qkv, out; float *c0 = nullptr, *c1 = nullptr; };
+struct Attn { NormW pre; PackedConv qkv, out; float *c0 = nullptr, *c1 = nullptr; };
+struct Level { Res r0, r1; LinAttn attn; PackedConv resample; };
 
-struct Act { void* p = nullptr; int C = 0, H = 0, W = 0, rep = 1; };
+struct Act : rt::Act { int rep = 1; };      // rep: the tensor holds nhyp / rep samples, each shared by rep hypotheses
 
 }  // namespace
 
@@ -51,15 +49,11 @@ struct Act { void* p = nullptr; int C = 0, H = 0, W = 0, rep = 1; };
 // staged through the workspace so that the caller's pointers stay out of the graph.
 struct UGraph { void* ws; size_t ws_bytes; int n_hyp, n_src, H, W, out_dt; hipGraphExec_t exec; };
 
-struct nope_unet {
+struct nope_unet : rt::Net {      // (dt / sdt / x2 / x2r / allocs: rt::Net, runtime_common.h)
     nope_unet_config cfg;
-    int dt = NOPE_F32;      // compute dtype: what the conv kernels and the weight packing see
-    int sdt = NOPE_F32;     // storage dtype of the activations: what every other kernel sees (NOPE_BF16X3 keeps f32 activations)
-    bool x2 = false;        // NOPE_F16X2: dt = NOPE_BF16X3 everywhere, plus a second weight pack per 3x3 layer for the tap-resident kernel's f16 + MX-fp8 tile
-    std::vector<void*> allocs;
     int dims[9];
     int classes = 0;
-    Conv init_conv, final_conv1;
+    PackedConv init_conv, final_conv1;
     float* final_w_raw = nullptr;      // final_conv.1.weight as stored, [out_dim][u_net_dim] f32: the fused tail (gn_apply_proj, kernels_norm.hip)
     Level downs[8], ups[8];
     Res mid1, mid2, final_res, final_conv0;
@@ -82,90 +76,32 @@ struct nope_unet {
     mutable std::mutex graph_mu;
     mutable int graph_replays = 0;           // forwards served by a graph replay since create (tests assert the path really ran)
     long long graph_max = 0;                 // largest n_hyp * H * W that replays a graph; 0 = off
-    // NOPE_F16X2 activation ranges: per-layer shifts of the tile's operands, producer-side maxima, device-side verdict (x2_range.h)
-    mutable X2Range x2r;
 };
 
 namespace {
 
-struct Loader {
+struct Loader : rt::LoaderCore {
     nope_unet* net;
-    hipStream_t s;
-    std::map<std::string, const nope_tensor_desc*> tab;
-    int err = NOPE_OK;
-    std::string missing;
-
-    const nope_tensor_desc* get(const std::string& name, std::initializer_list<int64_t> shape) {
-        auto it = tab.find(name);
-        if (it == tab.end() || !it->second->data) { fail(name); return nullptr; }
-        const nope_tensor_desc* d = it->second;
-        if (d->ndim != (int)shape.size()) { fail(name); return nullptr; }
-        int i = 0;
-        for (int64_t v : shape) if (d->shape[i++] != v) { fail(name); return nullptr; }
-        return d;
-    }
-    void fail(const std::string& n) { if (err == NOPE_OK) { err = NOPE_ERR_WEIGHT; missing = n; } }
-    // device-to-device copy of a state-dict tensor at create time; a refused copy (bad pointer, wrong device) fails the create call itself,
-    // not just the stream synchronisation that ends it
-    void copy_d2d(void* dst, const void* src, size_t bytes) {
-        if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess && err == NOPE_OK) err = NOPE_ERR_LAUNCH;
-    }
-    void* dmalloc(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err == NOPE_OK) err = NOPE_ERR_ALLOC; return nullptr; }
-        net->allocs.push_back(p);
-        return p;
-    }
-    float* copy_f32(const std::string& name, std::initializer_list<int64_t> shape) {
-        const nope_tensor_desc* d = get(name, shape);
-        if (!d) return nullptr;
-        size_t n = 1;
-        for (int64_t v : shape) n *= (size_t)v;
-        float* p = (float*)dmalloc(n * 4);
-        if (p) copy_d2d(p, d->data, n * 4);
-        return p;
-    }
+    Loader(nope_unet* n, hipStream_t s_, const nope_tensor_desc* tensors, int n_tensors) : LoaderCore(n->allocs, n->dt, s_, tensors, n_tensors, &n->x2r), net(n) {}
     // (ksz 4 with UP2P: the weight is a ConvTranspose2d(4, 2, 1)'s, [Cin][Cout][4][4], repacked into the same four phase sets)
     // (Cin_pad > Cin: the kernel sees Cin_pad input channels, the last ones zero -- a latent whose channel count is not a whole 16-byte
     //  vector, e.g. a 4-channel VAE latent, zero-padded at pack time and in the NHWC input)
-    Conv conv(const std::string& pfx, int Cin, int Cout, int ksz, int mode, bool has_bias, const float* cin_scale = nullptr, int Cin_pad = 0) {
-        Conv c;
+    PackedConv conv(const std::string& pfx, int Cin, int Cout, int ksz, int mode, bool has_bias, const float* cin_scale = nullptr, int Cin_pad = 0) {
         const int Csrc = Cin;
         if (Cin_pad > Cin) Cin = Cin_pad;
-        c.Cin = Cin; c.Cout = Cout; c.mode = mode;
-        c.ntaps = (mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_UP2P) ? 4 : ksz * ksz;
         const bool convT = mode == NOPE_CONV_UP2P && ksz == 4;
         const nope_tensor_desc* d = mode == NOPE_CONV_DOWN2 ? get(pfx + "weight", {Cout, (int64_t)Cin * 4, 1, 1})
                                     : convT             ? get(pfx + "weight", {Cin, Cout, 4, 4})
                                                         : get(pfx + "weight", {Cout, Csrc, ksz, ksz});
-        if (d) {
-            const size_t es = (size_t)dt_es(net->dt);
-            c.w = dmalloc((size_t)Cout * c.ntaps * Cin * es * (mode == NOPE_CONV_UP2P ? 4 : 1));
-            if (c.w) { int e = launch_pack_conv_w(net->dt, d->data, c.w, Cout, Cin, convT ? 16 : c.ntaps, mode, s, cin_scale, nullptr, Csrc); if (e && err == NOPE_OK) err = e; }
-            // NOPE_F16X2: every layer a ping-pong kernel may run (3x3, 1x1, space-to-depth, phase convs) carries the second pack; launch_conv
-            // takes it when the launch's shape lands on one of them
-            if (net->x2 && (mode == NOPE_CONV_PLAIN || mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_UP2P) && (ksz == 3 || ksz == 1 || mode != NOPE_CONV_PLAIN) &&
-                !cin_scale && Csrc == Cin && Cin % 32 == 0) {
-                const size_t x2b = conv_w_x2_bytes(Cout, Cin, c.ntaps, mode);
-                c.w_x2 = dmalloc(x2b);
-                if (c.w_x2) {
-                    int e = launch_pack_conv_w_x2((const float*)d->data, c.w_x2, Cout, Cin, s, convT ? 16 : c.ntaps, mode); if (e && err == NOPE_OK) err = e;
-                    c.x2_id = net->x2r.add_layer(c.w_x2, x2b);
-                }
-            }
-        }
-        if (has_bias) c.bias = copy_f32(pfx + "bias", {Cout});
-        return c;
-    }
-    Norm norm(const std::string& pfx, int C) {
-        Norm n;
-        n.C = C;
-        n.gamma = copy_f32(pfx + "weight", {C});
-        n.beta = copy_f32(pfx + "bias", {C});
-        return n;
+        // NOPE_F16X2: every layer a ping-pong kernel may run (3x3, 1x1, space-to-depth, phase convs) carries the second pack; launch_conv
+        // takes it when the launch's shape lands on one of them
+        const bool second = net->x2 && (mode == NOPE_CONV_PLAIN || mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_UP2P) &&
+                            (ksz == 3 || ksz == 1 || mode != NOPE_CONV_PLAIN) && !cin_scale && Csrc == Cin && Cin % 32 == 0;
+        return pack_conv(d, pfx, Csrc, Cin, Cout, (mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_UP2P) ? 4 : ksz * ksz, mode, has_bias, second,
+                         convT ? 16 : 0, -1, cin_scale);
     }
     // qkv conv of an attention block with its PreNorm folded in (see LinAttn)
-    void prenorm_qkv(const std::string& p, int C, int N, Norm& pre, Conv& qkv, float*& c0, float*& c1) {
+    void prenorm_qkv(const std::string& p, int C, int N, NormW& pre, PackedConv& qkv, float*& c0, float*& c1) {
         pre = norm(p + "fn.norm.", C);
         qkv = conv(p + "fn.fn.to_qkv.", C, N, 1, NOPE_CONV_PLAIN, false, pre.gamma);
         c0 = (float*)dmalloc((size_t)N * 4);
@@ -174,7 +110,7 @@ struct Loader {
         if (w && c0 && c1 && pre.beta && qkv.w) {
             int e = launch_linear_naive(pre.beta, w->data, nullptr, c0, 1, N, C, 0, N, s);
             if (!e) e = launch_rowsum(net->dt, qkv.w, c1, N, C, s);
-            if (e && err == NOPE_OK) err = e;
+            chk(e);
         }
     }
     Res res(const std::string& pfx, int Cin, int Cout, bool use_emb, std::vector<std::pair<std::string, int>>& embs) {
@@ -190,51 +126,22 @@ struct Loader {
     }
 };
 
-struct Arena {
-    unsigned char* base = nullptr;
-    size_t cap = 0, off = 0, peak = 0;
-    bool dry = false;
-    void* alloc(size_t bytes) {
-        const size_t o = align_up(off, 256);
-        off = o + bytes;
-        if (off > peak) peak = off;
-        if (dry) return (void*)(uintptr_t)(0x1000 + o);   // never dereferenced
-        if (off > cap) return nullptr;
-        return base + o;
-    }
-};
-
 // Fused GroupNorm statistics of a conv output: [n][blocks][C][2] column sums per row block (null: the conv cannot emit them --
 // the GroupNorm takes its own statistics pass)
 struct Stats { float* cs = nullptr; int blocks = 0; };
 
-struct Fwd {
-    const nope_unet* net;
-    hipStream_t s;
-    Arena ar;
-    int nhyp = 0, err = NOPE_OK;
-    size_t es = 4;
-    float* gn_partial = nullptr;
+// The shared core's bookkeeping (arena, error state, range tracking); conv / gn are this network's own: two sources, fused statistics,
+// PreNorm, the tail fusion
+struct Fwd : rt::FwdCore<nope_unet> {
+    using Arena = rt::Arena;
     float* pn_partial = nullptr;   // (sum, sum sq) partials of the tensor that feeds the next attention block
     float* pn_ms = nullptr;        // its per-hypothesis (mean, rstd)
     const float* emb_all = nullptr;
 
-    X2Fwd x2;                                    // NOPE_F16X2 range tracking of this forward (x2_range.h)
-    bool tracking() const { return x2.on && err == NOPE_OK; }
-
-    bool dry() const { return ar.dry; }
-    void chk(int e) { if (e != NOPE_OK && err == NOPE_OK) err = e; }
-    void* alloc_act(size_t elems) {
-        void* p = ar.alloc(elems * es);
-        if (!p && err == NOPE_OK) err = NOPE_ERR_WORKSPACE;
-        return p;
-    }
-    bool live() const { return !ar.dry && err == NOPE_OK; }
-
     // out = conv(a [cat b]) (+bias) (+resid);  n = number of samples computed (nhyp or fewer).  `stats`: also emit the column
     // statistics of the output when this launch can (conv_stat_rows: whole 64-row blocks per sample on every kernel, 16 / 32-pixel
     // maps on the small-tile kernel); the scratch comes from the arena and lives until the caller's release.
-    void conv(const Conv& c, const Act& a, const Act* b, void* out, int Ho, int Wo, int n, int rep1, int rep2,
+    void conv(const PackedConv& c, const Act& a, const Act* b, void* out, int Ho, int Wo, int n, int rep1, int rep2,
               const void* resid = nullptr, int out_nchw = 0, int out_dt = NOPE_F32, Stats* stats = nullptr,
               const float* pn_c0 = nullptr, const float* pn_c1 = nullptr, bool track_out = false) {
         if (err != NOPE_OK) return;
@@ -309,8 +216,8 @@ struct Fwd {
     // produced by the conv epilogue and only need folding.
     // proj (with proj_out): GroupNorm + SiLU + residual + this 1x1 conv in one pass (launch_gn_apply_proj: y is not written) when the arguments
     // qualify; returns whether it did -- the caller launches the conv itself otherwise
-    bool gn(const Norm& nm, int G, const void* x, int x_rep, void* y, int HW, int act, int emb_off, const void* resid,
-            int resid_rep, const Stats& st = Stats(), float* out_stats = nullptr, const Conv* proj = nullptr, void* proj_out = nullptr, int proj_out_dt = NOPE_F32) {
+    bool gn(const NormW& nm, int G, const void* x, int x_rep, void* y, int HW, int act, int emb_off, const void* resid,
+            int resid_rep, const Stats& st = Stats(), float* out_stats = nullptr, const PackedConv* proj = nullptr, void* proj_out = nullptr, int proj_out_dt = NOPE_F32) {
         if (!live()) return false;
         const int nx = nhyp / x_rep;
         int nch = 1;
@@ -351,7 +258,7 @@ struct Fwd {
     // `next_is_attention`: also emit the GroupNorm(1) partials of the block's output into pn_partial.
     // proj / proj_out: the 1x1 conv that is the ONLY reader of the block's output (the U-Net's tail), fused into the block's last pass where gn() can;
     // returns whether it was (then `out` holds the un-normalised conv output and must not be read)
-    bool resnet(const Res& R, const Act& a, const Act* b, bool use_emb, void* out, bool next_is_attention = false, const Conv* proj = nullptr,
+    bool resnet(const Res& R, const Act& a, const Act* b, bool use_emb, void* out, bool next_is_attention = false, const PackedConv* proj = nullptr,
                 void* proj_out = nullptr, int proj_out_dt = NOPE_F32) {
         const int HW = a.H * a.W, G = net->cfg.groups;
         const size_t M = (size_t)nhyp * HW;
@@ -387,7 +294,7 @@ struct Fwd {
 
     // PreNorm folded into the qkv conv: finalize (mean, rstd) of x from the producer's partials, then
     // qkv = rstd * ((W gamma) x - mean * c1) + c0 in the conv epilogue -- x is read once, never re-written.
-    void qkv_prenorm(const Conv& qkvw, const float* c0, const float* c1, const Act& x, void* qkv) {
+    void qkv_prenorm(const PackedConv& qkvw, const float* c0, const float* c1, const Act& x, void* qkv) {
         if (!live()) return;
         const int HW = x.H * x.W;
         chk(launch_gn_finalize(pn_partial, pn_ms, nhyp, gn_apply_blocks(HW, x.C, net->sdt, nhyp), (float)HW * (float)x.C, 1e-5f, s));
@@ -432,9 +339,7 @@ int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, cons
     const nope_unet_config& cfg = net->cfg;
     const int L = cfg.n_levels;
     Fwd f;
-    f.net = net; f.s = s; f.nhyp = n_hyp; f.es = (size_t)dt_es(net->dt);
-    f.ar.base = (unsigned char*)ws; f.ar.cap = ws_bytes; f.ar.dry = dry;
-    f.x2.r = &net->x2r; f.x2.s = s; f.x2.on = net->x2 && net->x2r.active() && !dry;
+    f.begin(net, n_hyp, ws, ws_bytes, s, dry);
     const int HW = H * W;
     const int* dims = net->dims;
 
@@ -595,10 +500,7 @@ int nope_unet_create(const nope_unet_config* cfg, const nope_tensor_desc* tensor
     const int* dims = net->dims;
     const int HD = cfg->heads * cfg->dim_head;
 
-    Loader ld;
-    ld.net = net; ld.s = s;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name) ld.tab[tensors[i].name] = &tensors[i];
+    Loader ld(net, s, tensors, n_tensors);
     std::vector<std::pair<std::string, int>> embs;
 
     if (cfg->pose_mlp_layers >= 1) {
@@ -661,15 +563,8 @@ int nope_unet_create(const nope_unet_config* cfg, const nope_tensor_desc* tensor
         }
         off += e.second;
     }
-    if (ld.err == NOPE_OK) { const int e = net->x2r.init([&](size_t bytes) { return ld.dmalloc(bytes); }, s); if (e) ld.err = e; }
-    if (ld.err == NOPE_OK && hipStreamSynchronize(s) != hipSuccess) ld.err = NOPE_ERR_LAUNCH;
-    if (ld.err != NOPE_OK) {
-        if (!ld.missing.empty()) fprintf(stderr, "nope_unet_create: missing or mis-shaped tensor '%s'\n", ld.missing.c_str());
-        nope_unet_destroy(net);
-        return ld.err;
-    }
-    *out = net;
-    return NOPE_OK;
+    ld.init_x2();
+    return rt::finish_create(ld, "nope_unet_create", net, nope_unet_destroy, out);
 }
 
 int nope_unet_profile(nope_unet* net, int enable) {
@@ -710,31 +605,10 @@ int nope_unet_profile_launches(nope_unet* net, nope_conv_launch_info* out, int m
     return NOPE_OK;
 }
 
-// ---- NOPE_F16X2 activation ranges ---------------------------------------------------------------------------------------------------------
-// The f16 + MX-fp8 tile forms its A operands from a' = a * 2^-t (t per layer, nope_common.h: kX2*): f16(a') (saturates at 65504),
-// e4m3(a'_lo * 2^9) and e4m3(a' * 2^-2) (saturates at |a'| = 1792, below 2^-4 it runs out of significant bits).  A launch whose LARGEST |a'|
-// lies above 1792 or below 2^-4 computed its cross terms from saturated / subnormal operands: plain-f16 accuracy instead of ~2^-15 per
-// product.  Every forward is judged on the device (x2_verdict_kernel) and an out-of-range forward's output is NaN.  The poll reads the verdicts
-// that have arrived in mapped host memory since the previous poll -- no synchronisation -- and re-centres t where a layer was out of, or within
-// a binade or two of the end of, its window (max |a'| in [256, 512): three binades of headroom, full accuracy down to 2^-13 of the maximum);
-// the new shifts travel on `stream`, ordered before whatever is enqueued on it next.
-int nope_unet_x2_poll(nope_unet* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) {
-    if (n_out_of_range) *n_out_of_range = 0;
-    if (n_adjusted) *n_adjusted = 0;
-    if (max_abs) *max_abs = 0.f;
-    if (!net) return NOPE_ERR_ARG;
-    if (!net->x2) return NOPE_OK;
-    // (a cached hipGraph replays the same kernels and pointers; the shifts live in device memory: nothing to rebuild)
-    return net->x2r.poll((hipStream_t)stream, n_out_of_range, n_adjusted, max_abs);
-}
-
-// ... behind a synchronisation of `stream`: the verdicts of every forward issued on it so far.  NOPE_ERR_RANGE: at least one of them was out of
-// range (its output is NaN); the shifts are re-centred -- issue it again.
-int nope_unet_x2_range_check(nope_unet* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) {
-    if (!net) return NOPE_ERR_ARG;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return NOPE_ERR_LAUNCH;
-    return nope_unet_x2_poll(net, stream, n_out_of_range, n_adjusted, max_abs);
-}
+// ---- NOPE_F16X2 activation ranges: the poll / range check / switch every tracked network shares (runtime_common.h, x2_range.h) -------------------
+// (a cached hipGraph replays the same kernels and pointers; the shifts live in device memory: a poll leaves nothing to rebuild)
+int nope_unet_x2_poll(nope_unet* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) { return rt::x2_poll(net, stream, n_out_of_range, n_adjusted, max_abs); }
+int nope_unet_x2_range_check(nope_unet* net, nope_stream_t stream, int* n_out_of_range, int* n_adjusted, float* max_abs) { return rt::x2_range_check(net, stream, n_out_of_range, n_adjusted, max_abs); }
 
 int nope_unet_x2_enable(nope_unet* net, int on) {
     if (!net) return NOPE_ERR_ARG;
@@ -743,8 +617,7 @@ int nope_unet_x2_enable(nope_unet* net, int on) {
         for (const UGraph& g : net->graphs) hipGraphExecDestroy(g.exec);
         net->graphs.clear();
     }
-    net->x2r.off = on == 0;
-    return NOPE_OK;
+    return rt::x2_enable(net, on);
 }
 
 int nope_unet_x2_shifts(const nope_unet* net, int* shifts, int max, int* n) {
@@ -769,8 +642,7 @@ void nope_unet_destroy(nope_unet* net) {
     if (!net) return;
     for (const UGraph& g : net->graphs) hipGraphExecDestroy(g.exec);
     for (auto& e : net->evs) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
-    for (void* p : net->allocs) hipFree(p);
-    net->x2r.destroy();
+    rt::free_device(net->allocs, &net->x2r);
     delete net;
 }
 
@@ -805,19 +677,18 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
     if (e) return e;
     if (!x || !pose || !out || !workspace) return NOPE_ERR_ARG;
     if (out_dtype != NOPE_F32 && out_dtype != NOPE_BF16 && out_dtype != NOPE_F16) return NOPE_ERR_UNSUPPORTED;
-    unsigned char* base = (unsigned char*)(((uintptr_t)workspace + 255) / 256 * 256);
-    const size_t lost = (size_t)(base - (unsigned char*)workspace);
-    if (workspace_bytes < lost) return NOPE_ERR_WORKSPACE;
+    unsigned char* base;
+    size_t avail;
+    if (!rt::workspace_base(workspace, workspace_bytes, base, avail)) return NOPE_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     size_t xb, pb, ob;
     const size_t sb = unet_stage_bytes(net, n_hyp, n_src, H, W, xb, pb, ob);
-    const size_t avail = workspace_bytes - lost;
     // Opt-in (net->graph_max > 0): batches of at most that many hypothesis-pixels replay a captured launch sequence; everything else
     // launches directly.
     // (NOPE_F16X2 with range tracking launches directly: the per-forward table of the verdict kernel is a host-to-device copy)
     const bool want_graph = net->graph_max > 0 && net->graphs_ok && !net->profile && avail > sb && (long long)n_hyp * H * W <= net->graph_max &&
                             !(net->x2 && net->x2r.active());
-    if (net->x2 && net->x2r.active()) (void)net->x2r.poll((hipStream_t)stream, nullptr, nullptr, nullptr);      // verdicts that have arrived: re-centre first
+    rt::x2_poll_before_forward(net, stream);
     if (!want_graph)
         return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr);
     std::lock_guard<std::mutex> lock(net->graph_mu);

@@ -14,119 +14,60 @@
 //     half of the moments), with 0.18215 folded into them; decode: 1 / 0.18215 folded into post_quant_conv's weights;
 //   * decode with unnormalize: (x + 1) / 2 folded into a second pack of conv_out (weights / 2, bias / 2 + 1 / 2);
 //   * latent and image channel counts are zero-padded to a multiple of 8 in the NHWC tensors (16-byte vectors of the 16-bit modes).
-#include <cstdio>
-#include <map>
-#include <string>
-#include <vector>
-
-#include "nope_common.h"
+//
+// Loader core, arena, the conv / GroupNorm launches and the entry-point bodies are the shared ones (runtime_common.h); this file keeps its
+// ResnetBlock / AttnBlock / mid block, the two-slot ping-pong, and one chunk loop under nope_vae_encode / nope_vae_decode.
+#include "runtime_common.h"
 
 using namespace nope;
+using namespace nope::rt;
 
 namespace {
 
 constexpr float kScale = 0.18215f;      // AutoencoderKL.py:34,45
 
-struct VConv { void* w = nullptr; float* bias = nullptr; int Cin = 0, Cout = 0, ntaps = 1, mode = NOPE_CONV_PLAIN; };
-struct VNorm { float* gamma = nullptr; float* beta = nullptr; int C = 0; };
-struct VRes { VNorm n1, n2; VConv c1, c2, sc; bool has_sc = false; int Cin = 0, Cout = 0; };
-struct VAttn { VNorm norm; VConv qkv, proj; int C = 0; };
-struct VLevel { std::vector<VRes> res; bool has_resample = false; VConv resample; };
+struct VRes { NormW n1, n2; PackedConv c1, c2, sc; bool has_sc = false; int Cin = 0, Cout = 0; };
+struct VAttn { NormW norm; PackedConv qkv, proj; int C = 0; };
+struct VLevel { std::vector<VRes> res; bool has_resample = false; PackedConv resample; };
 
 int pad8(int c) { return (c + 7) / 8 * 8; }
 
 }  // namespace
 
-struct nope_vae {
+struct nope_vae : Net {      // (dt / sdt / allocs: rt::Net; NOPE_F16X2 runs as NOPE_BF16X3: x2 stays false, no layer takes a second pack)
     nope_vae_config cfg;
-    int dt = NOPE_F32;      // compute dtype (conv kernels, weight packing); NOPE_F16X2 runs as NOPE_BF16X3
-    int sdt = NOPE_F32;     // storage dtype of the activations
     float eps = 1e-6f;
     int cin_p = 8, zp = 8, mp = 8;      // padded channel counts: image in, latent, encoder moments (2 z)
-    std::vector<void*> allocs;
     // encoder
-    VConv e_conv_in, e_conv_out, quant;
+    PackedConv e_conv_in, e_conv_out, quant;
     std::vector<VLevel> e_down;
     VRes e_mid1, e_mid2;
     VAttn e_attn;
-    VNorm e_norm_out;
+    NormW e_norm_out;
     // decoder
-    VConv post_quant, d_conv_in, d_conv_out, d_conv_out_un;
+    PackedConv post_quant, d_conv_in, d_conv_out, d_conv_out_un;
     std::vector<VLevel> d_up;
     VRes d_mid1, d_mid2;
     VAttn d_attn;
-    VNorm d_norm_out;
+    NormW d_norm_out;
 };
 
 namespace {
 
-struct Loader {
+struct Loader : LoaderCore {
     nope_vae* net;
-    hipStream_t s;
-    std::map<std::string, const nope_tensor_desc*> tab;
-    int err = NOPE_OK;
-    std::string missing;
-    std::vector<void*> temps;
-    void fail(const std::string& n) { if (err == NOPE_OK) { err = NOPE_ERR_WEIGHT; missing = n; } }
-    void chk(int e) { if (e && err == NOPE_OK) err = e; }
-    const nope_tensor_desc* get(const std::string& name, std::initializer_list<int64_t> shape) {
-        auto it = tab.find(name);
-        if (it == tab.end() || !it->second->data || it->second->ndim != (int)shape.size()) { fail(name); return nullptr; }
-        int i = 0;
-        for (int64_t v : shape) if (it->second->shape[i++] != v) { fail(name); return nullptr; }
-        return it->second;
-    }
-    void* dmalloc(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err == NOPE_OK) err = NOPE_ERR_ALLOC; return nullptr; }
-        net->allocs.push_back(p);
-        return p;
-    }
-    void* tmalloc(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err == NOPE_OK) err = NOPE_ERR_ALLOC; return nullptr; }
-        temps.push_back(p);
-        return p;
-    }
-    void free_temps() { for (void* p : temps) hipFree(p); temps.clear(); }
-    void copy_d2d(void* dst, const void* src, size_t bytes) {
-        if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess && err == NOPE_OK) err = NOPE_ERR_LAUNCH;
-    }
-    float* copy_f32(const std::string& name, std::initializer_list<int64_t> shape) {
-        const nope_tensor_desc* d = get(name, shape);
-        if (!d) return nullptr;
-        size_t n = 1;
-        for (int64_t v : shape) n *= (size_t)v;
-        float* p = (float*)dmalloc(n * 4);
-        if (p) copy_d2d(p, d->data, n * 4);
-        return p;
-    }
-    VNorm norm(const std::string& pfx, int C) {
-        VNorm n;
-        n.C = C;
-        n.gamma = copy_f32(pfx + "weight", {C});
-        n.beta = copy_f32(pfx + "bias", {C});
-        return n;
-    }
+    Loader(nope_vae* n, hipStream_t s_, const nope_tensor_desc* tensors, int n_tensors) : LoaderCore(n->allocs, n->dt, s_, tensors, n_tensors), net(n) {}
     // conv with bias, packed for the implicit-GEMM kernels; Cin_pad > Cin: zero weights for the padded input channels
-    VConv conv(const std::string& pfx, int Cin, int Cout, int ksz, int mode, int Cin_pad = 0) {
-        VConv c;
-        const int Ck = Cin_pad > Cin ? Cin_pad : Cin;
-        c.Cin = Ck; c.Cout = Cout; c.mode = mode;
-        c.ntaps = mode == NOPE_CONV_UP2P ? 4 : ksz * ksz;
+    // (NOPE_CONV_STRIDE2_PAD01 differs from NOPE_CONV_STRIDE2 in the launch geometry only: the weights are packed as the latter's)
+    PackedConv conv(const std::string& pfx, int Cin, int Cout, int ksz, int mode, int Cin_pad = 0) {
         const nope_tensor_desc* d = get(pfx + "weight", {Cout, Cin, ksz, ksz});
-        if (d) {
-            c.w = dmalloc((size_t)Cout * c.ntaps * Ck * dt_es(net->dt) * (mode == NOPE_CONV_UP2P ? 4 : 1));
-            if (c.w) chk(launch_pack_conv_w(net->dt, (const float*)d->data, c.w, Cout, Ck, c.ntaps, mode == NOPE_CONV_STRIDE2_PAD01 ? NOPE_CONV_STRIDE2 : mode, s,
-                                            nullptr, nullptr, Cin));
-        }
-        c.bias = copy_f32(pfx + "bias", {Cout});
-        return c;
+        return pack_conv(d, pfx, Cin, Cin_pad > Cin ? Cin_pad : Cin, Cout, mode == NOPE_CONV_UP2P ? 4 : ksz * ksz, mode, true, false, 0,
+                         mode == NOPE_CONV_STRIDE2_PAD01 ? NOPE_CONV_STRIDE2 : mode);
     }
     // the small convs at the latent end, rewritten on the host at create time: rows [0, rows) of the stored conv, scaled (w * ws, b * bs + ba),
     // zero rows up to Cout_pad and zero input channels up to Cin_pad
-    VConv conv_host(const std::string& pfx, int Cin, int Cout, int ksz, int rows, int Cin_pad, int Cout_pad, float ws, float bs, float ba) {
-        VConv c;
+    PackedConv conv_host(const std::string& pfx, int Cin, int Cout, int ksz, int rows, int Cin_pad, int Cout_pad, float ws, float bs, float ba) {
+        PackedConv c;
         c.Cin = Cin_pad; c.Cout = Cout_pad; c.mode = NOPE_CONV_PLAIN; c.ntaps = ksz * ksz;
         const nope_tensor_desc* d = get(pfx + "weight", {Cout, Cin, ksz, ksz});
         const nope_tensor_desc* bd = get(pfx + "bias", {Cout});
@@ -198,61 +139,15 @@ struct Loader {
     }
 };
 
-struct Arena {
-    unsigned char* base = nullptr;
-    size_t cap = 0, off = 0, peak = 0;
-    bool dry = false;
-    void* alloc(size_t bytes) {
-        const size_t o = align_up(off, 256);
-        off = o + bytes;
-        if (off > peak) peak = off;
-        if (dry) return (void*)(uintptr_t)(0x1000 + o);
-        if (off > cap) return nullptr;
-        return base + o;
-    }
-};
-
-struct Act { void* p = nullptr; int C = 0, H = 0, W = 0; };
-
-struct Fwd {
-    const nope_vae* net;
-    hipStream_t s;
-    Arena ar;
-    int n = 0, err = NOPE_OK;
-    size_t es = 4;
-    float* gn_partial = nullptr;
-
-    void chk(int e) { if (e != NOPE_OK && err == NOPE_OK) err = e; }
-    bool live() const { return !ar.dry && err == NOPE_OK; }
-    Act act(int C, int H, int W) {
-        Act a{ar.alloc((size_t)n * H * W * C * es), C, H, W};
-        if (!a.p && err == NOPE_OK) err = NOPE_ERR_WORKSPACE;
-        return a;
-    }
+struct Fwd : FwdCore<nope_vae> {
+    Act act(int C, int H, int W) { return Act{alloc_act((size_t)nhyp * H * W * C), C, H, W}; }
     // conv of `a` into `out` (NHWC of the storage type, or NCHW f32 with out_nchw); output size from the geometry
-    void conv(const VConv& c, const Act& a, void* out, const void* resid = nullptr, int out_nchw = 0) {
-        if (!live()) return;
-        if (a.C != c.Cin) { chk(NOPE_ERR_ARG); return; }
-        ConvArgs ca;
-        ca.src1 = a.p; ca.C1 = a.C; ca.Hs = a.H; ca.Ws = a.W;
-        ca.Ho = c.mode == NOPE_CONV_UP2P ? 2 * a.H : c.mode == NOPE_CONV_STRIDE2_PAD01 ? a.H / 2 : a.H;
-        ca.Wo = c.mode == NOPE_CONV_UP2P ? 2 * a.W : c.mode == NOPE_CONV_STRIDE2_PAD01 ? a.W / 2 : a.W;
-        ca.mode = c.mode; ca.ntaps = c.ntaps; ca.w = c.w; ca.bias = c.bias; ca.resid = resid; ca.out = out; ca.Cout = c.Cout;
-        ca.nhyp = n; ca.out_nchw = out_nchw; ca.out_dt = NOPE_F32;
-        chk(launch_conv(net->dt, ca, s));
+    void conv(const PackedConv& c, const Act& a, void* out, const void* resid = nullptr, int out_nchw = 0) {
+        const int up = c.mode == NOPE_CONV_UP2P, down = c.mode == NOPE_CONV_STRIDE2_PAD01;
+        FwdCore::conv(c, a, out, up ? 2 * a.H : down ? a.H / 2 : a.H, up ? 2 * a.W : down ? a.W / 2 : a.W, resid, out_nchw);
     }
-    // y = [silu](GroupNorm(G, eps)(x))
-    void gn(const VNorm& nm, const Act& x, void* y, int act) {
-        if (!live()) return;
-        const int HW = x.H * x.W, G = net->cfg.norm_num_groups;
-        const int nch = gn_stats_chunks(HW, nm.C, net->sdt);
-        chk(launch_gn_stats(net->sdt, x.p, gn_partial, n, HW, nm.C, G, nch, s));
-        GnApplyArgs ga;
-        ga.x = x.p; ga.y = y; ga.partial = gn_partial; ga.nchunk = nch; ga.gamma = nm.gamma; ga.beta = nm.beta;
-        ga.nhyp = n; ga.HW = HW; ga.C = nm.C; ga.G = G; ga.act = act; ga.eps = net->eps;
-        ga.fast_silu = net->dt != NOPE_F32 ? 1 : 0;      // (as the LDM runtime: the f32 mode keeps expf and the division)
-        chk(launch_gn_apply(net->sdt, ga, s));
-    }
+    // y = [silu](GroupNorm(norm_num_groups, eps)(x))
+    void gn(const NormW& nm, const Act& x, void* y, int act) { FwdCore::gn(nm, net->cfg.norm_num_groups, x.p, y, x.H * x.W, act, net->eps); }
     // ResnetBlock: out = shortcut(x) + conv2(silu(norm2(conv1(silu(norm1(x))))))
     void res(const VRes& R, const Act& x, void* out) {
         const size_t mark = ar.off;
@@ -276,17 +171,14 @@ struct Fwd {
         Act t = act(C, x.H, x.W), qkv = act(3 * C, x.H, x.W), o = act(C, x.H, x.W);
         gn(A.norm, x, t.p, 0);
         conv(A.qkv, t, qkv.p);
-        if (live()) chk(C <= 128 ? launch_token_attention(net->dt, qkv.p, o.p, n, HW, C, C, s) : launch_wide_attention(net->dt, qkv.p, o.p, n, HW, C, s));
+        if (live()) chk(C <= 128 ? launch_token_attention(net->dt, qkv.p, o.p, nhyp, HW, C, C, s) : launch_wide_attention(net->dt, qkv.p, o.p, nhyp, HW, C, s));
         conv(A.proj, o, out, x.p);
         ar.off = mark;
     }
     // the network's activations alternate between two slots sized for the largest one (block temporaries sit above them): out = other(in)
     void* slot[2] = {nullptr, nullptr};
     void alloc_slots(size_t elems_per_sample) {
-        for (int i = 0; i < 2; ++i) {
-            slot[i] = ar.alloc((size_t)n * elems_per_sample * es);
-            if (!slot[i] && err == NOPE_OK) err = NOPE_ERR_WORKSPACE;
-        }
+        for (int i = 0; i < 2; ++i) slot[i] = alloc_act((size_t)nhyp * elems_per_sample);
     }
     void* other(const Act& a) const { return a.p == slot[0] ? slot[1] : slot[0]; }
     Act res_next(const VRes& R, const Act& x) { Act o{other(x), R.Cout, x.H, x.W}; res(R, x, o.p); return o; }
@@ -296,23 +188,35 @@ struct Fwd {
         attn(a, b, c.p);
         return res_next(r2, c);
     }
+    // Set-up of an encode / decode pass over n samples whose full-resolution side is H x W: the arena, the GroupNorm partials and the two
+    // slots.  A level's blocks run at its own width or (its first block's input) its predecessor's: the finer level's in the encoder, the
+    // coarser one's in the decoder.  in_elems: the padded network input per sample.  false: the workspace does not hold even that.
+    bool start(const nope_vae* vae, int decode, int n, int H, int W, size_t in_elems, void* ws, size_t ws_bytes, hipStream_t s_, bool dry) {
+        begin(vae, n, ws, ws_bytes, s_, dry);
+        gn_partial = (float*)ar.alloc((size_t)n * 16 * 64 * 2 * 4);
+        if (!gn_partial) return false;
+        const int* boc = net->cfg.block_out_channels;
+        const int L = net->cfg.n_levels;
+        size_t big = in_elems;                              // largest activation per sample
+        for (int l = 0; l < L; ++l) {
+            const int nb = decode ? (l + 1 < L ? l + 1 : l) : (l ? l - 1 : 0);
+            const size_t e = (size_t)(boc[nb] > boc[l] ? boc[nb] : boc[l]) * (H >> l) * (W >> l);
+            if (e > big) big = e;
+        }
+        alloc_slots(big);
+        return true;
+    }
+    int finish(size_t* peak) const {
+        if (peak) *peak = ar.peak;
+        return err;
+    }
 };
 
 int run_encode(const nope_vae* net, const float* image, int n, int H, int W, float* latent, void* ws, size_t ws_bytes, hipStream_t s, bool dry,
                size_t* peak) {
     const nope_vae_config& cfg = net->cfg;
     Fwd f;
-    f.net = net; f.s = s; f.n = n; f.es = (size_t)dt_es(net->dt);
-    f.ar.base = (unsigned char*)ws; f.ar.cap = ws_bytes; f.ar.dry = dry;
-    f.gn_partial = (float*)f.ar.alloc((size_t)n * 16 * 64 * 2 * 4);
-    if (!f.gn_partial) return NOPE_ERR_WORKSPACE;
-    size_t big = (size_t)net->cin_p * H * W;            // largest activation per sample
-    for (int l = 0, prev = cfg.block_out_channels[0]; l < cfg.n_levels; prev = cfg.block_out_channels[l++]) {
-        const int c = prev > cfg.block_out_channels[l] ? prev : cfg.block_out_channels[l];
-        const size_t e = (size_t)c * (H >> l) * (W >> l);
-        if (e > big) big = e;
-    }
-    f.alloc_slots(big);
+    if (!f.start(net, 0, n, H, W, (size_t)net->cin_p * H * W, ws, ws_bytes, s, dry)) return NOPE_ERR_WORKSPACE;
     Act x{f.slot[0], net->cin_p, H, W};
     if (f.live()) f.chk(launch_nchw_to_nhwc(net->sdt, image, x.p, n, net->cin_p, H * W, s, cfg.in_channels));
     Act h{f.other(x), net->e_conv_in.Cout, H, W};
@@ -331,26 +235,15 @@ int run_encode(const nope_vae* net, const float* image, int n, int H, int W, flo
     Act m = f.act(net->mp, h.H, h.W);
     f.conv(net->e_conv_out, t, m.p);
     f.conv(net->quant, m, latent, nullptr, 1);          // first latent_channels moments x 0.18215, NCHW f32
-    if (peak) *peak = f.ar.peak;
-    return f.err;
+    return f.finish(peak);
 }
 
 int run_decode(const nope_vae* net, const float* latent, int n, int h, int w, float* image, int unnorm, void* ws, size_t ws_bytes, hipStream_t s,
                bool dry, size_t* peak) {
     const nope_vae_config& cfg = net->cfg;
     Fwd f;
-    f.net = net; f.s = s; f.n = n; f.es = (size_t)dt_es(net->dt);
-    f.ar.base = (unsigned char*)ws; f.ar.cap = ws_bytes; f.ar.dry = dry;
-    f.gn_partial = (float*)f.ar.alloc((size_t)n * 16 * 64 * 2 * 4);
-    if (!f.gn_partial) return NOPE_ERR_WORKSPACE;
-    const int L = cfg.n_levels;
-    size_t big = (size_t)net->zp * h * w;               // largest activation per sample
-    for (int i = 0, prev = cfg.block_out_channels[L - 1]; i < L; prev = cfg.block_out_channels[L - 1 - i++]) {
-        const int c = prev > cfg.block_out_channels[L - 1 - i] ? prev : cfg.block_out_channels[L - 1 - i];
-        const size_t e = (size_t)c * (h << i) * (w << i);
-        if (e > big) big = e;
-    }
-    f.alloc_slots(big);
+    const int up = cfg.n_levels - 1;
+    if (!f.start(net, 1, n, h << up, w << up, (size_t)net->zp * h * w, ws, ws_bytes, s, dry)) return NOPE_ERR_WORKSPACE;
     Act z{f.slot[0], net->zp, h, w};
     if (f.live()) f.chk(launch_nchw_to_nhwc(net->sdt, latent, z.p, n, net->zp, h * w, s, cfg.latent_channels));
     Act zq{f.other(z), net->zp, h, w};
@@ -369,16 +262,18 @@ int run_decode(const nope_vae* net, const float* latent, int n, int h, int w, fl
     Act t = f.act(x.C, x.H, x.W);
     f.gn(net->d_norm_out, x, t.p, 1);
     f.conv(unnorm ? net->d_conv_out_un : net->d_conv_out, t, image, nullptr, 1);
-    if (peak) *peak = f.ar.peak;
-    return f.err;
+    return f.finish(peak);
+}
+
+int run(const nope_vae* net, int decode, const float* in, int n, int H, int W, float* out, int unnorm, void* ws, size_t ws_bytes, hipStream_t s, bool dry,
+        size_t* peak) {
+    return decode ? run_decode(net, in, n, H, W, out, unnorm, ws, ws_bytes, s, dry, peak) : run_encode(net, in, n, H, W, out, ws, ws_bytes, s, dry, peak);
 }
 
 // arena bytes a chunk of n samples uses (0: unsupported); the caller's workspace adds up to 255 bytes of base alignment (nope_vae_workspace_bytes)
 size_t peak_bytes(const nope_vae* net, int decode, int n, int H, int W) {
     size_t peak = 0;
-    const int e = decode ? run_decode(net, nullptr, n, H, W, nullptr, 0, nullptr, 0, nullptr, true, &peak)
-                         : run_encode(net, nullptr, n, H, W, nullptr, nullptr, 0, nullptr, true, &peak);
-    return e ? 0 : peak;
+    return run(net, decode, nullptr, n, H, W, nullptr, 0, nullptr, 0, nullptr, true, &peak) ? 0 : peak;
 }
 
 int check_size(const nope_vae* net, int decode, int n, int H, int W) {
@@ -402,6 +297,29 @@ int chunk_for(const nope_vae* net, int decode, int n, int H, int W, size_t bytes
         else hi = mid - 1;
     }
     return lo;
+}
+
+// nope_vae_encode / nope_vae_decode: the batch in the largest chunks the workspace holds.  H x W: the input's size (image or latent)
+int run_chunks(const nope_vae* vae, int decode, const float* in, int n_img, int H, int W, float* out, int unnorm, void* workspace, size_t workspace_bytes,
+               nope_stream_t stream) {
+    int e = check_size(vae, decode, n_img, H, W);
+    if (e) return e;
+    if (!in || !out || !workspace) return NOPE_ERR_ARG;
+    unsigned char* base;
+    size_t cap;
+    if (!workspace_base(workspace, workspace_bytes, base, cap)) return NOPE_ERR_WORKSPACE;
+    const int chunk = chunk_for(vae, decode, n_img, H, W, cap);
+    if (chunk < 1) return NOPE_ERR_WORKSPACE;
+    const int f = 1 << (vae->cfg.n_levels - 1);
+    const size_t img_px = decode ? (size_t)(H * f) * (W * f) : (size_t)H * W, lat_px = decode ? (size_t)H * W : (size_t)(H / f) * (W / f);
+    const size_t in_per = decode ? vae->cfg.latent_channels * lat_px : vae->cfg.in_channels * img_px;
+    const size_t out_per = decode ? vae->cfg.out_channels * img_px : vae->cfg.latent_channels * lat_px;
+    for (int i0 = 0; i0 < n_img; i0 += chunk) {
+        const int c = n_img - i0 < chunk ? n_img - i0 : chunk;
+        e = run(vae, decode, in + (size_t)i0 * in_per, c, H, W, out + (size_t)i0 * out_per, unnorm, base, cap, (hipStream_t)stream, false, nullptr);
+        if (e) return e;
+    }
+    return NOPE_OK;
 }
 
 }  // namespace
@@ -432,10 +350,7 @@ int nope_vae_create(const nope_vae_config* cfg, const nope_tensor_desc* tensors,
     net->mp = pad8(2 * z);
     const int* boc = cfg->block_out_channels;
     const int lpb = cfg->layers_per_block;
-    Loader ld;
-    ld.net = net; ld.s = s;
-    for (int i = 0; i < n_tensors; ++i)
-        if (tensors[i].name) ld.tab[tensors[i].name] = &tensors[i];
+    Loader ld(net, s, tensors, n_tensors);
 
     // encoder: conv_in, down blocks (resnets + Downsample but on the last level), mid block, norm + SiLU + conv_out, quant_conv
     net->e_conv_in = ld.conv("encoder.conv_in.", cfg->in_channels, boc[0], 3, NOPE_CONV_PLAIN, net->cin_p);
@@ -478,20 +393,12 @@ int nope_vae_create(const nope_vae_config* cfg, const nope_tensor_desc* tensors,
     net->d_conv_out = ld.conv_host("decoder.conv_out.", ch, cfg->out_channels, 3, cfg->out_channels, ch, cfg->out_channels, 1.f, 1.f, 0.f);
     net->d_conv_out_un = ld.conv_host("decoder.conv_out.", ch, cfg->out_channels, 3, cfg->out_channels, ch, cfg->out_channels, 0.5f, 0.5f, 0.5f);
 
-    if (hipStreamSynchronize(s) != hipSuccess && ld.err == NOPE_OK) ld.err = NOPE_ERR_LAUNCH;
-    ld.free_temps();
-    if (ld.err != NOPE_OK) {
-        if (!ld.missing.empty()) fprintf(stderr, "nope_vae_create: missing or mis-shaped tensor '%s'\n", ld.missing.c_str());
-        nope_vae_destroy(net);
-        return ld.err;
-    }
-    *out = net;
-    return NOPE_OK;
+    return finish_create(ld, "nope_vae_create", net, nope_vae_destroy, out);
 }
 
 void nope_vae_destroy(nope_vae* vae) {
     if (!vae) return;
-    for (void* p : vae->allocs) hipFree(p);
+    free_device(vae->allocs);
     delete vae;
 }
 
@@ -503,45 +410,12 @@ size_t nope_vae_workspace_bytes(const nope_vae* vae, int decode, int n_img, int 
 
 int nope_vae_encode(const nope_vae* vae, const float* image, int n_img, int H, int W, float* latent, void* workspace, size_t workspace_bytes,
                     nope_stream_t stream) {
-    int e = check_size(vae, 0, n_img, H, W);
-    if (e) return e;
-    if (!image || !latent || !workspace) return NOPE_ERR_ARG;
-    unsigned char* base = (unsigned char*)(((uintptr_t)workspace + 255) / 256 * 256);
-    const size_t lost = (size_t)(base - (unsigned char*)workspace);
-    if (workspace_bytes < lost) return NOPE_ERR_WORKSPACE;
-    const size_t cap = workspace_bytes - lost;
-    const int chunk = chunk_for(vae, 0, n_img, H, W, cap);
-    if (chunk < 1) return NOPE_ERR_WORKSPACE;
-    const int f = 1 << (vae->cfg.n_levels - 1);
-    const size_t in_per = (size_t)vae->cfg.in_channels * H * W, out_per = (size_t)vae->cfg.latent_channels * (H / f) * (W / f);
-    for (int i0 = 0; i0 < n_img; i0 += chunk) {
-        const int c = n_img - i0 < chunk ? n_img - i0 : chunk;
-        e = run_encode(vae, image + (size_t)i0 * in_per, c, H, W, latent + (size_t)i0 * out_per, base, cap, (hipStream_t)stream, false, nullptr);
-        if (e) return e;
-    }
-    return NOPE_OK;
+    return run_chunks(vae, 0, image, n_img, H, W, latent, 0, workspace, workspace_bytes, stream);
 }
 
 int nope_vae_decode(const nope_vae* vae, const float* latent, int n_img, int h, int w, float* image, int unnormalize, void* workspace,
                     size_t workspace_bytes, nope_stream_t stream) {
-    int e = check_size(vae, 1, n_img, h, w);
-    if (e) return e;
-    if (!latent || !image || !workspace) return NOPE_ERR_ARG;
-    unsigned char* base = (unsigned char*)(((uintptr_t)workspace + 255) / 256 * 256);
-    const size_t lost = (size_t)(base - (unsigned char*)workspace);
-    if (workspace_bytes < lost) return NOPE_ERR_WORKSPACE;
-    const size_t cap = workspace_bytes - lost;
-    const int chunk = chunk_for(vae, 1, n_img, h, w, cap);
-    if (chunk < 1) return NOPE_ERR_WORKSPACE;
-    const int f = 1 << (vae->cfg.n_levels - 1);
-    const size_t in_per = (size_t)vae->cfg.latent_channels * h * w, out_per = (size_t)vae->cfg.out_channels * (h * f) * (w * f);
-    for (int i0 = 0; i0 < n_img; i0 += chunk) {
-        const int c = n_img - i0 < chunk ? n_img - i0 : chunk;
-        e = run_decode(vae, latent + (size_t)i0 * in_per, c, h, w, image + (size_t)i0 * out_per, unnormalize ? 1 : 0, base, cap, (hipStream_t)stream,
-                       false, nullptr);
-        if (e) return e;
-    }
-    return NOPE_OK;
+    return run_chunks(vae, 1, latent, n_img, h, w, image, unnormalize ? 1 : 0, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

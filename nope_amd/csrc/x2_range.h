@@ -1,4 +1,4 @@
-// NOPE_F16X2 activation-range tracking, shared by the network runtimes (unet_runtime.hip, ldm_runtime.hip).
+// NOPE_F16X2 activation-range tracking, shared by the network runtimes that track ranges (unet_runtime.hip, ldm_runtime.hip, gd_runtime.hip) through runtime_common.h.
 //
 // The f16 + MX-fp8 tile forms its A operands from a' = a * 2^-t (t per layer: word 3 of the tail of the layer's second weight pack,
 // nope_common.h: kX2*): f16(a') saturates at 65504, e4m3(a' * 2^-2) at |a'| = 1792 and runs out of significant bits below 2^-4.  A launch

@@ -4,6 +4,7 @@ Test infrastructure only -- never loaded by nope_amd."""
 from __future__ import annotations
 
 import concurrent.futures
+import glob
 import os
 import subprocess
 
@@ -24,8 +25,7 @@ def build(force: bool = False) -> str:
     from nope_amd.csrc.build import SOURCES
     objdir = os.path.join(ROOT, "build", "emu")
     os.makedirs(objdir, exist_ok=True)
-    deps = [os.path.join(CSRC, "nope_common.h"), os.path.join(CSRC, "conv_gemm_common.h"), os.path.join(CSRC, "conv_gemm_dma.h"), os.path.join(ROOT, "include", "nope_hip.h"),
-            os.path.join(HERE, "include", "hip", "hip_runtime.h")]
+    deps = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "nope_hip.h"), os.path.join(HERE, "include", "hip", "hip_runtime.h")]
     flags = ["-x", "c++", "-std=c++20", "-O2", "-fPIC", "-pthread", "-I", os.path.join(HERE, "include"),
              "-Wno-unused-value", "-Wno-unknown-attributes", "-Wno-ignored-attributes", "-Wno-unknown-pragmas",
              "-Wno-pass-failed", "-Wno-psabi"]

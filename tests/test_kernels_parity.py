@@ -685,6 +685,117 @@ def test_workspace_canary_odd_hypotheses(be, n_hyp):
     assert rel(out.cpu(), R.unet_forward(sd, x, pose)) < F32_TOL
 
 
+# ---- the boundary code every network runtime shares (create tail, workspace base alignment) ---------------------
+def _boundary_case(net, golden, dev):
+    """(module, handle getter, tensor whose absence create must report, forwards) of a network at the smallest configuration the goldens
+    use, one sample.  A forward is (workspace bytes, output shape, call(out, ws_ptr, ws_bytes) -> code) straight on lib().dll."""
+    from nope_amd import hip
+    d = hip.lib().dll
+    if net in ("unet", "ldm", "gd"):
+        if net == "unet":
+            from nope_amd.u_net import UNet
+            from nope_amd.weights import synth_init_
+            g = golden("unet_tiny.npz")
+            x, pose = g["d8/x"][:1], g["d8/pose"][:1]
+            m = UNet(u_net_dim=8, rot_representation_dim=6, encoder=StubEncoder(8), pose_mlp_name="single_layer")
+            synth_init_(m, 2022)
+            drop = "mid_block1.block1.proj.weight"
+        elif net == "ldm":
+            from tests.test_oracle_golden import build_ldm
+            g = golden("ldm_tiny.npz")
+            x, pose = g["m32/x"][:1], g["m32/pose"][:1]
+            m = build_ldm("m32")
+            drop = "middle_block.0.in_layers.2.weight"
+        else:
+            from tests import test_guided as tg
+            x, pose = (t[:1] for t in tg.inputs(tg.TINY[0]))
+            m = tg._build(tg.TINY[0])
+            drop = "middle_block.0.in_layers.2.weight"
+        m = m.to(dev)
+        h = m._get_handle(torch.device(dev))
+        xd, pd = x.contiguous().to(dev), pose.contiguous().to(dev)
+        H, W = x.shape[-2:]
+        need = int(getattr(d, f"nope_{net}_workspace_bytes")(h._h, 1, 1, H, W))
+        fwd = getattr(d, f"nope_{net}_forward")
+        oc = h.out_dim if net == "unet" else h.out_channels
+
+        def call(out, ws, nbytes):
+            return fwd(h._h, xd.data_ptr(), 1, 1, pd.data_ptr(), 1, H, W, out.data_ptr(), hip.F32, ws, nbytes, hip._stream(xd))
+        return m, drop, [(need, (1, oc, H, W), call)]
+    if net == "vae":
+        from tests.golden.make_golden_vae import CASES, inputs, make_vae
+        tag = min(CASES, key=lambda t: CASES[t][1][1])          # the smallest image
+        image, latent = (t[:1].contiguous().to(dev) for t in inputs(tag))
+        m = make_vae(tag)
+        h = m._get_handle(torch.device(dev))
+        H, hh = image.shape[-1], latent.shape[-1]
+
+        def enc(out, ws, nbytes):
+            return d.nope_vae_encode(h._h, image.data_ptr(), 1, H, H, out.data_ptr(), ws, nbytes, hip._stream(image))
+
+        def dec(out, ws, nbytes):
+            return d.nope_vae_decode(h._h, latent.data_ptr(), 1, hh, hh, out.data_ptr(), 0, ws, nbytes, hip._stream(latent))
+        return m, "decoder.mid_block.resnets.0.conv1.weight", [
+            (int(d.nope_vae_workspace_bytes(h._h, 0, 1, H, H)), (1, h.latent_channels, H // h.factor, H // h.factor), enc),
+            (int(d.nope_vae_workspace_bytes(h._h, 1, 1, hh, hh)), (1, h.out_channels, hh * h.factor, hh * h.factor), dec)]
+    m = _encoder_pair()
+    h = m._get_handle(torch.device(dev))
+    img = (torch.rand(1, 3, 16, 16, generator=torch.Generator().manual_seed(3)) * 2 - 1).to(dev)
+
+    def call(out, ws, nbytes):
+        return d.nope_encoder_forward(h._h, img.data_ptr(), 1, 16, 16, out.data_ptr(), ws, nbytes, hip._stream(img))
+    return m, "backbone.layer2.0.bn2.running_var", [(int(d.nope_encoder_workspace_bytes(h._h, 1, 16, 16)), (1, 8, 2, 2), call)]
+
+
+@pytest.mark.parametrize("net", ["unet", "ldm", "gd", "vae", "encoder"])
+def test_runtime_boundary_of_every_network(be, golden, net, monkeypatch):
+    """What the five network runtimes do alike at the C boundary, pinned per handle: a state dict with one tensor removed fails create under the
+    function's name; a 1024-byte workspace comes back as NOPE_ERR_WORKSPACE with the output untouched; a workspace of exactly the reported
+    size whose base is 8 bytes past a 256-byte boundary works, writes nothing behind those bytes and gives the bits of the aligned run
+    (the reported size is the arena peak rounded up to 256, plus 256: 248 bytes of alignment loss fit).
+
+    The encoder is the one runtime that does not move its base: nope_encoder_workspace_bytes is stage buffers + arena with no spare 256
+    bytes, and its forward puts the arena at the pointer it is given (a base that is no multiple of 16 makes its 16-byte vector accesses
+    misaligned: the interpreter dies of it, a device may fault).  Its third check therefore runs at the aligned base only: exactly the
+    reported bytes, the canary behind them, the bits of a second run."""
+    hip, dev, _ = be
+    cls = {"unet": hip.UNetHandle, "ldm": hip.LdmHandle, "gd": hip.GdHandle, "vae": hip.VaeHandle, "encoder": hip.EncoderHandle}[net]
+    made = []
+
+    class Recording(cls):        # the arguments the module builds its handle from
+        def __init__(self, first, state_dict, *rest, **kw):
+            made.append((first, state_dict, rest, kw))
+            super().__init__(first, state_dict, *rest, **kw)
+    monkeypatch.setattr(hip, cls.__name__, Recording)
+    m, drop, forwards = _boundary_case(net, golden, dev)
+    first, sd, rest, kw = made[0]
+    assert drop in sd
+    with pytest.raises(hip.NopeError, match=f"nope_{net}_create"):
+        cls(first, {k: v for k, v in sd.items() if k != drop}, *rest, **kw)
+
+    def sync():
+        if dev != "cpu":
+            torch.cuda.synchronize()
+    for need, oshape, call in forwards:
+        assert need > 1024
+        out = torch.full(oshape, 777.0, device=dev)
+        small = torch.empty(1024, dtype=torch.uint8, device=dev)
+        assert call(out, small.data_ptr(), 1024) == -3          # NOPE_ERR_WORKSPACE
+        sync()
+        assert bool((out == 777.0).all()), "a refused forward wrote to its output"
+        buf = torch.full((need + 8 + 256 + 4096,), 0xAB, dtype=torch.uint8, device=dev)
+        a = -buf.data_ptr() % 256
+        want = torch.full(oshape, 777.0, device=dev)
+        assert call(want, buf.data_ptr() + a, need) == 0
+        sync()
+        buf.fill_(0xAB)
+        off = a + (0 if net == "encoder" else 8)
+        assert call(out, buf.data_ptr() + off, need) == 0
+        sync()
+        assert bool((buf[:off] == 0xAB).all()) and bool((buf[off + need:] == 0xAB).all()), "write outside the workspace"
+        assert bool(torch.isfinite(out).all()) and torch.equal(out, want)
+
+
 # ---- LDM cross-attention variant (SURVEY.md section 8 row f4) ---------------------------------------
 @pytest.mark.parametrize("dt", [0, 1, 2])
 def test_ldm_token_ops(be, dt):
