@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from . import hip
+from .handle_cache import HandleCache
 
 _LAYERS = (3, 4, 6, 3)
 _STRIDES = (1, 2, 2, 1)      # resnet.py:102-105
@@ -70,12 +71,10 @@ class _Trunk(_Holder):
                 m.weight.data.normal_(0, math.sqrt(2.0 / n_))
 
 
-class FeatureExtractor(nn.Module):
+class FeatureExtractor(HandleCache, nn.Module):
     def __init__(self, descriptor_size, threshold=0.2, normalize=False, compute_dtype="f32", **kwargs):
         super().__init__()
         self.compute_dtype = compute_dtype      # "f32": parity mode, "bf16": throughput mode (as UNet.compute_dtype)
-        self._handle = None
-        self._handle_key = None
         self.latent_dim = descriptor_size
         self.normalize = normalize
         self.threshold = threshold
@@ -85,29 +84,14 @@ class FeatureExtractor(nn.Module):
                                        nn.Conv2d(256, descriptor_size, 1, bias=False))
         self.encoder = nn.Sequential(self.backbone, self.projector)   # aliased, as in template.py:40
         self.eval()
-        # runs for a load_state_dict on this module or on any parent (UNet, PoseConditional, a Lightning module)
-        self.register_load_state_dict_post_hook(lambda mod, _keys: mod.invalidate())
+        self._init_handle_cache()
 
-    def invalidate(self):
-        """Drop the folded / repacked device weights; the next device call rebuilds them."""
-        self._handle = None
-        self.__dict__.pop("_own_tensors", None)      # the cached tensor list: parameters may have been re-assigned (load_state_dict(assign=True))
+    def _versioned_tensors(self):       # every parameter and BatchNorm buffer the handle folds
+        return list(self.backbone.parameters()) + list(self.backbone.buffers()) + list(self.projector.parameters())
 
-    def _weights_version(self):
-        # (storage address, version counter) per parameter / BatchNorm buffer, as UNet._weights_version: `.data` writes need invalidate()
-        ts = self.__dict__.get("_own_tensors")
-        if ts is None:
-            ts = self.__dict__["_own_tensors"] = list(self.backbone.parameters()) + list(self.backbone.buffers()) + list(self.projector.parameters())
-        return hash(tuple((t.data_ptr(), t._version) for t in ts))
-
-    def _get_handle(self, device) -> "hip.EncoderHandle":
-        key = (str(device), self.compute_dtype, self._weights_version())
-        if self._handle is None or self._handle_key != key:
-            sd = {k: v.to(device) for k, v in self.state_dict().items() if k.startswith(("backbone.", "projector."))}
-            self._handle = hip.EncoderHandle(self.latent_dim, sd, hip.dtype_code(self.compute_dtype),
-                                             bn_eps=self.backbone.bn1.eps)
-            self._handle_key = key
-        return self._handle
+    def _make_handle(self, device):
+        sd = {k: v.to(device) for k, v in self.state_dict().items() if k.startswith(("backbone.", "projector."))}
+        return hip.EncoderHandle(self.latent_dim, sd, hip.dtype_code(self.compute_dtype), bn_eps=self.backbone.bn1.eps)
 
     @torch.no_grad()
     def encode_image(self, image, mode=None):

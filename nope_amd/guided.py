@@ -25,12 +25,10 @@ whose H and W are multiples of 2^(levels-1).  Anything else raises NotImplemente
 """
 from __future__ import annotations
 
-from typing import Optional
-
-import torch
 from torch import nn
 
 from . import hip
+from .handle_cache import HypothesisNetwork
 from .u_net import _Params, _slot
 
 POSE_MLP = {"single_layer": 1, "two_layers": 2, "posEncoding": 3}          # NOPE_GD_POSE_*
@@ -71,7 +69,11 @@ def head_channels(ch, num_heads, num_head_channels):
     return dh
 
 
-class UNetModelPose(nn.Module):
+class UNetModelPose(HypothesisNetwork, nn.Module):
+    """adapt_u_net.py:13-97; `forward(x, pose)` is adapt_u_net.py:78-97 with module(h, emb) (-> (B,out_channels,h,w) f32),
+    `forward_hypotheses` the template loop model.py:212-222 (both, the device handle behind them and `invalidate()` in
+    handle_cache.HypothesisNetwork)."""
+
     def __init__(self, pose_mlp_name, rot_representation_dim, encoder, image_size, in_channels, model_channels, out_channels,
                  num_res_blocks, attention_resolutions, dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2,
                  num_classes=None, use_checkpoint=False, use_fp16=False, num_heads=1, num_head_channels=-1, num_heads_upsample=-1,
@@ -157,56 +159,14 @@ class UNetModelPose(nn.Module):
             self.pose_mlp = _slot(nn.Linear(rot_representation_dim, emb))
         elif pose_mlp_name == "two_layers":
             self.pose_mlp = _slot(nn.Linear(rot_representation_dim, emb), None, nn.Linear(emb, emb))
-        self._handle: Optional[hip.GdHandle] = None
-        self._handle_key = None
-        self.register_load_state_dict_post_hook(lambda mod, _keys: mod.invalidate())
+        self._init_handle_cache()
 
-    def own_state_dict(self):
-        return {k: v for k, v in self.state_dict().items() if not k.startswith("encoder.")}
-
-    def invalidate(self):
-        self._handle = None
-        self.__dict__.pop("_own_params", None)      # the cached tensor list: parameters may have been re-assigned (load_state_dict(assign=True))
-        inv = getattr(self.encoder, "invalidate", None)
-        if callable(inv):
-            inv()
-
-    def _weights_version(self):
-        # (storage address, version counter) per tensor, as nope_amd.ldm.UNetModelPose: `.data` writes need invalidate()
-        ps = self.__dict__.get("_own_params")
-        if ps is None:
-            ps = self.__dict__["_own_params"] = [p for n, p in self.named_parameters(recurse=True) if not n.startswith("encoder.")]
-        return hash(tuple((p.data_ptr(), p._version) for p in ps))
-
-    def _get_handle(self, device) -> "hip.GdHandle":
-        key = (str(device), self.compute_dtype, self._weights_version())
-        if self._handle is None or self._handle_key != key:
-            sd = {k: v.to(device) for k, v in self.own_state_dict().items() if not k.startswith("time_embed.")}
-            cfg = dict(in_channels=self.in_channels, model_channels=self.model_channels, out_channels=self.out_channels,
-                       num_res_blocks=self.num_res_blocks, channel_mult=self.channel_mult, attn_levels=self.attn_levels,
-                       head_channels_in=self.head_channels_in, head_channels_out=self.head_channels_out,
-                       head_channels_mid=self.head_channels_mid, pose_dim=self.rot_representation_dim, pose_mlp=POSE_MLP[self.pose_mlp_name],
-                       new_attention_order=int(self.use_new_attention_order), resblock_updown=int(self.resblock_updown),
-                       conv_resample=int(self.conv_resample), use_scale_shift_norm=int(self.use_scale_shift_norm))
-            self._handle = hip.GdHandle(cfg, sd, hip.dtype_code(self.compute_dtype))
-            self._handle_key = key
-        return self._handle
-
-    @torch.no_grad()
-    def forward(self, x, pose):
-        """adapt_u_net.py:78-97 with module(h, emb).  x (B,C,h,w), pose (B,rot_dim) -> (B,out_channels,h,w) f32."""
-        return self._get_handle(x.device).forward(x, pose, x_rep=1)
-
-    @torch.no_grad()
-    def forward_hypotheses(self, x, poses, out=None, out_dtype="f32", defer_range_check=False):
-        """x (B,C,h,w) reference latents, poses (B,N,rot_dim) -> (B,N,C,h,w): the body of the template loop model.py:212-222.
-        defer_range_check (f16x2): the caller calls finish_range_check() before it reads the output (as nope_amd.UNet)."""
-        B, N = poses.shape[:2]
-        flat = poses.reshape(B * N, poses.shape[-1])
-        o = None if out is None else out.view(B * N, *out.shape[2:])
-        y = self._get_handle(x.device).forward(x, flat, x_rep=N, out=o, out_dtype=hip.dtype_code(out_dtype), defer_range_check=defer_range_check)
-        return y.view(B, N, *y.shape[1:])
-
-    def finish_range_check(self) -> bool:
-        """f16x2: check (and if needed repeat) the forwards issued with defer_range_check; True when any was repeated (hip.GdHandle)."""
-        return self._handle.finish_range_check() if self._handle is not None else False
+    def _make_handle(self, device):
+        sd = {k: v.to(device) for k, v in self.own_state_dict().items() if not k.startswith("time_embed.")}
+        cfg = dict(in_channels=self.in_channels, model_channels=self.model_channels, out_channels=self.out_channels,
+                   num_res_blocks=self.num_res_blocks, channel_mult=self.channel_mult, attn_levels=self.attn_levels,
+                   head_channels_in=self.head_channels_in, head_channels_out=self.head_channels_out,
+                   head_channels_mid=self.head_channels_mid, pose_dim=self.rot_representation_dim, pose_mlp=POSE_MLP[self.pose_mlp_name],
+                   new_attention_order=int(self.use_new_attention_order), resblock_updown=int(self.resblock_updown),
+                   conv_resample=int(self.conv_resample), use_scale_shift_norm=int(self.use_scale_shift_norm))
+        return hip.GdHandle(cfg, sd, hip.dtype_code(self.compute_dtype))

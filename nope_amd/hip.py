@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -79,35 +80,15 @@ _PROTOS = {
     "nope_op_render_depth": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "nope_op_vsd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nope_op_vsd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i, _vp, _vp, _sz, _vp]),
-    "nope_unet_create": (_i, [C.POINTER(UNetConfig), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)]),
-    "nope_unet_destroy": (None, [_vp]),
-    "nope_unet_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "nope_unet_forward": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "nope_unet_graph_limit": (_i, [_vp, C.c_longlong]),
     "nope_unet_graph_replays": (_i, [_vp]),
-    "nope_unet_x2_range_check": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
-    "nope_unet_x2_poll": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
-    "nope_unet_x2_enable": (_i, [_vp, _i]),
     "nope_unet_x2_shifts": (_i, [_vp, C.POINTER(_i), _i, C.POINTER(_i)]),
-    "nope_ldm_x2_range_check": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
-    "nope_ldm_x2_poll": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
-    "nope_ldm_x2_enable": (_i, [_vp, _i]),
-    "nope_gd_create": (_i, [C.POINTER(GdConfig), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)]),
-    "nope_gd_destroy": (None, [_vp]),
-    "nope_gd_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "nope_gd_forward": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
-    "nope_gd_x2_range_check": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
-    "nope_gd_x2_poll": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
-    "nope_gd_x2_enable": (_i, [_vp, _i]),
     "nope_unet_profile": (_i, [_vp, _i]),
     "nope_unet_profile_read": (_i, [_vp, C.POINTER(_i), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nope_unet_profile_launches": (_i, [_vp, C.POINTER(ConvLaunchInfo), _i, C.POINTER(_i)]),
     "nope_op_nchw_to_nhwc": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_nhwc_to_nchw": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_pack_conv_weight": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "nope_encoder_create": (_i, [C.POINTER(EncoderConfig), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)]),
-    "nope_encoder_destroy": (None, [_vp]),
-    "nope_encoder_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "nope_encoder_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "nope_op_conv": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nope_op_conv_ws": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
@@ -127,21 +108,27 @@ _PROTOS = {
     "nope_op_linear_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_linear": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "nope_ldm_create": (_i, [C.POINTER(LdmConfig), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)]),
-    "nope_ldm_destroy": (None, [_vp]),
-    "nope_ldm_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "nope_ldm_forward": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "nope_op_warp_perspective": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_float), _vp, _i, _i, C.c_float, C.c_float, _vp]),
     "nope_op_layer_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, _vp]),
     "nope_op_geglu": (_i, [_i, _vp, _vp, _i64, _i, _vp]),
     "nope_op_token_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_wide_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
-    "nope_vae_create": (_i, [C.POINTER(VaeConfig), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)]),
-    "nope_vae_destroy": (None, [_vp]),
-    "nope_vae_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "nope_vae_encode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "nope_vae_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
 }
+# the entries every network runtime exports under its own stem, nope_{stem}_{entry}; the hypothesis networks (forward(x, pose) with the
+# NOPE_F16X2 range tracking) share their whole call surface
+_NETWORKS = {"unet": (UNetConfig, 4, True), "ldm": (LdmConfig, 4, True), "gd": (GdConfig, 4, True),       # stem: (config struct, size arguments
+             "encoder": (EncoderConfig, 3, False), "vae": (VaeConfig, 4, False)}                           #  of workspace_bytes, hypothesis network)
+_X2_VERDICT = (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)])
+for _stem, (_cfg, _nsize, _hyp) in _NETWORKS.items():
+    _PROTOS[f"nope_{_stem}_create"] = (_i, [C.POINTER(_cfg), C.POINTER(TensorDesc), _i, _vp, C.POINTER(_vp)])
+    _PROTOS[f"nope_{_stem}_destroy"] = (None, [_vp])
+    _PROTOS[f"nope_{_stem}_workspace_bytes"] = (_sz, [_vp] + [_i] * _nsize)
+    if _hyp:
+        _PROTOS[f"nope_{_stem}_forward"] = (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp])
+        _PROTOS[f"nope_{_stem}_x2_range_check"] = _PROTOS[f"nope_{_stem}_x2_poll"] = _X2_VERDICT
+        _PROTOS[f"nope_{_stem}_x2_enable"] = (_i, [_vp, _i])
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
 
@@ -419,33 +406,72 @@ def _tensor_descs(state_dict: Dict[str, torch.Tensor]):
 
 
 # --------------------------------------------------------------------------------------------
-# Template-encoder handle
+# Network handles: what the five of them share
 # --------------------------------------------------------------------------------------------
-class EncoderHandle:
-    """Owns a `nope_encoder*` built from the FeatureExtractor's state dict (BatchNorm folded at create time)."""
+def _fill(c, cfg: dict, ints=(), arrays=(), **defaults):
+    """Config struct c from the cfg dict: the int fields `ints` (required) and `defaults` (name=value when absent), and the fixed-length int
+    arrays `arrays`, of which the first gives c.n_levels and each is read up to that length."""
+    for k in ints:
+        setattr(c, k, int(cfg[k]))
+    for k, d in defaults.items():
+        setattr(c, k, int(cfg.get(k, d)))
+    for k in arrays:
+        if k == arrays[0]:
+            c.n_levels = len(tuple(cfg[k]))
+        for i in range(c.n_levels):
+            getattr(c, k)[i] = int(cfg[k][i])
+    return c
 
-    def __init__(self, descriptor_size: int, state_dict: Dict[str, torch.Tensor], compute_dtype=F32, bn_eps: float = 1e-5):
-        l = lib()
-        self._l = l
-        c = EncoderConfig()
-        c.descriptor_size = int(descriptor_size)
-        c.compute_dtype = dtype_code(compute_dtype)
-        c.bn_eps = float(bn_eps)
-        self.descriptor_size, self.compute_dtype = c.descriptor_size, c.compute_dtype
-        sd = {k: v for k, v in state_dict.items() if k.startswith(("backbone.", "projector.")) and v.dtype.is_floating_point}
-        descs, keep, dev = _tensor_descs(sd)
+
+class _Handle:
+    """Owns one `nope_{_stem}*` of the library: create / destroy by symbol stem, and one workspace arena per (device, stream)."""
+    _stem = ""
+
+    def _fn(self, entry: str):
+        return getattr(self._l.dll, f"nope_{self._stem}_{entry}")
+
+    def _create(self, c, state_dict: Dict[str, torch.Tensor]):
+        self._l = l = lib()
+        self.compute_dtype = c.compute_dtype
+        descs, keep, dev = _tensor_descs(state_dict)
         self.device = dev
         h = _vp()
         stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else 0
-        l.check(l.dll.nope_encoder_create(C.byref(c), descs, len(sd), stream, C.byref(h)), "nope_encoder_create")
+        l.check(self._fn("create")(C.byref(c), descs, len(state_dict), stream, C.byref(h)), f"nope_{self._stem}_create")
         self._h = h
-        self._ws: Dict[tuple, torch.Tensor] = {}
+        self._ws: Dict[tuple, torch.Tensor] = {}     # one arena per (device, stream): forwards on different streams never share one
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            self._l.dll.nope_encoder_destroy(h)
+            self._fn("destroy")(h)
             self._h = None
+
+    def _arena(self, t: torch.Tensor, need: int) -> torch.Tensor:
+        """The workspace of t's (device, stream), grown to at least `need` bytes."""
+        key = (str(t.device), _stream(t))
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            self._ws.pop(key, None)          # release the smaller arena before taking a bigger one
+            ws = None
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=t.device)
+        return ws
+
+
+# --------------------------------------------------------------------------------------------
+# Template-encoder handle
+# --------------------------------------------------------------------------------------------
+class EncoderHandle(_Handle):
+    """Owns a `nope_encoder*` built from the FeatureExtractor's state dict (BatchNorm folded at create time)."""
+    _stem = "encoder"
+
+    def __init__(self, descriptor_size: int, state_dict: Dict[str, torch.Tensor], compute_dtype=F32, bn_eps: float = 1e-5):
+        c = EncoderConfig()
+        c.descriptor_size = int(descriptor_size)
+        c.compute_dtype = dtype_code(compute_dtype)
+        c.bn_eps = float(bn_eps)
+        self.descriptor_size = c.descriptor_size
+        self._create(c, {k: v for k, v in state_dict.items() if k.startswith(("backbone.", "projector.")) and v.dtype.is_floating_point})
 
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         """image (B,3,H,W) f32 -> (B,descriptor_size,H/8,W/8) f32."""
@@ -457,11 +483,7 @@ class EncoderHandle:
         need = int(self._l.dll.nope_encoder_workspace_bytes(self._h, B, H, W))
         if need == 0:
             raise NopeError(f"unsupported encoder input size {H}x{W} (must be multiples of 8)")
-        # one workspace per stream: two encoder passes may be in flight on different streams (model.generate_and_retrieve)
-        key = (str(image.device), _stream(image))
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=image.device)
+        ws = self._arena(image, need)      # (per stream: two encoder passes may be in flight on different streams, model.generate_and_retrieve)
         out = torch.empty((B, self.descriptor_size, H // 8, W // 8), dtype=torch.float32, device=image.device)
         self._l.check(self._l.dll.nope_encoder_forward(self._h, _ptr(image), B, H, W, _ptr(out), _ptr(ws), need, _stream(image)),
                       "nope_encoder_forward")
@@ -481,12 +503,15 @@ def op_stem_conv(dt: int, image: torch.Tensor, w: torch.Tensor, scale: torch.Ten
 
 
 # --------------------------------------------------------------------------------------------
-# NOPE_F16X2 activation ranges: shared by the network handles (include/nope_hip.h: nope_unet_x2_poll)
+# The hypothesis networks (U-Net, LDM, guided diffusion): one forward(x, pose) and the NOPE_F16X2 activation ranges
+# (include/nope_hip.h: nope_unet_x2_poll; the three runtimes export the same entries under their stems)
 # --------------------------------------------------------------------------------------------
-class _X2RangeMixin:
-    _x2_prefix = "unet"
+class _HypothesisHandle(_Handle):
+    _label = ""          # the network's name in the "unsupported ... problem size" message
 
-    def _x2_init(self):
+    def _create(self, c, state_dict, cin: int, cout: int):
+        self._cin, self._cout, self.pose_dim = cin, cout, c.pose_dim
+        super()._create(c, state_dict)
         # NOPE_F16X2 activation ranges.  The library judges every forward on the device and overwrites the output of one whose layers left
         # their accurate windows with NaNs (include/nope_hip.h: nope_unet_x2_poll) -- no synchronisation in the step.  range_mode:
         #   "poison"            nothing more: the verdicts that have arrived are read at the start of the next forward (shifts re-centred,
@@ -504,6 +529,39 @@ class _X2RangeMixin:
         self._pending: List[tuple] = []              # forwards issued with defer_range_check: (re-launch closure, stream)
         self._warned = False
         self.x2_enabled = self.compute_dtype == F16X2
+
+    def forward(self, x: torch.Tensor, pose: torch.Tensor, x_rep: int = 1, out: Optional[torch.Tensor] = None,
+                out_dtype=F32, defer_range_check: bool = False) -> torch.Tensor:
+        """out[j] = net(x[j // x_rep], pose[j]); x (n_src,C,H,W) f32, pose (n_src*x_rep, pose_dim).  defer_range_check (NOPE_F16X2): the
+        caller will call finish_range_check() itself before it hands results out."""
+        require_device(x)
+        x = _f32c(x)
+        pose = _f32c(pose)
+        n_src, Cc, H, W = x.shape
+        n_hyp = pose.shape[0]
+        if Cc != self._cin or pose.shape[1] != self.pose_dim or n_src * x_rep != n_hyp:
+            raise NopeError(f"shape mismatch: x {tuple(x.shape)}, pose {tuple(pose.shape)}, x_rep {x_rep}")
+        odt = dtype_code(out_dtype)
+        if out is None:
+            out = torch.empty((n_hyp, self._cout, H, W), dtype=torch_dtype(odt), device=x.device)
+        assert out.is_contiguous() and out.numel() == n_hyp * self._cout * H * W and out.dtype == torch_dtype(odt)
+        need = int(self._fn("workspace_bytes")(self._h, n_hyp, n_src, H, W))
+        if need == 0:
+            raise NopeError(f"unsupported {self._label} problem size n_hyp={n_hyp} H={H} W={W}")
+        ws = self._arena(x, need)
+        fn, what = self._fn("forward"), f"nope_{self._stem}_forward"
+        def launch():
+            self._l.check(fn(self._h, _ptr(x), n_src, x_rep, _ptr(pose), n_hyp, H, W, _ptr(out), odt, _ptr(ws), ws.numel(), _stream(x)), what)
+        self._x2_before_forward(_stream(x))
+        launch()
+        if self._x2_mode() == "repeat" and self.x2_enabled:
+            # the check needs the forward to have finished: callers that go on issuing work on the stream (PoseConditional: scoring,
+            # top-k) call finish_range_check() at the END of their step -- one synchronisation where the results are read anyway --
+            # and repeat their own tail when it says the forward was repeated
+            self._pending.append((launch, _stream(x)))
+            if not defer_range_check:
+                self.finish_range_check()
+        return out
 
     def _x2_mode(self) -> str:
         if self.range_mode == "auto":
@@ -531,14 +589,13 @@ class _X2RangeMixin:
         """(code, layers out of range, layers whose shift moved, largest |activation|) of the forwards judged since the last look; sync:
         synchronise `stream` first (every forward issued on it is judged), else only the verdicts that have already arrived."""
         bad, moved, amax = _i(0), _i(0), C.c_float(0)
-        fn = getattr(self._l.dll, f"nope_{self._x2_prefix}_x2_range_check" if sync else f"nope_{self._x2_prefix}_x2_poll")
-        code = int(fn(self._h, stream, C.byref(bad), C.byref(moved), C.byref(amax)))
+        code = int(self._fn("x2_range_check" if sync else "x2_poll")(self._h, stream, C.byref(bad), C.byref(moved), C.byref(amax)))
         if code not in (0, ERR_RANGE, ERR_RANGE_F16):
-            self._l.check(code, f"nope_{self._x2_prefix}_x2_range_check")
+            self._l.check(code, f"nope_{self._stem}_x2_range_check")
         return code, bad.value, moved.value, float(amax.value)
 
     def x2_enable(self, on: bool):
-        self._l.check(getattr(self._l.dll, f"nope_{self._x2_prefix}_x2_enable")(self._h, int(bool(on))), f"nope_{self._x2_prefix}_x2_enable")
+        self._l.check(self._fn("x2_enable")(self._h, int(bool(on))), f"nope_{self._stem}_x2_enable")
         self.x2_enabled = bool(on) and self.compute_dtype == F16X2
 
     def finish_range_check(self) -> bool:
@@ -567,43 +624,18 @@ class _X2RangeMixin:
         return repeated
 
 
-# --------------------------------------------------------------------------------------------
-# U-Net handle
-# --------------------------------------------------------------------------------------------
-class UNetHandle(_X2RangeMixin):
+class UNetHandle(_HypothesisHandle):
     """Owns a `nope_unet*` built from a reference-keyed state dict."""
+    _stem, _label = "unet", "U-Net"
 
     def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], compute_dtype=F32):
-        l = lib()
-        self._l = l
-        c = UNetConfig()
-        c.u_net_dim = cfg["u_net_dim"]; c.channels = cfg["channels"]; c.out_dim = cfg.get("out_dim", cfg["channels"])
-        c.pose_dim = cfg.get("pose_dim", 6)
-        mults = tuple(cfg.get("dim_mults", (1, 2, 4, 8)))
-        c.n_levels = len(mults)
-        for i, m in enumerate(mults):
-            c.dim_mults[i] = m
-        c.groups = cfg.get("groups", 8); c.heads = 4; c.dim_head = 32
-        c.pose_mlp_layers = cfg.get("pose_mlp_layers", 1)
+        c = _fill(UNetConfig(), {"dim_mults": (1, 2, 4, 8), **cfg}, ints=("u_net_dim", "channels"), arrays=("dim_mults",),
+                  out_dim=cfg["channels"], pose_dim=6, groups=8, pose_mlp_layers=1, soft_up_down=0)
+        c.heads, c.dim_head = 4, 32
         c.compute_dtype = dtype_code(compute_dtype)
-        c.soft_up_down = int(cfg.get("soft_up_down", 0))
         self.cfg = dict(cfg)
-        self.compute_dtype = c.compute_dtype
-        self.channels, self.out_dim, self.pose_dim = c.channels, c.out_dim, c.pose_dim
-        descs, keep, dev = _tensor_descs(state_dict)
-        self.device = dev
-        h = _vp()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else 0
-        l.check(l.dll.nope_unet_create(C.byref(c), descs, len(state_dict), stream, C.byref(h)), "nope_unet_create")
-        self._h = h
-        self._ws: Dict[tuple, torch.Tensor] = {}     # one arena per (device, stream): forwards on different streams never share one
-        self._x2_init()
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._l.dll.nope_unet_destroy(h)
-            self._h = None
+        self.channels, self.out_dim = c.channels, c.out_dim
+        self._create(c, state_dict, c.channels, c.out_dim)
 
     def x2_shifts(self) -> List[int]:
         n = _i(0)
@@ -644,158 +676,33 @@ class UNetHandle(_X2RangeMixin):
     def workspace_bytes(self, n_hyp: int, n_src: int, H: int, W: int) -> int:
         return int(self._l.dll.nope_unet_workspace_bytes(self._h, n_hyp, n_src, H, W))
 
-    def forward(self, x: torch.Tensor, pose: torch.Tensor, x_rep: int = 1, out: Optional[torch.Tensor] = None,
-                out_dtype=F32, defer_range_check: bool = False) -> torch.Tensor:
-        """out[j] = UNet(x[j // x_rep], pose[j]); x (n_src,C,H,W) f32, pose (n_src*x_rep, pose_dim).  defer_range_check (NOPE_F16X2): the
-        caller will call finish_range_check() itself before it hands results out."""
-        require_device(x)
-        x = _f32c(x)
-        pose = _f32c(pose)
-        n_src, Cc, H, W = x.shape
-        n_hyp = pose.shape[0]
-        if Cc != self.channels or pose.shape[1] != self.pose_dim or n_src * x_rep != n_hyp:
-            raise NopeError(f"shape mismatch: x {tuple(x.shape)}, pose {tuple(pose.shape)}, x_rep {x_rep}")
-        odt = dtype_code(out_dtype)
-        if out is None:
-            out = torch.empty((n_hyp, self.out_dim, H, W), dtype=torch_dtype(odt), device=x.device)
-        assert out.is_contiguous() and out.numel() == n_hyp * self.out_dim * H * W and out.dtype == torch_dtype(odt)
-        need = self.workspace_bytes(n_hyp, n_src, H, W)
-        if need == 0:
-            raise NopeError(f"unsupported U-Net problem size n_hyp={n_hyp} H={H} W={W}")
-        key = (str(x.device), _stream(x))
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            self._ws.pop(key, None)          # release the smaller arena before taking a bigger one
-            ws = None
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
-        def launch():
-            self._l.check(self._l.dll.nope_unet_forward(self._h, _ptr(x), n_src, x_rep, _ptr(pose), n_hyp, H, W, _ptr(out), odt,
-                                                        _ptr(ws), ws.numel(), _stream(x)), "nope_unet_forward")
-        self._x2_before_forward(_stream(x))
-        launch()
-        if self._x2_mode() == "repeat" and self.x2_enabled:
-            # the check needs the forward to have finished: callers that go on issuing work on the stream (PoseConditional: scoring,
-            # top-k) call finish_range_check() at the END of their step -- one synchronisation where the results are read anyway --
-            # and repeat their own tail when it says the forward was repeated
-            self._pending.append((launch, _stream(x)))
-            if not defer_range_check:
-                self.finish_range_check()
-        return out
 
-
-# --------------------------------------------------------------------------------------------
-# LDM cross-attention U-Net handle
-# --------------------------------------------------------------------------------------------
-class LdmHandle(_X2RangeMixin):
-    _x2_prefix = "ldm"
-
+class LdmHandle(_HypothesisHandle):
     """Owns a `nope_ldm*` built from a UNetModelPose state dict (reference keys)."""
+    _stem, _label = "ldm", "LDM U-Net"
 
     def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], compute_dtype=F32):
-        l = lib()
-        self._l = l
-        c = LdmConfig()
-        for k in ("in_channels", "model_channels", "out_channels", "num_res_blocks", "num_head_channels", "context_dim", "pose_dim",
-                  "pose_mlp_layers", "injecting_condition_twice"):
-            setattr(c, k, int(cfg[k]))
-        mult = tuple(cfg["channel_mult"])
-        c.n_levels = len(mult)
-        for i, m in enumerate(mult):
-            c.channel_mult[i] = m
-            c.attn_levels[i] = int(cfg["attn_levels"][i])
-        c.compute_dtype = dtype_code(compute_dtype)
-        c.use_scale_shift_norm = int(cfg.get("use_scale_shift_norm", 0))
-        c.transformer_depth = int(cfg.get("transformer_depth", 1))
-        heads = tuple(cfg.get("head_channels", ()))          # per level (num_head_channels = 0); else num_head_channels everywhere
-        for i, d in enumerate(heads):
+        c = _fill(LdmConfig(), cfg, ints=("in_channels", "model_channels", "out_channels", "num_res_blocks", "num_head_channels", "context_dim",
+                                          "pose_dim", "pose_mlp_layers", "injecting_condition_twice"), arrays=("channel_mult", "attn_levels"),
+                  use_scale_shift_norm=0, transformer_depth=1, resblock_updown=0, conv_resample=1)
+        for i, d in enumerate(cfg.get("head_channels", ())):      # per level (num_head_channels = 0); else num_head_channels everywhere
             c.head_channels[i] = int(d)
-        c.resblock_updown = int(cfg.get("resblock_updown", 0))
-        c.conv_resample = int(cfg.get("conv_resample", 1))
-        self.in_channels, self.out_channels, self.pose_dim = c.in_channels, c.out_channels, c.pose_dim
-        descs, keep, dev = _tensor_descs(state_dict)
-        self.device = dev
-        h = _vp()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else 0
-        l.check(l.dll.nope_ldm_create(C.byref(c), descs, len(state_dict), stream, C.byref(h)), "nope_ldm_create")
-        self._h = h
-        self._ws: Dict[tuple, torch.Tensor] = {}
-        self.compute_dtype = c.compute_dtype
-        self._x2_init()
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            getattr(self._l.dll, f"nope_{self._x2_prefix}_destroy")(h)
-            self._h = None
-
-    def forward(self, x: torch.Tensor, pose: torch.Tensor, x_rep: int = 1, out: Optional[torch.Tensor] = None, out_dtype=F32,
-                defer_range_check: bool = False) -> torch.Tensor:
-        """As UNetHandle.forward: defer_range_check (NOPE_F16X2): the caller calls finish_range_check() itself before it hands results out."""
-        require_device(x)
-        x, pose = _f32c(x), _f32c(pose)
-        n_src, Cc, H, W = x.shape
-        n_hyp = pose.shape[0]
-        if Cc != self.in_channels or pose.shape[1] != self.pose_dim or n_src * x_rep != n_hyp:
-            raise NopeError(f"shape mismatch: x {tuple(x.shape)}, pose {tuple(pose.shape)}, x_rep {x_rep}")
-        odt = dtype_code(out_dtype)
-        if out is None:
-            out = torch.empty((n_hyp, self.out_channels, H, W), dtype=torch_dtype(odt), device=x.device)
-        assert out.is_contiguous() and out.numel() == n_hyp * self.out_channels * H * W and out.dtype == torch_dtype(odt)
-        pfx = self._x2_prefix
-        need = int(getattr(self._l.dll, f"nope_{pfx}_workspace_bytes")(self._h, n_hyp, n_src, H, W))
-        if need == 0:
-            raise NopeError(f"unsupported {pfx.upper()} U-Net problem size n_hyp={n_hyp} H={H} W={W}")
-        key = (str(x.device), _stream(x))
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            self._ws.pop(key, None)
-            ws = None
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
-        def launch():
-            self._l.check(getattr(self._l.dll, f"nope_{pfx}_forward")(self._h, _ptr(x), n_src, x_rep, _ptr(pose), n_hyp, H, W, _ptr(out), odt,
-                                                                      _ptr(ws), ws.numel(), _stream(x)), f"nope_{pfx}_forward")
-        self._x2_before_forward(_stream(x))          # NOPE_F16X2: verdicts of earlier forwards (no waiting), _X2RangeMixin
-        launch()
-        if self._x2_mode() == "repeat" and self.x2_enabled:
-            self._pending.append((launch, _stream(x)))
-            if not defer_range_check:
-                self.finish_range_check()
-        return out
+        c.compute_dtype = dtype_code(compute_dtype)
+        self.in_channels, self.out_channels = c.in_channels, c.out_channels
+        self._create(c, state_dict, c.in_channels, c.out_channels)
 
 
-# --------------------------------------------------------------------------------------------
-# Guided-diffusion U-Net handle (forward / range checks as LdmHandle, on nope_gd_*)
-# --------------------------------------------------------------------------------------------
-class GdHandle(LdmHandle):
-    _x2_prefix = "gd"
-
+class GdHandle(_HypothesisHandle):
     """Owns a `nope_gd*` built from a guided-diffusion UNetModelPose state dict (reference keys)."""
+    _stem, _label = "gd", "GD U-Net"
 
     def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], compute_dtype=F32):
-        l = lib()
-        self._l = l
-        c = GdConfig()
-        for k in ("in_channels", "model_channels", "out_channels", "num_res_blocks", "head_channels_mid", "pose_dim", "pose_mlp",
-                  "new_attention_order", "resblock_updown", "conv_resample", "use_scale_shift_norm"):
-            setattr(c, k, int(cfg[k]))
-        mult = tuple(cfg["channel_mult"])
-        c.n_levels = len(mult)
-        for i, m in enumerate(mult):
-            c.channel_mult[i] = m
-            c.attn_levels[i] = int(cfg["attn_levels"][i])
-            c.head_channels_in[i] = int(cfg["head_channels_in"][i])
-            c.head_channels_out[i] = int(cfg["head_channels_out"][i])
+        c = _fill(GdConfig(), cfg, ints=("in_channels", "model_channels", "out_channels", "num_res_blocks", "head_channels_mid", "pose_dim", "pose_mlp",
+                                         "new_attention_order", "resblock_updown", "conv_resample", "use_scale_shift_norm"),
+                  arrays=("channel_mult", "attn_levels", "head_channels_in", "head_channels_out"))
         c.compute_dtype = dtype_code(compute_dtype)
-        self.in_channels, self.out_channels, self.pose_dim = c.in_channels, c.out_channels, c.pose_dim
-        descs, keep, dev = _tensor_descs(state_dict)
-        self.device = dev
-        h = _vp()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else 0
-        l.check(l.dll.nope_gd_create(C.byref(c), descs, len(state_dict), stream, C.byref(h)), "nope_gd_create")
-        self._h = h
-        self._ws: Dict[tuple, torch.Tensor] = {}
-        self.compute_dtype = c.compute_dtype
-        self._x2_init()
+        self.in_channels, self.out_channels = c.in_channels, c.out_channels
+        self._create(c, state_dict, c.in_channels, c.out_channels)
 
 
 def op_warp_perspective(img: torch.Tensor, minv, size: int, scale: float = 1.0, shift: float = 0.0, round_u8: bool = False) -> torch.Tensor:
@@ -853,39 +760,19 @@ def op_wide_attention(dt: int, qkv: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------------------------
 # Stable Diffusion VAE handle
 # --------------------------------------------------------------------------------------------
-class VaeHandle:
+class VaeHandle(_Handle):
     """Owns a `nope_vae*` built from an AutoencoderKL state dict (diffusers 0.14 keys, without the wrapper's `encoder.` prefix)."""
+    _stem = "vae"
 
     def __init__(self, cfg: dict, state_dict: Dict[str, torch.Tensor], compute_dtype=F32, max_workspace_bytes: int = 4 << 30):
-        l = lib()
-        self._l = l
-        c = VaeConfig()
-        boc = tuple(int(v) for v in cfg["block_out_channels"])
-        c.in_channels, c.out_channels = int(cfg["in_channels"]), int(cfg["out_channels"])
-        c.n_levels = len(boc)
-        for i, v in enumerate(boc):
-            c.block_out_channels[i] = v
-        c.layers_per_block, c.latent_channels = int(cfg["layers_per_block"]), int(cfg["latent_channels"])
-        c.norm_num_groups = int(cfg["norm_num_groups"])
+        c = _fill(VaeConfig(), cfg, ints=("in_channels", "out_channels", "layers_per_block", "latent_channels", "norm_num_groups"),
+                  arrays=("block_out_channels",))
         c.compute_dtype = dtype_code(compute_dtype)
         c.gn_eps = 1e-6
         self.in_channels, self.out_channels, self.latent_channels = c.in_channels, c.out_channels, c.latent_channels
         self.factor = 2 ** (c.n_levels - 1)
-        self.compute_dtype = c.compute_dtype
         self.max_workspace_bytes = int(max_workspace_bytes)
-        descs, keep, dev = _tensor_descs(state_dict)
-        self.device = dev
-        h = _vp()
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None and dev.type == "cuda" else 0
-        l.check(l.dll.nope_vae_create(C.byref(c), descs, len(state_dict), stream, C.byref(h)), "nope_vae_create")
-        self._h = h
-        self._ws: Dict[tuple, torch.Tensor] = {}
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._l.dll.nope_vae_destroy(h)
-            self._h = None
+        self._create(c, state_dict)
 
     def _workspace(self, x: torch.Tensor, decode: int, n: int, H: int, W: int) -> torch.Tensor:
         """The workspace of the largest chunk of at most n samples within max_workspace_bytes (the library runs the batch chunk by chunk)."""
@@ -903,13 +790,7 @@ class VaeHandle:
                 hi = mid - 1
         if lo == 1:
             need = one
-        key = (str(x.device), _stream(x))
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            self._ws.pop(key, None)
-            ws = None
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
-        return ws
+        return self._arena(x, need)
 
     def encode(self, image: torch.Tensor) -> torch.Tensor:
         """image (B, in_channels, H, W) f32 -> latent (B, latent_channels, H/f, W/f) f32 (x 0.18215)."""
@@ -982,17 +863,10 @@ def pack_conv_weight(w: torch.Tensor, dt: int, mode: int = CONV_PLAIN) -> Tuple[
     return out, cin, ntaps
 
 
-def op_conv(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
-            src2: Optional[torch.Tensor] = None, mode: int = CONV_PLAIN, rep1: int = 1, rep2: int = 1,
-            resid: Optional[torch.Tensor] = None, n_hyp: Optional[int] = None, out_nchw: bool = False,
-            out_dtype: int = F32, act_relu: bool = False, split_k: bool = False, x2_shift: int = 0) -> torch.Tensor:
-    """src* NHWC tensors of dtype dt; w torch Conv2d weight (f32).  Returns NHWC (or NCHW).  split_k: hand the launcher the scratch it
-    asks for (as the U-Net / encoder runtimes do), so shapes it would split along K (few tiles, long K) are.  x2_shift (F16X2 only): the
-    activation range shift t of the packed layer (word 3 of the pack's tail; include/nope_hip.h: full accuracy for 2^(t-4) <= |a| <= 1792 2^t)."""
+def _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k):
+    """What op_conv and op_conv_ex set up alike: the packed weight, the shapes, the output tensor, the f32 bias and -- split_k -- the scratch the
+    launcher asks for (sk bytes), under the names of the entry points' arguments."""
     pw, cin, ntaps = pack_conv_weight(w, dt, mode)
-    if x2_shift:
-        assert dt == F16X2
-        pw.view(torch.int32)[-1] = int(x2_shift)
     n1, hs, ws, c1 = src1.shape
     c2 = 0 if src2 is None else src2.shape[3]
     assert c1 + c2 == cin
@@ -1004,16 +878,30 @@ def op_conv(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
     else:
         out = torch.empty((n_hyp, ho, wo, cout), dtype=torch_dtype(dt), device=src1.device)
     b = None if bias is None else _f32c(bias)
-    l = lib()
     scratch, sk = None, 0
     if split_k:
-        sk = int(l.dll.nope_op_conv_splitk_bytes(dt, c1, c2, rep1, hs, ws, mode, ntaps, cout, n_hyp))
+        sk = int(lib().dll.nope_op_conv_splitk_bytes(dt, c1, c2, rep1, hs, ws, mode, ntaps, cout, n_hyp))
         if sk:
             scratch = torch.empty(sk, dtype=torch.uint8, device=src1.device)
-    l.check(l.dll.nope_op_conv_ws(dt, _ptr(src1), c1, rep1, _ptr(src2), c2, rep2, hs, ws, mode, ntaps, _ptr(pw), _ptr(b),
-                                  _ptr(resid), _ptr(out), cout, n_hyp, int(out_nchw), out_dtype, int(act_relu), _ptr(scratch), sk,
+    return SimpleNamespace(pw=pw, ntaps=ntaps, c1=c1, c2=c2, hs=hs, ws=ws, ho=ho, wo=wo, cout=cout, n_hyp=n_hyp, out=out, b=b, scratch=scratch, sk=sk)
+
+
+def op_conv(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
+            src2: Optional[torch.Tensor] = None, mode: int = CONV_PLAIN, rep1: int = 1, rep2: int = 1,
+            resid: Optional[torch.Tensor] = None, n_hyp: Optional[int] = None, out_nchw: bool = False,
+            out_dtype: int = F32, act_relu: bool = False, split_k: bool = False, x2_shift: int = 0) -> torch.Tensor:
+    """src* NHWC tensors of dtype dt; w torch Conv2d weight (f32).  Returns NHWC (or NCHW).  split_k: hand the launcher the scratch it
+    asks for (as the U-Net / encoder runtimes do), so shapes it would split along K (few tiles, long K) are.  x2_shift (F16X2 only): the
+    activation range shift t of the packed layer (word 3 of the pack's tail; include/nope_hip.h: full accuracy for 2^(t-4) <= |a| <= 1792 2^t)."""
+    s = _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k)
+    if x2_shift:
+        assert dt == F16X2
+        s.pw.view(torch.int32)[-1] = int(x2_shift)
+    l = lib()
+    l.check(l.dll.nope_op_conv_ws(dt, _ptr(src1), s.c1, rep1, _ptr(src2), s.c2, rep2, s.hs, s.ws, mode, s.ntaps, _ptr(s.pw), _ptr(s.b),
+                                  _ptr(resid), _ptr(s.out), s.cout, s.n_hyp, int(out_nchw), out_dtype, int(act_relu), _ptr(s.scratch), s.sk,
                                   _stream(src1)), "nope_op_conv")
-    return out
+    return s.out
 
 
 def op_group_norm(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, act_silu: bool = False,
@@ -1077,36 +965,20 @@ def op_conv_ex(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torc
         w, c0, c1 = prenorm_fold(w.cpu(), gamma.cpu(), beta.cpu(), dt)
         pn = (_f32c(ms), c0.to(src1.device), c1.to(src1.device))
         w = w.to(src1.device)
-    pw, cin, ntaps = pack_conv_weight(w, dt, mode)
-    n1, hs, ws, c1_ = src1.shape
-    c2 = 0 if src2 is None else src2.shape[3]
-    assert c1_ + c2 == cin
-    n_hyp = n_hyp if n_hyp is not None else n1 * rep1
-    ho, wo = (2 * hs, 2 * ws) if mode in (CONV_UP2, CONV_UP2P) else ((hs // 2, ws // 2) if mode in (CONV_DOWN2, CONV_STRIDE2, CONV_STRIDE2_PAD01) else (hs, ws))
-    cout = w.shape[0]
-    if out_nchw:
-        out = torch.empty((n_hyp, cout, ho, wo), dtype=torch_dtype(out_dtype), device=src1.device)
-    else:
-        out = torch.empty((n_hyp, ho, wo, cout), dtype=torch_dtype(dt), device=src1.device)
-    b = None if bias is None else _f32c(bias)
+    s = _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k)
     l = lib()
-    scratch, sk = None, 0
-    if split_k:
-        sk = int(l.dll.nope_op_conv_splitk_bytes(dt, c1_, c2, rep1, hs, ws, mode, ntaps, cout, n_hyp))
-        if sk:
-            scratch = torch.empty(sk, dtype=torch.uint8, device=src1.device)
     if colstats is not None:
         assert colstats.dtype == torch.float32 and colstats.is_contiguous()
-        assert stat_rows <= 0 or colstats.numel() >= (n_hyp * ho * wo // stat_rows) * cout * 2
+        assert stat_rows <= 0 or colstats.numel() >= (s.n_hyp * s.ho * s.wo // stat_rows) * s.cout * 2
     slot, amax = _amax_scratch(src1.device) if want_amax else (None, None)
     rec = _i(0)
-    l.check(l.dll.nope_op_conv_ex(dt, _ptr(src1), c1_, rep1, _ptr(src2), c2, rep2, hs, ws, mode, ntaps, _ptr(pw), _ptr(b),
-                                  _ptr(resid), _ptr(out), cout, n_hyp, int(out_nchw), out_dtype, int(act_relu), _ptr(scratch), sk,
+    l.check(l.dll.nope_op_conv_ex(dt, _ptr(src1), s.c1, rep1, _ptr(src2), s.c2, rep2, s.hs, s.ws, mode, s.ntaps, _ptr(s.pw), _ptr(s.b),
+                                  _ptr(resid), _ptr(s.out), s.cout, s.n_hyp, int(out_nchw), out_dtype, int(act_relu), _ptr(s.scratch), s.sk,
                                   _ptr(colstats), int(stat_rows), _ptr(pn[0]) if pn else None, _ptr(pn[1]) if pn else None,
                                   _ptr(pn[2]) if pn else None, _ptr(slot), _ptr(amax), C.byref(rec), _stream(src1)), "nope_op_conv_ex")
     if want_amax:
-        return out, float(amax.item()), bool(rec.value)
-    return out
+        return s.out, float(amax.item()), bool(rec.value)
+    return s.out
 
 
 def op_gn_apply_blocks(dt: int, hw: int, c: int, n_hyp: int) -> int:

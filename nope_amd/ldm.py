@@ -20,12 +20,10 @@ NotImplementedError -- among it `use_spatial_transformer=False`, which the refer
 """
 from __future__ import annotations
 
-from typing import Optional
-
-import torch
 from torch import nn
 
 from . import hip
+from .handle_cache import HypothesisNetwork
 from .u_net import _Params, _slot
 
 
@@ -86,7 +84,10 @@ def level_head_channels(ch, num_heads, num_head_channels, legacy):
     return dim_head
 
 
-class UNetModelPose(nn.Module):
+class UNetModelPose(HypothesisNetwork, nn.Module):
+    """adapt_openaimodel.py:14-158; `forward(x, pose)` is adapt_openaimodel.py:130-158 (-> (B,out_channels,h,w) f32), `forward_hypotheses`
+    the template loop model.py:212-222 (both, the device handle behind them and `invalidate()` in handle_cache.HypothesisNetwork)."""
+
     def __init__(self, injecting_condition_twice, pose_mlp_name, rot_representation_dim, encoder, image_size, in_channels,
                  model_channels, out_channels, num_res_blocks, attention_resolutions, dropout=0, channel_mult=(1, 2, 4, 8),
                  conv_resample=True, dims=2, num_classes=None, use_checkpoint=False, use_fp16=False, num_heads=-1,
@@ -166,58 +167,16 @@ class UNetModelPose(nn.Module):
             self._pose_layers = 2
         if self.injecting_condition_twice:                                                             # :119-123
             self.pose_mlp_timesteps = _slot(nn.Linear(rot_representation_dim, emb))
-        self._handle: Optional[hip.LdmHandle] = None
-        self._handle_key = None
-        self.register_load_state_dict_post_hook(lambda mod, _keys: mod.invalidate())
+        self._init_handle_cache()
 
-    def own_state_dict(self):
-        return {k: v for k, v in self.state_dict().items() if not k.startswith("encoder.")}
-
-    def invalidate(self):
-        self._handle = None
-        self.__dict__.pop("_own_params", None)      # the cached tensor list: parameters may have been re-assigned (load_state_dict(assign=True))
-        inv = getattr(self.encoder, "invalidate", None)
-        if callable(inv):
-            inv()
-
-    def _weights_version(self):
-        # (storage address, version counter) per tensor, as UNet._weights_version: `.data` writes need invalidate()
-        ps = self.__dict__.get("_own_params")
-        if ps is None:
-            ps = self.__dict__["_own_params"] = [p for n, p in self.named_parameters(recurse=True) if not n.startswith("encoder.")]
-        return hash(tuple((p.data_ptr(), p._version) for p in ps))
-
-    def _get_handle(self, device) -> "hip.LdmHandle":
-        key = (str(device), self.compute_dtype, self._weights_version())
-        if self._handle is None or self._handle_key != key:
-            sd = {k: v.to(device) for k, v in self.own_state_dict().items() if not k.startswith("time_embed.")}
-            levels = len(self.channel_mult)
-            cfg = dict(in_channels=self.in_channels, model_channels=self.model_channels, out_channels=self.out_channels,
-                       num_res_blocks=self.num_res_blocks, channel_mult=self.channel_mult,
-                       attn_levels=tuple(int((1 << l) in self.attention_resolutions) for l in range(levels)),
-                       num_head_channels=0, head_channels=self.head_channels, resblock_updown=int(self.resblock_updown),
-                       conv_resample=int(self.conv_resample), context_dim=self.context_dim, pose_dim=self.rot_representation_dim,
-                       pose_mlp_layers=self._pose_layers, injecting_condition_twice=int(self.injecting_condition_twice),
-                       use_scale_shift_norm=int(self.use_scale_shift_norm), transformer_depth=self.transformer_depth)
-            self._handle = hip.LdmHandle(cfg, sd, hip.dtype_code(self.compute_dtype))
-            self._handle_key = key
-        return self._handle
-
-    @torch.no_grad()
-    def forward(self, x, pose):
-        """adapt_openaimodel.py:130-158.  x (B,C,h,w), pose (B,rot_dim) -> (B,out_channels,h,w) f32."""
-        return self._get_handle(x.device).forward(x, pose, x_rep=1)
-
-    @torch.no_grad()
-    def forward_hypotheses(self, x, poses, out=None, out_dtype="f32", defer_range_check=False):
-        """x (B,C,h,w) reference latents, poses (B,N,rot_dim) -> (B,N,C,h,w): the body of the template loop model.py:212-222.
-        defer_range_check (f16x2): the caller calls finish_range_check() before it reads the output (as nope_amd.UNet)."""
-        B, N = poses.shape[:2]
-        flat = poses.reshape(B * N, poses.shape[-1])
-        o = None if out is None else out.view(B * N, *out.shape[2:])
-        y = self._get_handle(x.device).forward(x, flat, x_rep=N, out=o, out_dtype=hip.dtype_code(out_dtype), defer_range_check=defer_range_check)
-        return y.view(B, N, *y.shape[1:])
-
-    def finish_range_check(self) -> bool:
-        """f16x2: check (and if needed repeat) the forwards issued with defer_range_check; True when any was repeated (hip.LdmHandle)."""
-        return self._handle.finish_range_check() if self._handle is not None else False
+    def _make_handle(self, device):
+        sd = {k: v.to(device) for k, v in self.own_state_dict().items() if not k.startswith("time_embed.")}
+        levels = len(self.channel_mult)
+        cfg = dict(in_channels=self.in_channels, model_channels=self.model_channels, out_channels=self.out_channels,
+                   num_res_blocks=self.num_res_blocks, channel_mult=self.channel_mult,
+                   attn_levels=tuple(int((1 << l) in self.attention_resolutions) for l in range(levels)),
+                   num_head_channels=0, head_channels=self.head_channels, resblock_updown=int(self.resblock_updown),
+                   conv_resample=int(self.conv_resample), context_dim=self.context_dim, pose_dim=self.rot_representation_dim,
+                   pose_mlp_layers=self._pose_layers, injecting_condition_twice=int(self.injecting_condition_twice),
+                   use_scale_shift_norm=int(self.use_scale_shift_norm), transformer_depth=self.transformer_depth)
+        return hip.LdmHandle(cfg, sd, hip.dtype_code(self.compute_dtype))

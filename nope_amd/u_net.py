@@ -14,12 +14,10 @@ N pose hypotheses per reference embedding in one launch sequence.
 """
 from __future__ import annotations
 
-from typing import Optional
-
-import torch
 from torch import nn
 
 from . import hip
+from .handle_cache import HypothesisNetwork
 
 _HIDDEN = 4 * 32   # attention heads x dim_head (model_utils.py:368,394)
 
@@ -69,7 +67,10 @@ def _attention_params(dim, linear):
     return res
 
 
-class UNet(nn.Module):
+class UNet(HypothesisNetwork, nn.Module):
+    """u_net.py:26-198; `forward(x, pose)` is u_net.py:160-198, `forward_hypotheses` the template loop model.py:212-222 (both, the
+    device handle behind them and `invalidate()` in handle_cache.HypothesisNetwork)."""
+
     def __init__(self, u_net_dim, rot_representation_dim, encoder, pose_mlp_name, init_dim=None, out_dim=None,
                  use_hard_up_down=True, dim_mults=(1, 2, 4, 8), resnet_block_groups=8, compute_dtype="f32", **kwargs):
         super().__init__()
@@ -128,66 +129,12 @@ class UNet(nn.Module):
                                                   else nn.ConvTranspose2d(cout, cin, 4, 2, 1))]))                   # model_utils.py:119-126
         self.final_res_block = _resnet_params(2 * u_net_dim, u_net_dim, emb, g)
         self.final_conv = _slot(_resnet_params(u_net_dim, u_net_dim, emb, g), _conv(u_net_dim, self.channels, 1))
-        self._handle: Optional[hip.UNetHandle] = None
-        self._handle_key = None
-        # nn.Module.load_state_dict on a PARENT never calls a child's load_state_dict (it recurses through
-        # _load_from_state_dict), but it does run every sub-module's post hooks: drop the repacked device copy there.
-        self.register_load_state_dict_post_hook(lambda mod, _keys: mod.invalidate())
+        self._init_handle_cache()
 
-    # -- device handle ------------------------------------------------------------------
-    def own_state_dict(self):
-        """The U-Net's own tensors (no `encoder.*`), keyed as in the reference."""
-        return {k: v for k, v in self.state_dict().items() if not k.startswith("encoder.")}
-
-    def invalidate(self):
-        """Drop the repacked device weights (also the encoder's); the next forward repacks them.  Called
-        automatically after any load_state_dict that reaches this module and when a parameter was modified in place."""
-        self._handle = None
-        self.__dict__.pop("_own_params", None)      # the cached tensor list: parameters may have been re-assigned (load_state_dict(assign=True))
-        inv = getattr(self.encoder, "invalidate", None)
-        if callable(inv):
-            inv()
-
-    def _weights_version(self):
-        """Key of the repacked device copy: (storage address, version counter) of every tensor of the U-Net.  In-place writes through
-        the tensor itself (optimizer steps, `p.copy_`, `p.mul_`) bump `_version`, re-assigned storage moves `data_ptr`; writes
-        through `p.data` have their own counter and are NOT seen -- call `invalidate()` after those (EMA swaps, hand-written
-        checkpoint loaders); `load_state_dict` on this module or any parent invalidates by itself.  The parameter list is
-        cached (the module tree is fixed after __init__), so a forward pays ~40 us for the ~420 tensors, not a named_parameters walk."""
-        ps = self.__dict__.get("_own_params")
-        if ps is None:
-            ps = self.__dict__["_own_params"] = [p for n, p in self.named_parameters(recurse=True) if not n.startswith("encoder.")]
-        return hash(tuple((p.data_ptr(), p._version) for p in ps))
-
-    def _get_handle(self, device) -> hip.UNetHandle:
-        key = (str(device), self.compute_dtype, self._weights_version())
-        if self._handle is None or self._handle_key != key:
-            sd = {k: v.to(device) for k, v in self.own_state_dict().items()}
-            # (the reference stores `out_dim` but builds final_conv.1 with `channels` outputs, u_net.py:154-157)
-            cfg = dict(u_net_dim=self.u_net_dim, channels=self.channels, out_dim=self.channels,
-                       pose_dim=self.rot_representation_dim, dim_mults=self.dim_mults, groups=self.groups,
-                       pose_mlp_layers=self._pose_layers, soft_up_down=int(not self.use_hard_up_down))
-            self._handle = hip.UNetHandle(cfg, sd, hip.dtype_code(self.compute_dtype))
-            self._handle_key = key
-        return self._handle
-
-    # -- reference call surface ---------------------------------------------------------
-    @torch.no_grad()
-    def forward(self, x, pose):
-        """u_net.py:160-198.  x (B,C,h,w), pose (B,rot_dim) -> (B,C,h,w) f32."""
-        return self._get_handle(x.device).forward(x, pose, x_rep=1)
-
-    @torch.no_grad()
-    def forward_hypotheses(self, x, poses, out=None, out_dtype="f32", defer_range_check=False):
-        """x (B,C,h,w) reference embeddings, poses (B,N,rot_dim) -> (B,N,C,h,w):
-        UNet(x[b], poses[b,n]) for every (b,n) -- the body of the template loop
-        model.py:212-222 -- as one batched launch sequence."""
-        B, N = poses.shape[:2]
-        flat = poses.reshape(B * N, poses.shape[-1])
-        o = None if out is None else out.view(B * N, *out.shape[2:])
-        y = self._get_handle(x.device).forward(x, flat, x_rep=N, out=o, out_dtype=hip.dtype_code(out_dtype), defer_range_check=defer_range_check)
-        return y.view(B, N, *y.shape[1:])
-
-    def finish_range_check(self) -> bool:
-        """f16x2: check (and if needed repeat) the forwards issued with defer_range_check; True when any was repeated (hip.UNetHandle)."""
-        return self._handle.finish_range_check() if self._handle is not None else False
+    def _make_handle(self, device):
+        sd = {k: v.to(device) for k, v in self.own_state_dict().items()}
+        # (the reference stores `out_dim` but builds final_conv.1 with `channels` outputs, u_net.py:154-157)
+        cfg = dict(u_net_dim=self.u_net_dim, channels=self.channels, out_dim=self.channels,
+                   pose_dim=self.rot_representation_dim, dim_mults=self.dim_mults, groups=self.groups,
+                   pose_mlp_layers=self._pose_layers, soft_up_down=int(not self.use_hard_up_down))
+        return hip.UNetHandle(cfg, sd, hip.dtype_code(self.compute_dtype))

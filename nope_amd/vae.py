@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from . import hip
+from .handle_cache import HandleCache
 from .weights import synth_tensor
 
 SD15_CONFIG = dict(in_channels=3, out_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4,
@@ -167,7 +168,9 @@ def convert_state_dict(sd: dict) -> dict:
     return out
 
 
-class VAE_StableDiffusion(nn.Module):
+class VAE_StableDiffusion(HandleCache, nn.Module):
+    _cache_versioned_tensors = False     # (the parameters of `encoder` are walked at every call)
+
     def __init__(self, pretrained_path, latent_dim=4, name="vae", using_KL=False, compute_dtype="f32", config: Optional[dict] = None,
                  max_workspace_bytes: int = 4 << 30, **kwargs):
         super().__init__()
@@ -179,8 +182,6 @@ class VAE_StableDiffusion(nn.Module):
         self.config = check_config(config)
         self.compute_dtype = compute_dtype
         self.max_workspace_bytes = int(max_workspace_bytes)
-        self._handle = None
-        self._handle_key = None
         self.encoder = AutoencoderKLParams(self.config)
         if pretrained_path is not None:
             sd = torch.load(os.path.join(pretrained_path, "diffusion_pytorch_model.bin"), map_location="cpu")
@@ -190,12 +191,7 @@ class VAE_StableDiffusion(nn.Module):
         self.using_KL = using_KL
         self.encode_mode = None if using_KL else "mode"
         self.eval()
-        # runs for a load_state_dict on this module or on any parent (UNet, PoseConditional, a Lightning module)
-        self.register_load_state_dict_post_hook(lambda mod, _keys: mod.invalidate())
-
-    def invalidate(self):
-        """Drop the packed device weights; the next device call rebuilds them."""
-        self._handle = None
+        self._init_handle_cache()
 
     @torch.no_grad()
     def synth_init_(self, seed: int):
@@ -205,16 +201,15 @@ class VAE_StableDiffusion(nn.Module):
         self.invalidate()
         return self
 
-    def _weights_version(self):
-        return hash(tuple((t.data_ptr(), t._version) for t in self.encoder.parameters()))
+    def _versioned_tensors(self):
+        return self.encoder.parameters()
 
-    def _get_handle(self, device) -> "hip.VaeHandle":
-        key = (str(device), self.compute_dtype, self.max_workspace_bytes, self._weights_version())
-        if self._handle is None or self._handle_key != key:
-            sd = {k: v.to(device) for k, v in self.encoder.state_dict().items()}
-            self._handle = hip.VaeHandle(self.config, sd, hip.dtype_code(self.compute_dtype), max_workspace_bytes=self.max_workspace_bytes)
-            self._handle_key = key
-        return self._handle
+    def _handle_key_extra(self):
+        return (self.max_workspace_bytes,)
+
+    def _make_handle(self, device):
+        sd = {k: v.to(device) for k, v in self.encoder.state_dict().items()}
+        return hip.VaeHandle(self.config, sd, hip.dtype_code(self.compute_dtype), max_workspace_bytes=self.max_workspace_bytes)
 
     @torch.no_grad()
     def encode_image(self, image, mode=None):
