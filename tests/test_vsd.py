@@ -1,7 +1,16 @@
 """VSD evaluation (nope_amd/vsd.py, nope_op_render_depth / nope_op_vsd, PoseConditional.eval_vsd / load_mesh / test_step).
 
 The VSD arithmetic is pinned to the reference's own vsd_obj (tests/golden/make_golden_vsd.py -> vsd_ref.npz); the rasteriser, which has
-no runnable counterpart here (pyrender is not installed), to analytic depths and to a numpy restatement with the same sampling rule."""
+no runnable counterpart here (pyrender is not installed), to analytic depths and to a numpy restatement with the same sampling rule.
+
+This file runs one shape family: k = 4 or 5 (vsd_kernel<5, 4>, 16-byte aligned images with H W % 4 == 0), images at most 96 rows high,
+meshes whose listed triangles fit one trip of raster_big_kernel's loops.  tests/test_vsd_paths.py, which imports the helpers below,
+reaches the rest on the interpreter and on the device: vsd_kernel<1, .>, <5, .> with the `j >= k` skip, <16, .>; vsd_kernel<., 1> for
+H W % 4 != 0 and for a depth pointer at 4 mod 16; fewer pixels than one workgroup has threads; empty inputs, one K, B = 1;
+raster_big_kernel's second trips of `yb += 16 * gridDim.y` (a box more than 128 rows high) and `e += gridDim.x` (more than 256 listed
+triangles) and its list at the capacity P * max_faces; the kSmallArea boundary (64 / 65 pixels); `fl >= cnt` with cnt < max_faces over
+several blockIdx.x; the pixel box clamped at each border alone, triangles outside, sub-pixel, degenerate and beyond zfar; the exact
+skipped count; the launchers' argument checks and (interpreter only) their index and range guards; vsd_error at k = 1 and k = 7."""
 import os
 
 import numpy as np
