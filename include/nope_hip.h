@@ -82,9 +82,10 @@ typedef void* nope_stream_t;
  * 9: nope_op_render_depth, nope_op_vsd, NOPE_VSD_* / NOPE_VISIB_*;
  * 10: nope_gd_config, nope_gd_*;
  * 11: nope_op_conv_stat_rows, nope_op_conv_ex, nope_op_group_norm_ex, nope_op_gn_apply_blocks, nope_op_gn_finalize, nope_op_absmax_f32,
- *     nope_op_amax_slot_words -- the fused GroupNorm statistics / PreNorm / range-slot plumbing at operator level).  Callers compare nope_abi_version() against the header they were
+ *     nope_op_amax_slot_words -- the fused GroupNorm statistics / PreNorm / range-slot plumbing at operator level;
+ * 12: nope_vis_column, nope_op_vis_grid, nope_op_vis_sheet, NOPE_VIS_*).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 11
+#define NOPE_ABI_VERSION 12
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -170,6 +171,47 @@ size_t nope_op_vsd_workspace_bytes(int B, int k, int H, int W);
 int nope_op_vsd(const float* depth_test, const float* depth_gt, const float* depth_est, const double* K, int B, int k, int H, int W,
                 double delta, double tau, int cost_type, int visib_mode, double* err, void* workspace, size_t workspace_bytes,
                 nope_stream_t stream);
+
+/* (ABI 12) Visualisation pictures: the contact sheets PoseConditional saves as PNGs and the `vis_imgs` grid of its predictions file.
+ * A picture is n_cols (1 .. NOPE_VIS_MAX_COLS) columns; a column is one stack of f32 NCHW images, read where it lies -- nothing is copied
+ * or repeated on the host.  `cols` is a HOST array (it travels as kernel arguments); the pointers inside it are device pointers. */
+enum { NOPE_VIS_MAX_COLS = 8 };
+enum { NOPE_VIS_UNNORMALIZE = 1, /* (x + 1) * 0.5 first, in f32 */
+       NOPE_VIS_CLAMP = 2        /* then clamp to [0, 1]; both = unnormalize_to_zero_to_one, src/model/utils.py:12-15 */ };
+typedef struct {
+    const float* data;      /* (..., 3, H, W) f32 planes: sample b of frame f at data + b * stride_b + f * stride_f */
+    int64_t stride_b;       /* elements between samples b */
+    int64_t stride_f;       /* elements between frames f; 0 = the same images in every frame */
+    const int64_t* index;   /* NULL, or device indices: sample b of every frame reads frame index[b * index_stride]
+                               (gt_templates[b, nearest_idx[b, 0]], src/model/model.py:331-333) */
+    int64_t index_stride;
+    int64_t index_limit;    /* indices are clamped into [0, index_limit) on the device: a bad index never reads out of bounds */
+    int flags;              /* NOPE_VIS_UNNORMALIZE | NOPE_VIS_CLAMP */
+} nope_vis_column;
+
+/* The full-size f16 grid with its margin column.  Replaces put_image_to_grid(list_imgs, adding_margin=True),
+ * src/utils/visualization_utils.py:43-57 (and the unnormalize_to_zero_to_one calls on its inputs, src/model/model.py:215-218,292-296,
+ * 334-338), for F pictures in one launch.
+ *   grid_f16  (F, B * (n_cols + 1), 3, H, W) f16: image b * (n_cols + 1) + i is column i of sample b, image b * (n_cols + 1) + n_cols is
+ *             zero.  The flags run in f32, then ONE round-to-nearest-even cast to f16.
+ * 1 <= n_cols <= 8; B, H, W > 0; B * (n_cols + 1) <= 65535; 0 <= F <= 65535, F = 0 is a no-op that succeeds; non-null pointers when F > 0;
+ * index_limit >= 1 wherever index is set: otherwise NOPE_ERR_ARG, and nothing is launched. */
+int nope_op_vis_grid(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, void* grid_f16, nope_stream_t stream);
+
+/* The bytes of the PNG.  Replaces, per picture, put_image_to_grid + clone + F.interpolate(grid, (tile, tile), mode="bilinear",
+ * align_corners=False) + torchvision.utils.save_image(grid, path, nrow=nrow) up to the file encoder (src/model/model.py:231-240,297-306,
+ * 339-348; the reference: tile 64, nrow 4 * (n_cols + 1), padding 2), for F pictures in one launch; frames are independent.
+ *   sheet_u8  (F, Hs, Ws, 3) u8, HWC, any byte alignment.  n_img = B * (n_cols + 1), xmaps = min(nrow, n_img), ymaps = ceil(n_img / xmaps),
+ *             Hs = (tile + padding) * ymaps + padding, Ws = (tile + padding) * xmaps + padding (make_grid); image k has its corner at
+ *             ((k / xmaps) * (tile + padding) + padding, (k % xmaps) * (tile + padding) + padding); padding, margin images and the empty
+ *             slots of a ragged last row are 0.
+ * Per byte, in the arithmetic the reference's f16 grid goes through: column flags in f32 -> f16; bilinear resample (scale = (float)H / tile,
+ * src = max(scale * (o + 0.5f) - 0.5f, 0), i0 = min((int)src, H - 1), i1 = min(i0 + 1, H - 1), l1 = src - i0, l0 = 1 - l1; H and W
+ * independently) as l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d) in f32 on the four f16 taps -> f16; save_image's
+ * mul(255).add_(0.5).clamp_(0, 255).to(uint8) with an f16 rounding after the product and after the sum.
+ * Checks as nope_op_vis_grid (n_img is not limited to 65535 here), and tile, nrow > 0, padding >= 0, Hs <= 65535. */
+int nope_op_vis_sheet(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, int tile, int nrow, int padding,
+                      void* sheet_u8, nope_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Pose-conditioned U-Net.  Replaces UNet.__init__/forward,

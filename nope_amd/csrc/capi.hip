@@ -87,6 +87,15 @@ int nope_op_vsd(const float* depth_test, const float* depth_gt, const float* dep
                       (hipStream_t)stream);
 }
 
+int nope_op_vis_grid(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, void* grid_f16, nope_stream_t stream) {
+    return launch_vis_grid(cols, n_cols, B, F, H, W, static_cast<f16_t*>(grid_f16), (hipStream_t)stream);
+}
+
+int nope_op_vis_sheet(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, int tile, int nrow, int padding,
+                      void* sheet_u8, nope_stream_t stream) {
+    return launch_vis_sheet(cols, n_cols, B, F, H, W, tile, nrow, padding, static_cast<unsigned char*>(sheet_u8), (hipStream_t)stream);
+}
+
 int nope_op_nchw_to_nhwc(int dtype, const float* x, void* y, int n, int C, int HW, nope_stream_t s) {
     return launch_nchw_to_nhwc(dtype, x, y, n, C, HW, (hipStream_t)s);
 }

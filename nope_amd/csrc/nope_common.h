@@ -473,5 +473,8 @@ int launch_render_depth(const float* verts, int V, const int* faces, int F, cons
 size_t vsd_workspace_bytes(int B, int k, int H, int W);
 int launch_vsd(const float* dtest, const float* dgt, const float* dest, const double* K, int B, int k, int H, int W, double delta, double tau,
                int cost_type, int visib_mode, double* err, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_vis_grid(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, f16_t* grid, hipStream_t s);
+int launch_vis_sheet(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, int tile, int nrow, int padding,
+                     unsigned char* sheet, hipStream_t s);
 
 }  // namespace nope

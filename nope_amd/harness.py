@@ -8,8 +8,9 @@ like `ShapeNet.__getitem__` on the test split (src/dataloader/shapeNet.py:348-35
 then the geodesic angle / Acc@{15,30} (loss.py:76-115; non-symmetric branch only).  There is
 no dataset and no checkpoint in the tree or on the box, so images, poses and weights are
 synthetic and seeded; the numbers are plumbing checks, not accuracy claims.  It does not
-replicate the reference's `vis_imgs` UnboundLocalError (model.py:367): predictions are saved
-with `query_pose` and `similarity` only.
+replicate the reference's `vis_imgs` UnboundLocalError (model.py:367): without visualisation
+predictions are saved with `query_pose` and `similarity` only; with it (`--visualize`, the VAE
+encoder and `--save-dir`) the pictures, the video and `vis_imgs` are written (nope_amd/vis.py).
 
     python -m nope_amd.harness --batch 1 --templates 64 --size 128     # BASELINE config 1 shape
 """
@@ -23,6 +24,8 @@ from typing import Dict, Optional
 
 import numpy as np
 import torch
+
+from . import hip
 
 TEMPLATE_BASE = dict(          # configs/model/template_base.yaml
     u_net=dict(u_net_dim=192, rot_representation_dim=6, pose_mlp_name="single_layer",
@@ -63,11 +66,12 @@ def rotation_6d(m: torch.Tensor) -> torch.Tensor:
 
 
 def synthetic_batch(batch: int, n_templates: int, size: int, seed: int = 2022, device="cpu",
-                    pose_level: Optional[int] = None, pose_root: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                    pose_level: Optional[int] = None, pose_root: Optional[str] = None, gt_templates: bool = False) -> Dict[str, torch.Tensor]:
     """A test-split batch shaped like ShapeNet.__getitem__ (dataloader/shapeNet.py:348-357).  Template poses are
     Haar-random rotations, or -- `pose_level` 0..3 -- the upper-hemisphere icosphere grid the reference evaluates on
     (nope_amd.poses: 26 / 91 / 341 / 1321 viewpoints; `pose_root` = the reference's predefined_poses directory to
-    read its own files); `n_templates` is ignored then."""
+    read its own files); `n_templates` is ignored then.  gt_templates: add the (B, N, 3, size, size) ground-truth template images that the
+    visualisation shows (shapeNet.py:352; drawn last, the other tensors do not change)."""
     g = torch.Generator().manual_seed(seed)
     query = torch.rand(batch, 3, size, size, generator=g) * 2 - 1
     reference = torch.rand(batch, 3, size, size, generator=g) * 2 - 1
@@ -86,6 +90,8 @@ def synthetic_batch(batch: int, n_templates: int, size: int, seed: int = 2022, d
     out = dict(query=query, reference=reference, gt_relativeR=gt_rel, all_relativeR=all_rel,
                symmetry=torch.zeros(batch, 1), query_pose=R_query,
                template_poses=R_tpl[None].expand(batch, -1, -1, -1).contiguous())
+    if gt_templates:
+        out["gt_templates"] = torch.rand(batch, n_templates, 3, size, size, generator=g) * 2 - 1
     return {k: v.to(device) for k, v in out.items()}
 
 
@@ -129,10 +135,30 @@ def geodesic_deg(predR: torch.Tensor, gtR: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None):
-    """The body of PoseConditional.eval_geodesic (model.py:268-376) without visualisation."""
-    loss = model.forward(batch["query"], batch["reference"], batch["gt_relativeR"])
-    similarity, nearest_idx, _ = model.generate_and_retrieve(batch["query"], batch["reference"], batch["all_relativeR"])
+def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False):
+    """The body of PoseConditional.eval_geodesic (model.py:268-376).  visualize (effective with a decoding encoder and model.save_dir only,
+    model.py:269-274; needs batch["gt_templates"] (B, N, 3, S, S)): the three kinds of pictures and the video under save_dir/media
+    (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions."""
+    visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
+    if visualize and "gt_templates" not in batch:
+        raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
+                         "the template and retrieved pictures show them (model.py:217,331-333)")
+    query, reference = batch["query"], batch["reference"]
+    loss = model.forward(query, reference, batch["gt_relativeR"])
+    if not visualize:
+        similarity, nearest_idx, _ = model.generate_and_retrieve(query, reference, batch["all_relativeR"])
+    else:
+        from . import vis
+        media, tag = os.path.join(model.save_dir, "media"), f"step{model.global_step}_rank{model.global_rank}"
+        # the reconstruction under the ground-truth pose (model.py:284-306)
+        _, pred_rgb = model.sample(reference=reference, relativeR=batch["gt_relativeR"])
+        vis.save_png(vis.contact_sheet(vis.triptych(reference, query, pred_rgb, third_unnormalize=False))[0], os.path.join(media, f"reconst_{tag}.png"))
+        # the bank has to be decoded: generate_templates + retrieval, the two calls generate_and_retrieve fuses (same arithmetic, same bits)
+        bank, _, _ = model.generate_templates(reference=reference, all_relativeR=batch["all_relativeR"], gt_templates=batch["gt_templates"], visualize=True)
+        similarity, nearest_idx = model.retrieval(query=query, template_feat=bank)
+        # gt_templates[b, nearest_idx[b, 0]] (model.py:331-338): gathered by the kernel through the index, no look at it on the host
+        retrieved = vis.triptych(reference, query, batch["gt_templates"], third_unnormalize=True, index=nearest_idx[:, 0])
+        vis.save_png(vis.contact_sheet(retrieved)[0], os.path.join(media, f"retrieved_{tag}.png"))
     sym = batch.get("symmetry", torch.zeros(nearest_idx.shape[0], 1, dtype=torch.long, device=nearest_idx.device))
     # pred_R = template_poses[0][nearest_idx] -> GeodesicError (model.py:352-358, loss.py:78-115): gather + angle + symmetry branches as
     # one device launch (nope_op_geodesic); the grid of the first sample serves every query, as model.py:352 indexes it
@@ -140,7 +166,10 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     res = {"loss": float(loss)}
     res.update({k: float(v) for k, v in metric.items()})
     if save_path:
-        np.savez(save_path, query_pose=batch["query_pose"].cpu().numpy(), similarity=similarity.cpu().numpy())
+        extra = {}
+        if visualize:       # model.py:334-339,367-375: the un-resized grid of the last picture
+            extra["vis_imgs"] = hip.op_vis_grid(retrieved)[0].cpu().numpy()
+        np.savez(save_path, **extra, query_pose=batch["query_pose"].cpu().numpy(), similarity=similarity.cpu().numpy())
     return similarity, nearest_idx, res
 
 
@@ -159,16 +188,20 @@ def main(argv=None):
     ap.add_argument("--pose-root", default=None, help="directory with the reference's predefined_poses/*.npy")
     ap.add_argument("--encoder", default="template", choices=["template", "vae"],
                     help="vae: the Stable Diffusion VAE at the SD-1.5 shapes (synthetic weights) in place of the template encoder")
+    ap.add_argument("--visualize", action="store_true",
+                    help="with --encoder vae and --save-dir: write the reconstruction / template / retrieved pictures, the video and vis_imgs")
     a = ap.parse_args(argv)
+    if a.visualize and (a.encoder != "vae" or not a.save_dir):
+        ap.error("--visualize needs --encoder vae (the template encoder decodes nothing, model.py:269-274) and --save-dir")
     if not torch.cuda.is_available():
         raise SystemExit("nope_amd.harness needs an MI355X (no CPU fallback)")
     model = build_model(a.seed, a.dtype, a.bank_dtype, "cuda", save_dir=a.save_dir, encoder=a.encoder)
     batches = {f"shapeNet_{a.category}": synthetic_batch(a.batch, a.templates, a.size, a.seed, "cuda", pose_level=a.pose_level,
-                                                                  pose_root=a.pose_root)}
+                                                                  pose_root=a.pose_root, gt_templates=a.visualize)}
     for name, batch in batches.items():                         # test_step, model.py:550-565
         t0 = time.time()
         save = os.path.join(a.save_dir, "predictions", f"pred_step0_rank{model.global_rank}") if a.save_dir else None
-        sim, idx, res = eval_geodesic(model, batch, save_path=save)
+        sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize)
         torch.cuda.synchronize()
         res.update(dataloader=name, seconds=time.time() - t0, nearest_idx=idx.tolist())
         print(json.dumps(res))

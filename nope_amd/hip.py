@@ -15,7 +15,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 11                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 12                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -67,6 +67,14 @@ class EncoderConfig(C.Structure):
     _fields_ = [("descriptor_size", _i), ("compute_dtype", _i), ("bn_eps", C.c_float)]
 
 
+class VisColumn(C.Structure):
+    """nope_vis_column: one column of a picture, a stack of f32 NCHW images read in place."""
+    _fields_ = [("data", _vp), ("stride_b", _i64), ("stride_f", _i64), ("index", _vp), ("index_stride", _i64), ("index_limit", _i64), ("flags", _i)]
+
+
+VIS_UNNORMALIZE, VIS_CLAMP, VIS_MAX_COLS = 1, 2, 8
+
+
 _PROTOS = {
     "nope_strerror": (C.c_char_p, [_i]),
     "nope_abi_version": (_i, []),
@@ -80,6 +88,8 @@ _PROTOS = {
     "nope_op_render_depth": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "nope_op_vsd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nope_op_vsd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i, _vp, _vp, _sz, _vp]),
+    "nope_op_vis_grid": (_i, [C.POINTER(VisColumn), _i, _i, _i, _i, _i, _vp, _vp]),
+    "nope_op_vis_sheet": (_i, [C.POINTER(VisColumn), _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "nope_unet_graph_limit": (_i, [_vp, C.c_longlong]),
     "nope_unet_graph_replays": (_i, [_vp]),
     "nope_unet_x2_shifts": (_i, [_vp, C.POINTER(_i), _i, C.POINTER(_i)]),
@@ -388,6 +398,100 @@ def op_geodesic(poses: torch.Tensor, gt: torch.Tensor, symmetry: Optional[torch.
     if st & 1:
         raise ValueError("A matrix has trace outside valid range [-1-eps,3+eps].")      # pytorch3d so3_rotation_angle's message
     return err
+
+
+# --------------------------------------------------------------------------------------------
+# visualisation pictures (nope_amd/vis.py)
+# --------------------------------------------------------------------------------------------
+class VisCol:
+    """One column of a picture for op_vis_grid / op_vis_sheet: `tensor` (B, 3, H, W) -- the same images in every frame -- or (B, F, 3, H, W)
+    f32, any strides over B and F (a slice of the template axis is read in place; the (3, H, W) planes are contiguous); `unnormalize`:
+    (x + 1) * 0.5 first; `clamp`: clamp to [0, 1]; `index` (B,) int64 on the tensor's device, any stride (nearest_idx[:, 0]): sample b of
+    every frame shows tensor[b, index[b]], the index clamped into the tensor's frame axis on the device."""
+
+    def __init__(self, tensor: torch.Tensor, unnormalize: bool = False, clamp: bool = False, index: Optional[torch.Tensor] = None):
+        if tensor.dim() not in (4, 5) or tensor.shape[-3] != 3:
+            raise NopeError(f"picture column {tuple(tensor.shape)}: expected (B, 3, H, W) or (B, F, 3, H, W)")
+        if index is not None and (tensor.dim() != 5 or index.dim() != 1 or index.shape[0] != tensor.shape[0] or index.dtype != torch.int64
+                                  or index.device != tensor.device):
+            raise NopeError("picture column index: expected (B,) int64 on the device of a (B, N, 3, H, W) tensor")
+        if tensor.dtype != torch.float32:
+            tensor = tensor.float()
+        H, W = tensor.shape[-2:]
+        if tensor.numel() and tuple(tensor.stride()[-3:]) != (H * W, W, 1):
+            tensor = tensor.contiguous()
+        self.tensor, self.index = tensor, index
+        self.flags = (VIS_UNNORMALIZE if unnormalize else 0) | (VIS_CLAMP if clamp else 0)
+        self.frames = tensor.shape[1] if tensor.dim() == 5 and index is None else None      # None: the same images in every frame
+
+    def desc(self, frame0: int = 0) -> VisColumn:
+        t = self.tensor
+        c = VisColumn(data=t.data_ptr(), stride_b=t.stride(0), stride_f=0, index=None, index_stride=0, index_limit=0, flags=self.flags)
+        if t.dim() == 5:
+            c.stride_f = t.stride(1)
+            if self.index is not None:
+                c.index, c.index_stride, c.index_limit = self.index.data_ptr(), self.index.stride(0), t.shape[1]
+            else:
+                c.data = t.data_ptr() + 4 * frame0 * t.stride(1)
+        return c
+
+
+def _vis_setup(columns, frame0, n_frames):
+    if not columns:
+        raise NopeError("a picture needs at least one column")
+    columns = [c if isinstance(c, VisCol) else VisCol(*c) if isinstance(c, (tuple, list)) else VisCol(c) for c in columns]
+    t0 = columns[0].tensor
+    require_device(t0)
+    B, (H, W) = t0.shape[0], t0.shape[-2:]
+    counts = {c.frames for c in columns if c.frames is not None}
+    if len(counts) > 1:
+        raise NopeError(f"picture columns disagree on the number of frames: {sorted(counts)}")
+    if counts:
+        F = counts.pop()
+    else:           # no column has a frame axis: every frame shows the same images, as many as the caller asks for
+        F = 1 if n_frames is None else frame0 + n_frames
+    for c in columns:
+        if c.tensor.shape[0] != B or tuple(c.tensor.shape[-2:]) != (H, W) or c.tensor.device != t0.device:
+            raise NopeError(f"picture columns disagree: {tuple(c.tensor.shape)} against {tuple(t0.shape)}")
+    if n_frames is None:
+        n_frames = F - frame0
+    if frame0 < 0 or n_frames < 0 or frame0 + n_frames > F:
+        raise NopeError(f"frames [{frame0}, {frame0 + n_frames}) of {F}")
+    descs = (VisColumn * len(columns))(*[c.desc(frame0) for c in columns])
+    return columns, descs, B, n_frames, H, W, t0
+
+
+def op_vis_grid(columns, frame0: int = 0, n_frames: Optional[int] = None) -> torch.Tensor:
+    """put_image_to_grid (visualization_utils.py:43-57) of n_frames pictures: (n_frames, B * (n_cols + 1), 3, H, W) f16 with the zero margin
+    column.  columns: VisCol, or (tensor, unnormalize, clamp, index) tuples, or plain tensors."""
+    columns, descs, B, nf, H, W, t0 = _vis_setup(columns, frame0, n_frames)
+    out = torch.empty((nf, B * (len(columns) + 1), 3, H, W), dtype=torch.float16, device=t0.device)
+    l = lib()
+    l.check(l.dll.nope_op_vis_grid(descs, len(columns), B, nf, H, W, _ptr(out), _stream(t0)), "nope_op_vis_grid")
+    return out
+
+
+def vis_sheet_shape(n_cols: int, B: int, tile: int, nrow: int, padding: int) -> Tuple[int, int]:
+    """(Hs, Ws) of make_grid(nrow, padding) over B * (n_cols + 1) images of tile x tile."""
+    n_img = B * (n_cols + 1)
+    xmaps = max(1, min(nrow, n_img))
+    ymaps = -(-n_img // xmaps)
+    return (tile + padding) * ymaps + padding, (tile + padding) * xmaps + padding
+
+
+def op_vis_sheet(columns, tile: int = 64, nrow: int = 16, padding: int = 2, frame0: int = 0, n_frames: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The PNG bytes of n_frames pictures, (n_frames, Hs, Ws, 3) u8 (nope_op_vis_sheet); `out`: a contiguous u8 tensor of that shape to
+    write into (a slice of a larger sheet stack: any byte offset)."""
+    columns, descs, B, nf, H, W, t0 = _vis_setup(columns, frame0, n_frames)
+    Hs, Ws = vis_sheet_shape(len(columns), B, max(int(tile), 0), int(nrow), max(int(padding), 0))
+    if out is None:
+        out = torch.empty((nf, Hs, Ws, 3), dtype=torch.uint8, device=t0.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (nf, Hs, Ws, 3) or not out.is_contiguous() or out.device != t0.device:
+        raise NopeError(f"sheet output {tuple(out.shape)} {out.dtype}: expected contiguous uint8 {(nf, Hs, Ws, 3)}")
+    l = lib()
+    l.check(l.dll.nope_op_vis_sheet(descs, len(columns), B, nf, H, W, tile, nrow, padding, _ptr(out), _stream(t0)), "nope_op_vis_sheet")
+    return out
 
 
 def _tensor_descs(state_dict: Dict[str, torch.Tensor]):

@@ -11,7 +11,8 @@ Differences in *schedule*, none in arithmetic:
     unspecified; SURVEY.md §8 c3);
   * with `template_parallel=True` under torch.distributed each rank generates and scores only
     its slice of the template axis and the scores are all-gathered (nope_amd/dist.py).
-Lightning-specific members (optimizers, wandb logging, visualisation) are out of scope and are not provided.
+Lightning-specific members (optimizers, wandb logging) are out of scope and are not provided; the visualisation outputs
+(PNG contact sheets, video, `vis_imgs`) are written by nope_amd/vis.py.
 The evaluation entry points -- `eval_geodesic`, `eval_vsd` (T-LESS, on the device: nope_amd/vsd.py), `load_mesh`,
 `validation_step`, `test_step` -- return their scores instead of logging them.
 """
@@ -105,9 +106,15 @@ class PoseConditional(nn.Module):
     @torch.no_grad()
     def generate_templates(self, reference, all_relativeR, gt_templates=None, visualize=False):
         """reference (B,3,S,S); all_relativeR (B,N,6) -> (pred_feat_templates (B,N',C,S/8,S/8),
-        pred_templates, None).  N' = N, or this rank's slice of N under `template_parallel`.  pred_templates: with an encoder that has
+        pred_templates, vid_path).  N' = N, or this rank's slice of N under `template_parallel`.  pred_templates: with an encoder that has
         `decode_latent` (the VAE), the decoded templates (B,N',3,S,S) f32 (model.py:199-206,221-224), decoded on the device in chunks of
-        bounded workspace; else None.  (The PNG / video output of visualize=True is not provided.)"""
+        bounded workspace; else None.  visualize=True (model.py:214-249; needs gt_templates (B,N,3,S,S), a decoding encoder and save_dir):
+        one picture per template, media/template{i}_rank{rank}.png with i the global template index -- unnormalize(reference) |
+        unnormalize(gt_templates[:, i]) | unnormalize(pred_templates[:, i]) at 64 x 64 (pred_templates is the decoder's output in [-1, 1];
+        the reference shows its `sample`'s unnormalize_to_zero_to_one(decode), model.py:219-226: the same picture) -- and their video, whose path is the third value (None
+        otherwise; see nope_amd/vis.py)."""
+        if visualize and gt_templates is None:
+            raise ValueError("generate_templates(visualize=True) needs gt_templates (model.py:217)")
         reference_feat = self.u_net.encoder.encode_image(reference, mode="mode")   # hoisted: once, not N times
         bank = self.generate_templates_from_feat(reference_feat, all_relativeR)
         dec = self._decoder()
@@ -119,7 +126,26 @@ class PoseConditional(nn.Module):
         if lat.dtype != torch.float32:
             lat = lat.float()         # (16-bit banks: the decoder reads f32 latents)
         rgb = dec(lat)                # (an empty bank decodes to (0, 3, S, S))
-        return bank, rgb.reshape(B, n, *rgb.shape[1:]), None
+        rgb = rgb.reshape(B, n, *rgb.shape[1:])
+        vid_path = None
+        if visualize and self.save_dir is not None:
+            lo = bank.shard[0] if isinstance(bank, ndist.ShardedBank) else 0
+            vid_path = self._save_template_pictures(reference, gt_templates[:, lo:lo + n], rgb, lo)
+        return bank, rgb, vid_path
+
+    def _save_template_pictures(self, reference, gt_templates, pred_templates, first):
+        """model.py:214-249 for templates [first, first + n): every frame's PNG bytes from chunked launches over the frame axis (a chunk is copied out before the next is
+        made), one file per template, and the frames as a video.  Returns the video's path (None without frames)."""
+        from . import vis
+        media = os.path.join(self.save_dir, "media")
+        frames = []                   # on the host; the device holds one chunk of sheets at a time
+        for f0, chunk in vis.contact_sheet_chunks(vis.triptych(reference, gt_templates, pred_templates, third_unnormalize=True)):
+            for j, frame in enumerate(chunk.cpu().numpy()):
+                vis.save_png(frame, os.path.join(media, f"template{first + f0 + j}_rank{self.global_rank}.png"))
+                frames.append(frame)
+        if not frames:
+            return None
+        return vis.write_video(frames, os.path.join(media, f"video_step{self.global_step}_rank{self.global_rank}"))
 
     @torch.no_grad()
     def generate_templates_from_feat(self, reference_feat, all_relativeR, defer_range_check=False):
@@ -303,12 +329,14 @@ class PoseConditional(nn.Module):
     @torch.no_grad()
     def eval_geodesic(self, batch, data_name, visualize=False, save_prediction=False):
         """model.py:268-376 through nope_amd.harness.eval_geodesic: {"loss", geodesic / accuracy scores}.  save_prediction writes
-        predictions/pred_step{global_step}_rank{global_rank}.npz (with save_dir).  visualize is accepted and ignored."""
+        predictions/pred_step{global_step}_rank{global_rank}.npz (with save_dir).  visualize (with a decoding encoder and save_dir; forced
+        off otherwise, model.py:269-274) writes media/reconst_step*.png, the template pictures and video of generate_templates and
+        media/retrieved_step*.png, and adds `vis_imgs` to the npz; scores, indices and metrics are those of visualize=False."""
         from .harness import eval_geodesic
         save = None
         if save_prediction and self.save_dir is not None:
             save = os.path.join(self.save_dir, "predictions", f"pred_step{self.global_step}_rank{self.global_rank}")
-        _, _, res = eval_geodesic(self, batch, save_path=save)
+        _, _, res = eval_geodesic(self, batch, save_path=save, visualize=visualize)
         return res
 
     def validation_step(self, batch, idx):
