@@ -83,9 +83,10 @@ typedef void* nope_stream_t;
  * 10: nope_gd_config, nope_gd_*;
  * 11: nope_op_conv_stat_rows, nope_op_conv_ex, nope_op_group_norm_ex, nope_op_gn_apply_blocks, nope_op_gn_finalize, nope_op_absmax_f32,
  *     nope_op_amax_slot_words -- the fused GroupNorm statistics / PreNorm / range-slot plumbing at operator level;
- * 12: nope_vis_column, nope_op_vis_grid, nope_op_vis_sheet, NOPE_VIS_*).  Callers compare nope_abi_version() against the header they were
+ * 12: nope_vis_column, nope_op_vis_grid, nope_op_vis_sheet, NOPE_VIS_*;
+ * 13: nope_op_crop_frames).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 12
+#define NOPE_ABI_VERSION 13
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -517,6 +518,16 @@ int nope_op_linear(const float* in, const float* w, const float* bias, float* ou
  *   minv9_host: HOST pointer to the 3x3 inverse map, row-major; dst (C,Hd,Wd) f32. */
 int nope_op_warp_perspective(const void* src, int src_is_u8, int Hs, int Ws, int C, const float* minv9_host, float* dst_chw, int Hd, int Wd,
                              float scale, float shift, nope_stream_t s);
+/* (ABI 13) The test loader's chain for a STACK of decoded frames in one launch: paste on black through the alpha channel, crop, image transform
+ * (dataloader/shapeNet.py:184-210,167-182,64-69; bop.py:212-232 with the mask image as the alpha channel).
+ *   frames (F, Hs, Ws, Cs) uint8, Cs = 3 (RGB) or 4 (RGBA; 4-byte aligned); minv (F, 9) f32 ON THE DEVICE: one row-major inverse map per frame
+ *   (output pixel -> source pixel); dst (F, 3, Hd, Wd) f32; scale, shift, round_u8 (0 / 1) as nope_op_warp_perspective's (src_is_u8 = 1 / 2).
+ * Cs = 4: every source tap is composited on black first, round(c * a / 255) in integers (PIL's Image.paste(img, mask=alpha) onto black), and the
+ * composited taps are interpolated -- the reference's order, paste then warp.  Interpolation, zero border, rounding, scale and shift are
+ * nope_op_warp_perspective's arithmetic, operation for operation: frame f equals that call on the pasted frame f bit for bit (Cs = 3: on the raw frame).
+ * NOPE_ERR_ARG: null pointers, non-positive sizes; NOPE_ERR_UNSUPPORTED: any other Cs. */
+int nope_op_crop_frames(const void* frames, int F, int Hs, int Ws, int Cs, const float* minv, float* dst, int Hd, int Wd, float scale, float shift,
+                        int round_u8, nope_stream_t s);
 /* Token-space operators of the LDM variant (ldm/attention.py), tokens = NHWC pixels [M][C]:
  * LayerNorm over C (:210-212); GEGLU in [M][2D] -> out [M][D] (:37-44); softmax self-attention over the N tokens of each
  * sample on a fused [n][N][3C] q|k|v tensor, heads of dim_head = 32, 64 or 128 channels, C % dim_head = 0 (:168-189).  dtype = a storage code; nope_op_token_attention also takes the

@@ -261,6 +261,10 @@ int nope_op_warp_perspective(const void* src, int src_is_u8, int Hs, int Ws, int
                              float scale, float shift, nope_stream_t s) {
     return launch_warp_perspective(src, src_is_u8, Hs, Ws, C, minv9_host, dst_chw, Hd, Wd, scale, shift, (hipStream_t)s);
 }
+int nope_op_crop_frames(const void* frames, int F, int Hs, int Ws, int Cs, const float* minv, float* dst, int Hd, int Wd, float scale, float shift,
+                        int round_u8, nope_stream_t s) {
+    return launch_crop_frames(frames, F, Hs, Ws, Cs, minv, dst, Hd, Wd, scale, shift, round_u8, (hipStream_t)s);
+}
 int nope_op_linear(const float* in, const float* w, const float* bias, float* out, int M, int N, int K, int act_in, nope_stream_t s) {
     return launch_linear_naive(in, w, bias, out, M, N, K, act_in, N, (hipStream_t)s);
 }

@@ -445,29 +445,52 @@ struct Mat3 { float m[9]; };
 // ROUND_U8: the interpolated value is rounded to the nearest integer and clamped to [0, 255] before scale / shift, as a uint8
 // destination image does (cv2.warpPerspective on uint8 frames, then ToTensor's / 255): outputs land on the reference loader's
 // k / 255 grid.  OpenCV's own fixed-point interpolation weights (1/32 pixel) are not restated: parity unpinned (cv2 is absent).
+// The arithmetic of one output pixel, shared by warp_perspective_kernel and crop_frames_kernel (same f32 operations in the same order):
+// warp_taps = the source position of output pixel (x, y) under the inverse map m, its four taps, their weights and which of them lie
+// inside the source (none when w == 0); warp_interp = the weighted sum of the taps a fetch(t) hands out, rounding / clamp, scale and shift.
+// Which products are fused is spelled out (fmaf) and nothing else may be (contract(off)): left to the compiler, the choice differed from one
+// kernel to the next (its vectoriser pairs the three projections differently), and two kernels that agree only to an ulp in the source
+// position disagree by a grey level after round_u8.  The spelling is what warp_perspective_kernel has always computed on gfx950.
+struct WarpTaps { int x0, y0; float wt[4]; bool in[4]; };
+__device__ __forceinline__ WarpTaps warp_taps(const float* __restrict__ m, int x, int y, int Hs, int Ws) {
+#pragma clang fp contract(off)
+    WarpTaps tp;
+    const float xf = (float)x, yf = (float)y;
+    const float w = fmaf(m[7], yf, m[6] * xf) + m[8];
+    const float sx = ((m[0] * xf + m[1] * yf) + m[2]) / w;
+    const float sy = (fmaf(m[3], xf, m[4] * yf) + m[5]) / w;
+    const float fx = floorf(sx), fy = floorf(sy);
+    tp.x0 = (int)fx, tp.y0 = (int)fy;
+    const float ax = sx - fx, ay = sy - fy;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int xx = tp.x0 + (t & 1), yy = tp.y0 + (t >> 1);
+        tp.wt[t] = ((t & 1) ? ax : 1.f - ax) * ((t >> 1) ? ay : 1.f - ay);
+        tp.in[t] = xx >= 0 && xx < Ws && yy >= 0 && yy < Hs && w != 0.f;
+    }
+    return tp;
+}
+template <bool ROUND_U8, class Fetch>
+__device__ __forceinline__ float warp_interp(const WarpTaps& tp, float scale, float shift, Fetch fetch) {
+#pragma clang fp contract(off)
+    float v = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (tp.in[t]) v = fmaf(tp.wt[t], fetch(t), v);
+    if (ROUND_U8) v = fminf(fmaxf(rintf(v), 0.f), 255.f);
+    return fmaf(scale, v, shift);
+}
+
 template <class TIN, bool ROUND_U8>
 __global__ __launch_bounds__(NT) void warp_perspective_kernel(const TIN* __restrict__ src, int Hs, int Ws, int C, Mat3 inv, float* __restrict__ dst,
                                                               int Hd, int Wd, float scale, float shift) {
     const int total = Hd * Wd;
     for (int i = blockIdx.x * NT + threadIdx.x; i < total; i += gridDim.x * NT) {
         const int y = i / Wd, x = i - y * Wd;
-        const float w = inv.m[6] * x + inv.m[7] * y + inv.m[8];
-        const float sx = (inv.m[0] * x + inv.m[1] * y + inv.m[2]) / w;
-        const float sy = (inv.m[3] * x + inv.m[4] * y + inv.m[5]) / w;
-        const float fx = floorf(sx), fy = floorf(sy);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float ax = sx - fx, ay = sy - fy;
-        for (int c = 0; c < C; ++c) {
-            float v = 0.f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int xx = x0 + (t & 1), yy = y0 + (t >> 1);
-                const float wt = ((t & 1) ? ax : 1.f - ax) * ((t >> 1) ? ay : 1.f - ay);
-                if (xx >= 0 && xx < Ws && yy >= 0 && yy < Hs && w != 0.f) v += wt * (float)src[((size_t)yy * Ws + xx) * C + c];
-            }
-            if (ROUND_U8) v = fminf(fmaxf(rintf(v), 0.f), 255.f);
-            dst[(size_t)c * total + i] = scale * v + shift;
-        }
+        const WarpTaps tp = warp_taps(inv.m, x, y, Hs, Ws);
+        for (int c = 0; c < C; ++c)
+            dst[(size_t)c * total + i] = warp_interp<ROUND_U8>(tp, scale, shift, [&](int t) {
+                return (float)src[((size_t)(tp.y0 + (t >> 1)) * Ws + tp.x0 + (t & 1)) * C + c]; });
     }
 }
 
@@ -480,6 +503,57 @@ int launch_warp_perspective(const void* src, int src_u8, int Hs, int Ws, int C, 
     if (src_u8 == 2) hipLaunchKernelGGL((warp_perspective_kernel<unsigned char, true>), grid, dim3(NT), 0, s, (const unsigned char*)src, Hs, Ws, C, m, dst, Hd, Wd, scale, shift);
     else if (src_u8) hipLaunchKernelGGL((warp_perspective_kernel<unsigned char, false>), grid, dim3(NT), 0, s, (const unsigned char*)src, Hs, Ws, C, m, dst, Hd, Wd, scale, shift);
     else hipLaunchKernelGGL((warp_perspective_kernel<float, false>), grid, dim3(NT), 0, s, (const float*)src, Hs, Ws, C, m, dst, Hd, Wd, scale, shift);
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
+// The loader's whole chain for a stack of decoded frames in one pass (dataloader/shapeNet.py:184-210,167-182,64-69; bop.py:212-232): paste on
+// black through the alpha channel, crop_frame's warp, ToTensor, * 2 - 1.  frames (F, Hs, Ws, CS) uint8, CS = 3 (RGB) or 4 (RGBA); minv (F, 9): one
+// inverse map per frame, on the device; dst (F, 3, Hd, Wd).  One thread per output pixel, blockIdx.y walks the frames.  The reference pastes first
+// and warps the pasted image, so every tap is composited before it is weighted: round(c * a / 255) in integers, PIL's paste onto black (its
+// MULDIV255; c * a / 255 never ends in .5, 255 being odd).  An RGBA tap is one 32-bit load serving the three colour planes.
+template <int CS, bool ROUND_U8>
+__global__ __launch_bounds__(NT) void crop_frames_kernel(const unsigned char* __restrict__ frames, int Hs, int Ws, const float* __restrict__ minv,
+                                                         float* __restrict__ dst, int F, int Hd, int Wd, float scale, float shift) {
+    const int total = Hd * Wd;
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= total) return;
+    const int y = i / Wd, x = i - y * Wd;
+    for (int f = blockIdx.y; f < F; f += gridDim.y) {
+        const unsigned char* __restrict__ src = frames + (size_t)f * Hs * Ws * CS;
+        float* __restrict__ out = dst + (size_t)f * 3 * total + i;
+        const WarpTaps tp = warp_taps(minv + (size_t)f * 9, x, y, Hs, Ws);
+        if (CS == 4) {
+            unsigned px[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                px[t] = tp.in[t] ? ((const unsigned*)src)[(size_t)(tp.y0 + (t >> 1)) * Ws + tp.x0 + (t & 1)] : 0u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                out[(size_t)c * total] = warp_interp<ROUND_U8>(tp, scale, shift, [&](int t) {
+                    return (float)((2u * ((px[t] >> (8 * c)) & 255u) * (px[t] >> 24) + 255u) / 510u); });
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                out[(size_t)c * total] = warp_interp<ROUND_U8>(tp, scale, shift, [&](int t) {
+                    return (float)src[((size_t)(tp.y0 + (t >> 1)) * Ws + tp.x0 + (t & 1)) * 3 + c]; });
+        }
+    }
+}
+
+int launch_crop_frames(const void* frames, int F, int Hs, int Ws, int Cs, const float* minv, float* dst, int Hd, int Wd, float scale, float shift,
+                       int round_u8, hipStream_t s) {
+    if (!frames || !minv || !dst || F <= 0 || Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return NOPE_ERR_ARG;
+    if (Cs != 3 && Cs != 4) return NOPE_ERR_UNSUPPORTED;
+    if (((uintptr_t)frames & 3) && Cs == 4) return NOPE_ERR_ARG;       // the 32-bit tap loads
+    const size_t total = (size_t)Hd * Wd;
+    if (total > (size_t)0x7fffffff - NT) return NOPE_ERR_ARG;
+    const dim3 grid((unsigned)((total + NT - 1) / NT), (unsigned)(F < 65535 ? F : 65535));
+    const unsigned char* fr = (const unsigned char*)frames;
+#define NOPE_CROP_LAUNCH(CS, R) hipLaunchKernelGGL((crop_frames_kernel<CS, R>), grid, dim3(NT), 0, s, fr, Hs, Ws, minv, dst, F, Hd, Wd, scale, shift)
+    if (Cs == 4) { if (round_u8) NOPE_CROP_LAUNCH(4, true); else NOPE_CROP_LAUNCH(4, false); }
+    else { if (round_u8) NOPE_CROP_LAUNCH(3, true); else NOPE_CROP_LAUNCH(3, false); }
+#undef NOPE_CROP_LAUNCH
     NOPE_CHECK_LAUNCH();
     return NOPE_OK;
 }

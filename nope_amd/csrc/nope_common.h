@@ -446,6 +446,8 @@ int launch_linear_naive(const float* in, const float* w, const float* bias, floa
 int launch_silu_f32(const float* in, float* out, size_t n, hipStream_t s);
 int launch_warp_perspective(const void* src, int src_u8, int Hs, int Ws, int C, const float* minv9, float* dst, int Hd, int Wd, float scale,
                             float shift, hipStream_t s);
+int launch_crop_frames(const void* frames, int F, int Hs, int Ws, int Cs, const float* minv, float* dst, int Hd, int Wd, float scale, float shift,
+                       int round_u8, hipStream_t s);
 int launch_pos_emb(const float* pose, float* out, int n, int pose_dim, int classes, hipStream_t s);
 int launch_cast(int dt, const float* in, void* out, size_t n, hipStream_t s);
 

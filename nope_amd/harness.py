@@ -13,6 +13,12 @@ predictions are saved with `query_pose` and `similarity` only; with it (`--visua
 encoder and `--save-dir`) the pictures, the video and `vis_imgs` are written (nope_amd/vis.py).
 
     python -m nope_amd.harness --batch 1 --templates 64 --size 128     # BASELINE config 1 shape
+
+With a dataset on disk (`--data-root`, the reference's rendered ShapeNet layout) the same loop runs over a testing split read by
+`nope_amd.dataset.ShapeNet`: load_batch -> eval_geodesic per batch, then ONE JSON line with the split's sample-weighted Acc@15 / Acc@30 and
+the median over all samples' errors.  Weights stay synthetic unless a checkpoint is loaded by the caller.
+
+    python -m nope_amd.harness --data-root DIR --split bottle --id2cat FILE [--fast] [--limit N] [--batch B] [--visualize --save-dir DIR]
 """
 from __future__ import annotations
 
@@ -97,8 +103,8 @@ def synthetic_batch(batch: int, n_templates: int, size: int, seed: int = 2022, d
 
 def build_model(seed: int = 2022, compute_dtype="f32", bank_dtype="f32", device="cuda", u_net_dim: Optional[int] = None,
                 save_dir: Optional[str] = None, template_parallel: bool = False, max_hypotheses_per_launch: int = 512, encoder: str = "template"):
-    """encoder: "template" (template_base.yaml's FeatureExtractor) or "vae" (vae_base.yaml's VAE_StableDiffusion at the SD-1.5 shapes,
-    synthetic weights: images -> 4-channel latents -> the U-Net -> retrieval on the latents)."""
+    """encoder: "template" (template_base.yaml's FeatureExtractor), "vae" (vae_base.yaml's VAE_StableDiffusion at the SD-1.5 shapes,
+    synthetic weights: images -> 4-channel latents -> the U-Net -> retrieval on the latents) or "stub" (none: the images are the embeddings)."""
     from .encoder import FeatureExtractor
     from .model import PoseConditional
     from .u_net import UNet
@@ -110,8 +116,10 @@ def build_model(seed: int = 2022, compute_dtype="f32", bank_dtype="f32", device=
     elif encoder == "template":
         enc = FeatureExtractor(**cfg["u_net"]["encoder"], compute_dtype=compute_dtype)
         synth_init_(enc, seed, prefix="encoder.")
+    elif encoder == "stub":            # no encoder: the U-Net and the scoring run on the 3-channel images themselves (loader / plumbing checks)
+        enc = StubEncoder(3)
     else:
-        raise ValueError(f"encoder {encoder!r}: 'template' or 'vae'")
+        raise ValueError(f"encoder {encoder!r}: 'template', 'vae' or 'stub'")
     unet = UNet(u_net_dim=u_net_dim or cfg["u_net"]["u_net_dim"], rot_representation_dim=6, encoder=enc,
                 pose_mlp_name=cfg["u_net"]["pose_mlp_name"], compute_dtype=compute_dtype)
     # U-Net tensors are keyed without the "encoder." prefix; the encoder was initialised above
@@ -135,10 +143,12 @@ def geodesic_deg(predR: torch.Tensor, gtR: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False):
+def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False,
+                  errors_out: Optional[list] = None):
     """The body of PoseConditional.eval_geodesic (model.py:268-376).  visualize (effective with a decoding encoder and model.save_dir only,
     model.py:269-274; needs batch["gt_templates"] (B, N, 3, S, S)): the three kinds of pictures and the video under save_dir/media
-    (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions."""
+    (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions.  errors_out: a list that
+    receives this batch's (B,) top-1 errors in degrees (run_split pools them over a split)."""
     visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
     if visualize and "gt_templates" not in batch:
         raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
@@ -162,7 +172,9 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     sym = batch.get("symmetry", torch.zeros(nearest_idx.shape[0], 1, dtype=torch.long, device=nearest_idx.device))
     # pred_R = template_poses[0][nearest_idx] -> GeodesicError (model.py:352-358, loss.py:78-115): gather + angle + symmetry branches as
     # one device launch (nope_op_geodesic); the grid of the first sample serves every query, as model.py:352 indexes it
-    _, metric = GeodesicError(list(thresholds)).from_indices(batch["template_poses"][:1], nearest_idx, batch["query_pose"], sym)
+    top1, metric = GeodesicError(list(thresholds)).from_indices(batch["template_poses"][:1], nearest_idx, batch["query_pose"], sym)
+    if errors_out is not None:
+        errors_out.append(top1)
     res = {"loss": float(loss)}
     res.update({k: float(v) for k, v in metric.items()})
     if save_path:
@@ -173,11 +185,50 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     return similarity, nearest_idx, res
 
 
+def run_split(model, dataset, batch_size: int = 1, limit: Optional[int] = None, visualize: bool = False, save_dir: Optional[str] = None,
+              thresholds=(15, 30)) -> Dict[str, float]:
+    """The test loop over one ShapeNet testing split: `dataset.load_batch` -> `eval_geodesic` per batch.  Returns the split's scores over ALL
+    samples: accuracies weighted by sample (not a mean of per-batch percentages) and the median of the concatenated top-1 errors (not a mean
+    of per-batch medians).  The ground-truth templates are decoded only when they are drawn (visualize)."""
+    n = len(dataset) if limit is None else min(limit, len(dataset))
+    errors = []
+    for start in range(0, n, batch_size):
+        batch = dataset.load_batch(list(range(start, min(start + batch_size, n))), with_templates=visualize)
+        save = os.path.join(save_dir, "predictions", f"pred_step{start // batch_size}_rank{model.global_rank}") if save_dir else None
+        eval_geodesic(model, batch, thresholds, save_path=save, visualize=visualize, errors_out=errors)
+    errors = torch.cat([e.double().cpu() for e in errors]) if errors else torch.zeros(0, dtype=torch.float64)
+    res = {f"accuracy_{t}": float((errors <= t).double().mean() * 100) if n else float("nan") for t in thresholds}
+    res.update(median=float(errors.median()) if n else float("nan"), samples=n)
+    return res
+
+
+def main_dataset(a, ap):
+    """`--data-root`: a testing split from disk."""
+    from .dataset import ShapeNet
+    if not a.id2cat:
+        ap.error("--data-root needs --id2cat (the reference's src/utils/shapeNet_id2cat_v2.json)")
+    if a.visualize and (a.encoder != "vae" or not a.save_dir):
+        ap.error("--visualize needs --encoder vae (the template encoder decodes nothing, model.py:269-274) and --save-dir")
+    device = hip.compute_device().type                    # ("cpu" only under tests/' interpreter build of the kernels)
+    if device == "cuda" and not torch.cuda.is_available():
+        raise SystemExit("nope_amd.harness needs an MI355X (no CPU fallback)")
+    t0 = time.time()
+    ds = ShapeNet(a.data_root, a.split, "upper", "rotation6d", fast_evaluation=a.fast, img_size=a.size or 256, level=2, id2cat=a.id2cat,
+                  seed=a.seed, with_templates=a.visualize, pose_root=a.pose_root)
+    model = build_model(a.seed, a.dtype, a.bank_dtype, device, u_net_dim=a.u_net_dim, save_dir=a.save_dir, encoder=a.encoder)
+    res = run_split(model, ds, a.batch, a.limit, a.visualize, a.save_dir)
+    if device == "cuda":
+        torch.cuda.synchronize()
+    res.update(dataloader=f"shapeNet_{a.split}", templates=len(ds.testing_indexes), seconds=time.time() - t0)
+    print(json.dumps(res))
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--templates", type=int, default=64)
-    ap.add_argument("--size", type=int, default=128)
+    ap.add_argument("--size", type=int, default=None, help="image size (default: 128 for the synthetic batch, 256 for --data-root)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16x2", "bf16x3", "f16", "bf16"])
     ap.add_argument("--bank-dtype", default="f32", choices=["f32", "bf16", "f16"])
     ap.add_argument("--seed", type=int, default=2022)
@@ -186,11 +237,21 @@ def main(argv=None):
     ap.add_argument("--pose-level", type=int, default=None, choices=[0, 1, 2, 3],
                     help="use the upper-hemisphere icosphere grid (26/91/341/1321 templates) instead of --templates random poses")
     ap.add_argument("--pose-root", default=None, help="directory with the reference's predefined_poses/*.npy")
-    ap.add_argument("--encoder", default="template", choices=["template", "vae"],
-                    help="vae: the Stable Diffusion VAE at the SD-1.5 shapes (synthetic weights) in place of the template encoder")
+    ap.add_argument("--encoder", default="template", choices=["template", "vae", "stub"],
+                    help="vae: the Stable Diffusion VAE at the SD-1.5 shapes (synthetic weights) in place of the template encoder; "
+                         "stub: no encoder, the images themselves are the embeddings (a check of the loader and the plumbing)")
     ap.add_argument("--visualize", action="store_true",
                     help="with --encoder vae and --save-dir: write the reconstruction / template / retrieved pictures, the video and vis_imgs")
+    ap.add_argument("--data-root", default=None, help="a rendered ShapeNet root (cad_names.txt, images/, object_*_poses/): evaluate --split from disk")
+    ap.add_argument("--split", default="bottle", help="with --data-root: the testing category")
+    ap.add_argument("--id2cat", default=None, help="with --data-root: the reference's src/utils/shapeNet_id2cat_v2.json (synset id -> category)")
+    ap.add_argument("--fast", action="store_true", help="with --data-root: fast_evaluation, the 26 level-0 viewpoints instead of the 341 of level 2")
+    ap.add_argument("--limit", type=int, default=None, help="with --data-root: only the first N samples of the split")
+    ap.add_argument("--u-net-dim", type=int, default=None, help="with --data-root: U-Net width (default: template_base.yaml's 192)")
     a = ap.parse_args(argv)
+    if a.data_root:
+        return main_dataset(a, ap)
+    a.size = a.size or 128
     if a.visualize and (a.encoder != "vae" or not a.save_dir):
         ap.error("--visualize needs --encoder vae (the template encoder decodes nothing, model.py:269-274) and --save-dir")
     if not torch.cuda.is_available():

@@ -15,7 +15,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 12                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 13                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -119,6 +119,7 @@ _PROTOS = {
     "nope_op_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_linear": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_warp_perspective": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_float), _vp, _i, _i, C.c_float, C.c_float, _vp]),
+    "nope_op_crop_frames": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, C.c_float, C.c_float, _i, _vp]),
     "nope_op_layer_norm": (_i, [_i, _vp, _vp, _vp, _vp, _i64, _i, C.c_float, _vp]),
     "nope_op_geglu": (_i, [_i, _vp, _vp, _i64, _i, _vp]),
     "nope_op_token_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -201,6 +202,12 @@ def require_device(t: torch.Tensor):
     l = lib()      # (always: every binding starts here, and lib() is where a changed NOPE_* tuning variable is noticed)
     if not t.is_cuda and not getattr(l, "host_pointers", False):
         raise NopeError("nope_amd computes on the GPU only: pass CUDA (ROCm) tensors; there is no CPU path")
+
+
+def compute_device() -> torch.device:
+    """Where data that arrives from the host (decoded frames, maps) is put before a launch: the GPU -- or the host itself under the
+    interpreter build of tests/, which takes host pointers."""
+    return torch.device("cpu" if getattr(lib(), "host_pointers", False) else "cuda")
 
 
 class overlap_stream:
@@ -822,6 +829,24 @@ def op_warp_perspective(img: torch.Tensor, minv, size: int, scale: float = 1.0, 
     l = lib()
     l.check(l.dll.nope_op_warp_perspective(_ptr(img), (2 if round_u8 else 1) if img.dtype == torch.uint8 else 0, H, W, Cc, m, _ptr(out), size, size, scale, shift,
                                            _stream(img)), "nope_op_warp_perspective")
+    return out
+
+
+def op_crop_frames(frames: torch.Tensor, minv: torch.Tensor, size: int, scale: float = 1.0, shift: float = 0.0, round_u8: bool = False) -> torch.Tensor:
+    """frames (F,H,W,Cs) uint8 on the device, Cs = 3 (RGB) or 4 (RGBA: each tap is pasted on black through its alpha first); minv (F,3,3) or (F,9)
+    f32 on the device, one inverse map per frame -> (F,3,size,size) f32 in one launch; scale / shift / round_u8 as op_warp_perspective."""
+    require_device(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise NopeError(f"op_crop_frames: frames must be (F, H, W, Cs) uint8, got {tuple(frames.shape)} {frames.dtype}")
+    frames = frames.contiguous()
+    F, H, W, Cs = frames.shape
+    minv = minv.to(device=frames.device, dtype=torch.float32).reshape(-1, 9).contiguous()
+    if minv.shape[0] != F:
+        raise NopeError(f"op_crop_frames: {F} frames but {minv.shape[0]} maps")
+    out = torch.empty((F, 3, size, size), dtype=torch.float32, device=frames.device)
+    l = lib()
+    l.check(l.dll.nope_op_crop_frames(_ptr(frames), F, H, W, Cs, _ptr(minv), _ptr(out), size, size, scale, shift, int(bool(round_u8)), _stream(frames)),
+            "nope_op_crop_frames")
     return out
 
 
