@@ -122,8 +122,10 @@ int nope_topk(const float* scores, int64_t* idx, float* vals, int B, int N, int 
  *                     harness saves (model.py:323,369-375), AND its top-k (model.py:265; k = 0: scores only, idx / vals may be NULL);
  *   nope_topk_merge   cand_vals / cand_idx (B,M) = the all-gathered per-shard top-k lists (M = G k values with their GLOBAL template
  *                     indices, shards in rank order) -> the global top-k.  Same order as nope_topk on the full row: descending score, ties
- *                     -> lowest global index (a shard's list is already in that order and shards are contiguous, so position order =
- *                     index order among equal scores); pad short lists with (-inf, any index).  For callers that do not need the
+ *                     -> lowest global index, compared on the index each candidate CARRIES (then on list position, for two entries with
+ *                     the same index).  A pad fills a list that holds fewer than k real candidates: score -inf, index INT64_MAX.  It
+ *                     ranks behind every real candidate, a real -inf score included (INT64_MAX is the highest index), and comes back
+ *                     only when the lists hold fewer than k real candidates together.  For callers that do not need the
  *                     full similarity: 12 k bytes per query and rank cross the fabric instead of 4 N / G. */
 int nope_gather_topk(const float* gathered, int n_ranks, int B, int n_total, float* scores, int64_t* idx, float* vals, int k,
                      nope_stream_t stream);

@@ -11,6 +11,7 @@
 // Arithmetic is ~1.2 flop/byte: far below the VALU ridge, purely HBM-bound.
 // Accumulation is f32; reductions are fixed-shape (wave xor-tree + ordered LDS fold), so
 // scores are run-to-run deterministic.
+#include <cstdio>
 #include <cstdlib>
 
 #include "nope_common.h"
@@ -239,8 +240,20 @@ constexpr int KMAX = 16;
 
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
-// `map` (optional, [B][ld]): the value written to idx is map[b][position] instead of the position -- candidates that carry their own
-// (global) template index: the merge of per-shard top-k lists.
+// MAP (`map_row`, [ld]): candidates that carry their own (global) template index -- the merge of per-shard top-k lists.  The value written
+// to idx is map_row[position], and equal scores are ordered by THAT index (then by position: two pads, or the same template listed twice):
+// a pad (-inf, INT64_MAX) ahead of a real -inf score in the list must not be picked before it.
+template <bool MAP> __device__ __forceinline__ bool better_at(float v, int i, float bv, int bi, const long long* map_row) {
+    if constexpr (MAP) {
+        if (v != bv) return v > bv;
+        const long long gi = map_row[i], gbi = map_row[bi];
+        return gi < gbi || (gi == gbi && i < bi);
+    } else {
+        return better(v, i, bv, bi);
+    }
+}
+
+template <bool MAP>
 __device__ __forceinline__ void topk_row(const float* row, const long long* map_row, long long* __restrict__ idx, float* __restrict__ vals, int b, int N, int k) {
     __shared__ int s_chosen[KMAX];
     __shared__ float s_bv[NT / 64];
@@ -256,13 +269,13 @@ __device__ __forceinline__ void topk_row(const float* row, const long long* map_
             if (taken) continue;
             float v = row[n];
             if (v != v) v = INF;             // NaN ranks highest (torch.topk convention)
-            if (bi == 0x7fffffff || better(v, n, bv, bi)) { bv = v; bi = n; }
+            if (bi == 0x7fffffff || better_at<MAP>(v, n, bv, bi, map_row)) { bv = v; bi = n; }
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {
             const float ov = __shfl_xor(bv, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+            if (oi != 0x7fffffff && (bi == 0x7fffffff || better_at<MAP>(ov, oi, bv, bi, map_row))) { bv = ov; bi = oi; }
         }
         if (lane == 0) { s_bv[wave] = bv; s_bi[wave] = bi; }
         __syncthreads();
@@ -270,19 +283,20 @@ __device__ __forceinline__ void topk_row(const float* row, const long long* map_
             float fv = s_bv[0];
             int fi = s_bi[0];
             for (int w = 1; w < NT / 64; ++w)
-                if (s_bi[w] != 0x7fffffff && (fi == 0x7fffffff || better(s_bv[w], s_bi[w], fv, fi))) { fv = s_bv[w]; fi = s_bi[w]; }
+                if (s_bi[w] != 0x7fffffff && (fi == 0x7fffffff || better_at<MAP>(s_bv[w], s_bi[w], fv, fi, map_row))) { fv = s_bv[w]; fi = s_bi[w]; }
             s_chosen[r] = fi;
-            idx[(size_t)b * k + r] = map_row ? map_row[fi] : (long long)fi;
+            idx[(size_t)b * k + r] = MAP ? map_row[fi] : (long long)fi;
             if (vals) vals[(size_t)b * k + r] = row[fi];
         }
         __syncthreads();
     }
 }
 
+template <bool MAP>
 __global__ __launch_bounds__(NT) void topk_kernel(const float* __restrict__ scores, const long long* __restrict__ map, long long* __restrict__ idx,
                                                   float* __restrict__ vals, int N, int k, int ld) {
     const int b = blockIdx.x;
-    topk_row(scores + (size_t)b * ld, map ? map + (size_t)b * ld : nullptr, idx, vals, b, N, k);
+    topk_row<MAP>(scores + (size_t)b * ld, MAP ? map + (size_t)b * ld : nullptr, idx, vals, b, N, k);
 }
 
 // The tail of a template-sharded step in ONE launch: the all-gathered (G, B, nmax) padded score slices (rank r holds columns
@@ -302,7 +316,7 @@ __global__ __launch_bounds__(NT) void gather_topk_kernel(const float* __restrict
         row[n] = gathered[((size_t)r * B + b) * nmax + c];
     }
     __syncthreads();
-    if (k > 0) topk_row(row, nullptr, idx, vals, b, N, k);
+    if (k > 0) topk_row<false>(row, nullptr, idx, vals, b, N, k);
 }
 
 }  // namespace
@@ -320,6 +334,8 @@ int launch_similarity(const float* q, const void* bank, int bank_dt, float* scor
     // workgroups per sample: ~4096 in all, but at least NOPE_SIM_MINGROUPS template groups each (a workgroup's fixed cost is the 32 KiB
     // query tile: with two groups per workgroup -- 32 x 512 templates -- it is a third of the workgroup's traffic)
     const int min_groups = NOPE_ENV("NOPE_SIM_MINGROUPS", 1);
+    const bool trace = NOPE_ENV_SET("NOPE_SIM_TRACE");      // tuning / test aid: one line per launch saying which form ran
+    const char* const dt_name = bank_dt == NOPE_F32 ? "f32" : bank_dt == NOPE_BF16 ? "bf16" : "f16";
     const int lv = (bank_dt != NOPE_F32 && (variant & 8) && C <= 8 && HW % 4 == 0 && HW / 4 <= NT) ? 4 : vec;
     const int P = HW / lv;
     const bool reg_ok = (P <= NT) && (NT % P == 0) && (C <= 16);
@@ -344,6 +360,8 @@ int launch_similarity(const float* q, const void* bank, int bank_dt, float* scor
             if (nsplit > groups / min_groups) nsplit = groups / min_groups;                                                        \
             if (nsplit > groups) nsplit = groups;                                                                                  \
             if (nsplit < 1) nsplit = 1;                                                                                            \
+            if (trace) fprintf(stderr, "sim reg %s LV %d CMAX %d CEXACT %d nt %d qlds %d P %d hpi %d groups %d nsplit %d\n", dt_name, LV, CM, (int)EX, \
+                               (int)NTLOAD, (int)QL, P, hpi, groups, nsplit);                                                     \
             hipLaunchKernelGGL((sim_reg_kernel<T, CM, NTLOAD, LV, EX, QL>), dim3((unsigned)((long long)B * nsplit)), dim3(NT), 0, s, q, (const T*)bank, scores, \
                                N, C, HW, bank_stride_b, score_ld, nsplit);                                                         \
         } while (0)
@@ -363,6 +381,7 @@ int launch_similarity(const float* q, const void* bank, int bank_dt, float* scor
         if ((size_t)C * HW > 16384) return NOPE_ERR_UNSUPPORTED;
         nsplit = cdiv(4096, B);
         if (nsplit > N) nsplit = N;
+        if (trace) fprintf(stderr, "sim lds %s LV %d CMAX 0 CEXACT 0 nt 0 qlds 0 P %d hpi 1 groups %d nsplit %d\n", dt_name, vec, HW / vec, N, nsplit);
         dim3 grid((unsigned)((long long)B * nsplit)), block(NT);
         if (bank_dt == NOPE_F32) hipLaunchKernelGGL((sim_lds_kernel<float>), grid, block, 0, s, q, (const float*)bank, scores, N, C, HW, bank_stride_b, score_ld, nsplit);
         else if (bank_dt == NOPE_BF16) hipLaunchKernelGGL((sim_lds_kernel<bf16_t>), grid, block, 0, s, q, (const bf16_t*)bank, scores, N, C, HW, bank_stride_b, score_ld, nsplit);
@@ -374,7 +393,8 @@ int launch_similarity(const float* q, const void* bank, int bank_dt, float* scor
 
 int launch_topk(const float* scores, long long* idx, float* vals, int B, int N, int k, int ld, hipStream_t s, const long long* map) {
     if (!scores || !idx || B <= 0 || N <= 0 || k < 1 || k > KMAX || k > N || ld < N) return NOPE_ERR_ARG;
-    hipLaunchKernelGGL(topk_kernel, dim3((unsigned)B), dim3(NT), 0, s, scores, map, idx, vals, N, k, ld);
+    if (map) hipLaunchKernelGGL(topk_kernel<true>, dim3((unsigned)B), dim3(NT), 0, s, scores, map, idx, vals, N, k, ld);
+    else hipLaunchKernelGGL(topk_kernel<false>, dim3((unsigned)B), dim3(NT), 0, s, scores, map, idx, vals, N, k, ld);
     NOPE_CHECK_LAUNCH();
     return NOPE_OK;
 }

@@ -306,7 +306,7 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 # --------------------------------------------------------------------------------------------
 def similarity(q: torch.Tensor, bank: torch.Tensor, out: Optional[torch.Tensor] = None,
                col_offset: int = 0) -> torch.Tensor:
-    """score[b,n] of model.py:257-262.  q (B,C,H,W) f32; bank (B|1,N,C,H,W) f32|bf16.
+    """score[b,n] of model.py:257-262.  q (B,C,H,W) f32; bank (B|1,N,C,H,W) f32|bf16|fp16.
     With `out` (B, Ntotal) given, writes columns [col_offset, col_offset+N)."""
     require_device(q)
     q = _f32c(q)
