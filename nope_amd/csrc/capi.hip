@@ -1,6 +1,6 @@
 // extern "C" entry points of libnope_hip.so that are thin argument checks over the kernel
 // launchers (the U-Net entry points live in unet_runtime.hip).  See include/nope_hip.h.
-#include "nope_common.h"
+#include "conv_plan.h"      // (nope_common.h; ConvLaunch)
 
 #include <atomic>
 #include <cstdlib>
@@ -203,9 +203,10 @@ int nope_op_conv_ex(int dtype, const void* src1, int C1, int rep1, const void* s
     if (colstats) a.stat_rows = stat_rows;
     a.pn_ms = pn_ms; a.pn_c0 = pn_c0; a.pn_c1 = pn_c1;
     a.out_amax = amax_slot;
-    if (amax_recorded) *amax_recorded = conv_records_out_amax(dtype, a) ? 1 : 0;
+    const ConvLaunch L = conv_plan(dtype, a);
+    if (amax_recorded) *amax_recorded = L.p.out_amax ? 1 : 0;      // (of the launch that runs: a slot was given and its epilogue fills it)
     if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
-    if (const int e = launch_conv(dtype, a, (hipStream_t)s)) return e;
+    if (const int e = launch_conv(L, (hipStream_t)s)) return e;
     return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
 }
 

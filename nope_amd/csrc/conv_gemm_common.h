@@ -1,8 +1,8 @@
 // Shared internals of the implicit-GEMM conv kernels (kernels_gemm.hip: the 128 x 192 kernels and the launcher;
 // kernels_gemm_pp.hip: the 256 x 192 eight-wave ping-pong kernel): launch parameters, the MFMA tile traits, the LDS
-// swizzle, the fragment stage and the epilogues.  Included inside each translation unit (internal linkage).
+// swizzle, the fragment stage and the epilogues (the launch parameters themselves: conv_plan.h).  Included inside each translation unit (internal linkage).
 #pragma once
-#include "nope_common.h"
+#include "conv_plan.h"      // (nope_common.h; FastDiv, ConvParams)
 
 #ifndef NOPE_EPILOGUE_LEAN_GROUP
 #define NOPE_EPILOGUE_LEAN_GROUP 2      // 16-byte chunks a lane keeps in flight between the panel read and the store (1, 2, 4 or 8)
@@ -18,67 +18,6 @@ constexpr int NT = 256;
 constexpr int ROWB = 128;  // bytes per LDS row
 constexpr int A_ITERS = BM / 32;
 constexpr int B_ITERS = BN / 32;
-
-// Unsigned division by a launch-time constant, exact for n < 2^31: q = mulhi(n, M) >> sh with
-// M = floor(2^(32+sh) / d) + 1, sh = ceil(log2 d) - 1 (d >= 2); M == 0 encodes d == 1.  Replaces the ~35-instruction
-// integer-division sequences of the per-row index arithmetic in the conv prologue.
-struct FastDiv {
-    unsigned M, sh;
-    __device__ __forceinline__ unsigned div(unsigned n) const {
-        return M ? (unsigned)(((unsigned long long)n * M) >> 32) >> sh : n;
-    }
-};
-static inline FastDiv make_fastdiv(unsigned d) {
-    FastDiv f{0u, 0u};
-    if (d <= 1) return f;
-    unsigned s = 0;
-    while ((1ull << s) < d) ++s;                       // s = ceil(log2 d) >= 1
-    f.sh = s - 1;
-    f.M = (unsigned)(((1ull << (31 + s)) / d) + 1);    // < 2^32 because d > 2^(s-1)
-    return f;
-}
-
-struct ConvParams {
-    const unsigned char* src1; const unsigned char* src2;
-    int C1, C2, rep1, rep2;
-    int Hs, Ws, Ho, Wo;
-    int mode, ntaps;
-    const unsigned char* w;
-    const float* bias;
-    const unsigned char* resid;
-    unsigned char* out;
-    int Cout, M;
-    int out_nchw, out_dt;
-    int act;                           // 0 none, 1 ReLU (after bias and residual)
-    int tiles_m, tiles_n, xcd_map, wide_out;
-    int geglu;                         // host side only: selects the GEGLU-epilogue instantiation (ConvArgs::geglu)
-    int nchw_staged;                   // out_nchw through the per-wave LDS panels (epilogue_nchw): whole 64-row blocks inside one sample
-    int xcd_gn;                        // (xcd_map: 0 none, 1 one panel per XCD, 2 below, 3 small-tile kernel, 4 any tiles_n) xcd_map == 2: XCD columns the weight panels are split over (tile_coords)
-    int variant;                       // tuning switches (NOPE_CONV_VARIANT), 0 in production
-    FastDiv d_hw, d_w, d_rep1, d_rep2; // / (Hm*Wm), / Wm, / rep1, / rep2
-    unsigned char pos_order[64];       // posmajor: pixel positions by descending number of valid taps
-    int persist_iters;                 // > 1: a workgroup walks this many tiles
-    unsigned persist_d1, persist_d2;   // byte advance of the A offsets per walked tile (src1 / src2)
-    int persist_dm;                    // GEMM rows between the tiles a workgroup of the 128 x 192 kernel walks
-    unsigned* timeline;                // tuning only (NOPE_PP_VARIANT & 256): cycle stamps of workgroup 0, see conv3x3_halo_kernel
-    int posmajor;                      // 1: GEMM rows ordered (pixel position, sample) instead of (sample, pixel) -- see launch_conv
-    FastDiv d_n;                       // / nhyp (posmajor)
-    int nhyp;
-    int splits;                        // > 1: blockIdx.z owns a K range and writes raw f32 partial sums
-    float* split_out;                  // [splits][M][Cout]
-    int Hm, Wm;                        // grid the GEMM rows enumerate: output grid, or the SOURCE grid for UP2P
-    unsigned w_phase_bytes;            // UP2P: byte stride between the 4 phase weight sets
-    float* colstats;                   // optional [M/stat_rows][Cout][2]: per row block column sum / sum of squares
-    int stat_rows;                     // 64 (every kernel), 16 / 32 (small-tile kernel only)
-    const float* pn_ms; const float* pn_c0; const float* pn_c1;   // optional fused PreNorm (see ConvArgs)
-    unsigned bytes1, bytes2, bytesw;   // tensor sizes for the buffer descriptors of the DMA kernel
-    const int* x2_scale;               // NOPE_F16X2 (ping-pong kernels): the tail of the packed weights, [0] = E8M0 scale of the A operand, [3] = range shift t
-    unsigned* x2_amax;                 // NOPE_F16X2: optional device word, atomicMax of the bits of max |a| over every A element the launch converted (NOPE_X2_KERNEL_AMAX builds)
-    int x2_t_zero;                     // NOPE_F16X2: the caller vouches that the layer's range shift (tail word 3) is 0: the tap-resident kernel skips the a * 2^-t multiplies
-    int lean;                          // 1: f32 storage, every wave tile of the launch whole and in NHWC row order (see epilogue_wide, LEANM): the kernels' LEAN instantiations
-    unsigned* out_amax;                // f32-storage launches with a wide NHWC epilogue: optional range slot (amax_publish) for max |out| of what the launch writes
-    int s2_off;                        // STRIDE2: 0 = centre tap at (2 oy, 2 ox) (pad 1), 1 = at (2 oy + 1, 2 ox + 1) (NOPE_CONV_STRIDE2_PAD01: pad (0, 1, 0, 1))
-};
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
@@ -773,7 +712,7 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
             const size_t o = out_row(p, m) * p.Cout + n;
             if constexpr (GG && sizeof(T) == 4) {
                 // f32 storage: the lane's four columns are two (x, gate) pairs -> two values = 8 bytes per row into the [M][Cout / 2] output (no residual /
-                // activation / PreNorm: geglu_shape_ok); same operands and formula as geglu_kernel<float, true>: bit-identical to conv + geglu
+                // activation / PreNorm: conv_plan); same operands and formula as geglu_kernel<float, true>: bit-identical to conv + geglu
                 const f32x2_t y = {geglu_f(v[0], v[1]), geglu_f(v[2], v[3])};
                 *reinterpret_cast<f32x2_t*>(out + (o >> 1)) = y;
                 continue;

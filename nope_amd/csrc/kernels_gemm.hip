@@ -242,8 +242,6 @@ __global__ __launch_bounds__(NT, 2) void conv_gemm_kernel(ConvParams p) {
 
 }  // namespace
 
-// Split-K factor for a conv that would otherwise leave most of the 256 CUs idle (few output tiles, long K):
-// enough K slices to reach ~2 workgroups per CU, at least 4 K steps each.  1 = do not split.
 constexpr int POSMAJOR_MAX_HW = 64;
 
 void launch_conv_dma_f32(const void* params, int bm, dim3 grid, hipStream_t s);            // kernels_gemm_dma_*.hip
@@ -257,44 +255,56 @@ void launch_conv_halo(int dt, const void* params, dim3 grid, hipStream_t s);
 void launch_conv_stream(int dt, const void* params, dim3 grid, hipStream_t s);   // kernels_gemm_stream.hip
 int conv_halo_max_width();
 
-// Which kernel a conv takes.  NOPE_CONV_PP (tuning; default 3): bit 0 = the 256 x 192 ping-pong kernels for launches with
-// at least one 256-row tile per CU, bit 1 = also for the small-map 3x3 convs that would otherwise run position-major on
-// the 128 x 192 kernel (they then run in standard row order, all 9 taps, on the tap-resident kernel: 239 vs 257 us for
-// 1536 -> 1536 at 4 x 4 x 512 although it executes the 31 % of MACs the position-major order skips), bit 2 = those run position-major on the
-// ping-pong kernel (needs nhyp % 256 == 0), bit 3 = no minimum tile count (tests: small shapes on the ping-pong kernel),
-// bit 4 = 3x3 convs per tap on the ping-pong kernel instead of the tap-resident (halo) kernel.
-struct ConvPlan { bool dma, pp, posmajor, halo; int small; int hsplit; bool stream; };      // hsplit > 1: tap-resident kernel with that many K splits      // small: -1, or the tile of conv_gemm_small_kernel (0 = 64 x 64, 1 = 128 x 128, 2 = 64 x 64 / 6-stage ring, 3 = 64 x 64 by two K groups)
+// ---- the pieces conv_plan is built on; conv_stat_rows and conv_splitk_factor, which a caller asks BEFORE it has the scratch a plan needs,
+// ---- read the same ones.  `dt` is a base type everywhere below (NOPE_F16X2 plans as NOPE_BF16X3: same storage, same tiles).
+
+// Sizes of a launch, computed once: M = GEMM rows (source pixels for the phase convs of an up-sampling), b1 / b2 / bw = bytes of the two
+// sources and of one phase's weights.  (rep < 1 is refused by conv_plan; the pre-queries, which validate nothing, must not divide by it.)
+struct ConvSizes { int vec, es, bk, Cin; bool phased; long long M; unsigned long long b1, b2, bw; };
+static ConvSizes conv_sizes(int dt, const ConvArgs& a) {
+    const int es = dt_es(dt), Cin = a.C1 + a.C2;
+    const bool phased = a.mode == NOPE_CONV_UP2P;
+    return {dt_vec(dt), es, 8 * dt_vec(dt), Cin, phased, (long long)a.nhyp * (phased ? a.Hs * a.Ws : a.Ho * a.Wo),
+            (unsigned long long)cdiv(a.nhyp, a.rep1 < 1 ? 1 : a.rep1) * a.Hs * a.Ws * a.C1 * es, a.C2 ? (unsigned long long)cdiv(a.nhyp, a.rep2 < 1 ? 1 : a.rep2) * a.Hs * a.Ws * a.C2 * es : 0,
+            (unsigned long long)a.Cout * a.ntaps * Cin * es};
+}
+
+// LDS-DMA kernels: a K step (128 B of channels) never straddles sources and 32-bit offsets suffice
+// (the 4x4 stride-2 conv of the non-default soft downsampling runs on the generic kernel: its tap geometry is not a 3x3 mask)
+static bool takes_dma(const ConvArgs& a, const ConvSizes& z) {
+    const unsigned long long lim = 0x7fffffffULL;
+    return !a.force_generic && a.ntaps != 16 && z.Cin % z.bk == 0 && (a.C2 == 0 || (a.C1 % z.bk == 0 && a.mode == NOPE_CONV_PLAIN)) && z.b1 < lim && z.b2 < lim && z.bw < lim;
+}
 
 // Launches that cannot give every CU a 128 x 192 tile take the small-tile kernel (kernels_gemm_small.hip): fewer than
 // NOPE_SMALL_MAX_TILES (default 320) tiles of 128 x 192.  NOPE_CONV_SMALL: 0 = never, 1 = that policy (default), 2 = whenever the
-// kernel applies (tests); NOPE_SMALL_TILE forces the tile.
-static int plan_small(int dt, const ConvArgs& a, bool dma) {
-    dt = dt_base(dt);      // (NOPE_F16X2 plans as NOPE_BF16X3: same storage, same tiles)
+// kernel applies (tests); NOPE_SMALL_TILE forces the tile.  -1, or the tile (ConvLaunch::small).
+static int small_tile(int dt, const ConvArgs& a, const ConvSizes& z) {
     const int mode_env = NOPE_ENV("NOPE_CONV_SMALL", 1);
-    if (!dma || mode_env == 0 || a.mode == NOPE_CONV_UP2 || a.ntaps == 16 || a.force_generic) return -1;
+    if (!takes_dma(a, z) || a.geglu) return -1;          // (GEGLU epilogue: an instantiation of the 128 x 192 kernel only)
+    if (mode_env == 0 || a.mode == NOPE_CONV_UP2 || a.ntaps == 16 || a.force_generic) return -1;
     if (a.out_nchw && a.pn_ms) return -1;      // (the small-tile kernel's NCHW epilogue has no fused PreNorm: the 128 x 192 kernel's generic epilogue does)
     if (mode_env == 1 && (NOPE_ENV("NOPE_CONV_PP", 0) & 8)) return -1;      // bit 3 = "ping-pong kernels at ANY tile count" (their tests)
-    const bool phased = a.mode == NOPE_CONV_UP2P;
-    const long long M = (long long)a.nhyp * (phased ? a.Hs * a.Ws : a.Ho * a.Wo);
-    const long long tiles128 = (long long)cdiv((int)M, BM) * cdiv(a.Cout, BN) * (phased ? 4 : 1);
+    const int ph = z.phased ? 4 : 1, nk1 = z.Cin / z.bk;
+    const long long tiles128 = (long long)cdiv((int)z.M, BM) * cdiv(a.Cout, BN) * ph;
     const int max_tiles = NOPE_ENV("NOPE_SMALL_MAX_TILES", 320);      // (tuning sweeps toggle it: nope_tuning_reload)
     // Short-K 1x1 convs of ANY size (NOPE_SMALL_1X1_MAXK = K steps, default 0 = off): their 128 x 192 launches are bound by the epilogue
     // of a three-K-step tile, not by HBM (192 -> 384 at 32 x 32 x 512: 604 MB in 221 us = 2.7 TB/s); the 128 x 128 small tile has a one-pass
     // epilogue.
     const int maxk_1x1 = NOPE_ENV("NOPE_SMALL_1X1_MAXK", 0);
-    if (mode_env == 1 && a.mode == NOPE_CONV_PLAIN && a.ntaps == 1 && !a.out_nchw && (a.C1 + a.C2) / (8 * dt_vec(dt)) <= maxk_1x1 && tiles128 >= max_tiles)
+    if (mode_env == 1 && a.mode == NOPE_CONV_PLAIN && a.ntaps == 1 && !a.out_nchw && nk1 <= maxk_1x1 && tiles128 >= max_tiles)
         return NOPE_ENV("NOPE_SMALL_TILE", 1);
     if (mode_env == 1 && tiles128 >= max_tiles) return -1;
     if (mode_env == 1 && dt != NOPE_F32 && a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && a.Ws <= conv_halo_max_width() && a.rep1 == 1 && !a.out_nchw &&
-        !a.pn_ms && a.Cout % dt_vec(dt) == 0 && 9 * ((a.C1 + a.C2) / (8 * dt_vec(dt))) >= 54 && (long long)cdiv((int)M, 256) * cdiv(a.Cout, BN) >= 128)
+        !a.pn_ms && a.Cout % z.vec == 0 && 9 * nk1 >= 54 && (long long)cdiv((int)z.M, 256) * cdiv(a.Cout, BN) >= 128)
         return -1;       // the tap-resident kernel has its 128 tiles of 256 rows (measured at 16 x 16 x 64: 60.6 / 83 us against 83 / 116 us on 64 x 64 tiles)
     if (NOPE_ENV_SET("NOPE_SMALL_TILE")) { const int t = NOPE_ENV("NOPE_SMALL_TILE", 0); return t < 0 || t > 3 ? 0 : t; }
-    const long long tiles64 = (long long)cdiv((int)M, 64) * cdiv(a.Cout, 64) * (phased ? 4 : 1);
+    const long long tiles64 = (long long)cdiv((int)z.M, 64) * cdiv(a.Cout, 64) * ph;
     if (tiles64 > 1536) return 1;
     // (tile 2, the 6-stage ring, for launches of at most NOPE_SMALL_DEEP_MAX tiles with a K loop of >= 8 steps: with 512 -- launches that
     //  the 48 KiB ring runs two workgroups per CU -- measured SLOWER than the 3-stage ring, 26 / 64 templates 4.16 / 4.95 ms against
     //  4.04 / 4.81, profiles/r04e_small_bank_sweep.txt; off by default)
-    const int nk = a.ntaps * ((a.C1 + a.C2) / (8 * dt_vec(dt)));
+    const int nk = a.ntaps * nk1;
     const int deep_max = NOPE_ENV("NOPE_SMALL_DEEP_MAX", 0);
     if (tiles64 <= deep_max && nk >= 8) return 2;
     // at most one workgroup per CU and a long K: two wave groups per tile on alternate K steps (tile 3)
@@ -307,17 +317,14 @@ static int plan_small(int dt, const ConvArgs& a, bool dma) {
 // reduce): its 256-row tiles move a third of the L2 -> LDS bytes per flop of the 128 x 192 kernel, which is what bounds these
 // launches (profiles/r04b: 51 us for 1536 -> 1536 at 4 x 4 x 64 on the 128 x 192 kernel split 8 ways = 1.9 us per K step, 111 us on 64 x 64
 // tiles).  Returns the number of splits (1: does not apply).  NOPE_HALO_SPLIT=0 turns it off.
-static int halo_split_factor(int dt, const ConvArgs& a) {
-    dt = dt_base(dt);      // (NOPE_F16X2 plans as NOPE_BF16X3: same storage, same tiles)
+static int halo_split_factor(int dt, const ConvArgs& a, const ConvSizes& z) {
     if (NOPE_ENV("NOPE_HALO_SPLIT", -1) == 0) return 1;
     const int pp_mode = NOPE_ENV("NOPE_CONV_PP", (dt != NOPE_F32 ? 3 : 0));
     if (!(pp_mode & 1) || (pp_mode & 16)) return 1;
-    const int vec = dt_vec(dt), bk = 8 * vec, Cin = a.C1 + a.C2;
     if (a.mode != NOPE_CONV_PLAIN || a.ntaps != 9 || a.Ws > conv_halo_max_width() || a.rep1 != 1 || a.out_nchw || a.pn_ms ||
-        a.force_generic || a.Cout % vec || Cin % bk || (a.C2 && a.C1 % bk)) return 1;
-    const long long M = (long long)a.nhyp * a.Ho * a.Wo;
-    const int nchunks = Cin / bk;
-    const long long tiles = (long long)cdiv((int)M, 256) * cdiv(a.Cout, BN);
+        a.force_generic || a.Cout % z.vec || z.Cin % z.bk || (a.C2 && a.C1 % z.bk)) return 1;
+    const int nchunks = z.Cin / z.bk;
+    const long long tiles = (long long)cdiv((int)z.M, 256) * cdiv(a.Cout, BN);
     const int min_chunks = NOPE_ENV("NOPE_HALO_SPLIT_MIN_CHUNKS", 12);
     // 128 tiles split in two fill the 256 CUs in one round (256 hypotheses at the 4 x 4 level: 11.35 -> 10.76 ms per step, run t); above that a
     // split needs a second round of workgroups and loses (176 tiles, 341 hypotheses: 14.8 -> 15.3 ms)
@@ -331,48 +338,80 @@ static int halo_split_factor(int dt, const ConvArgs& a) {
     return S < 2 ? 1 : S;
 }
 
+// Split-K factor for a conv that would otherwise leave most of the 256 CUs idle (few output tiles, long K):
+// enough K slices to reach ~2 workgroups per CU, at least 4 K steps each.  1 = do not split.
+static int splitk_factor(int dt, const ConvArgs& a, const ConvSizes& z) {
+    {
+        const int hs = halo_split_factor(dt, a, z);   // long 3x3 convs with few tiles: split-K on the tap-resident kernel (its reduce kernel
+        if (hs > 1) return hs;                        // also serves a colstats request)
+    }
+    if (a.colstats || a.pn_ms || a.mode == NOPE_CONV_UP2P || a.mode == NOPE_CONV_UP2) return 1;
+    if (z.Cin % z.bk) return 1;
+    if (small_tile(dt, a, z) >= 0) return 1;          // the small-tile kernel has enough workgroups without splitting K
+    const long long tiles = (long long)cdiv((int)z.M, BM) * cdiv(a.Cout, BN);
+    const int nk = a.ntaps * (z.Cin / z.bk);
+    if (tiles > 128 || nk < 8) return 1;
+    int S = (int)((512 + tiles - 1) / tiles);
+    if (S > nk / 4) S = nk / 4;
+    if (S > 16) S = 16;
+    return S < 2 ? 1 : S;
+}
+int conv_splitk_factor(int dt, const ConvArgs& a) { return splitk_factor(dt_base(dt), a, conv_sizes(dt_base(dt), a)); }
+
+// Fused GroupNorm column statistics, rows per block (0: this conv cannot emit them): 64 wherever samples are whole 64-row blocks; 16 on
+// 16-pixel maps (the 4 x 4 level: per-sample blocks, every LDS-DMA kernel's wide epilogue, the small-tile kernel, the split-K reduce) -- which
+// removes that level's gn_stats passes; 32 on 32-pixel maps from the small-tile kernel and the split-K reduce.
+static int stat_rows(int dt, const ConvArgs& a, const ConvSizes& z) {
+    if (z.phased || a.resid || a.out_nchw || a.Cout % z.vec || a.Cout > 2048) return 0;
+    const long long HW = (long long)a.Ho * a.Wo;
+    if (HW % 64 == 0) return 64;
+    // 16-pixel maps (the 4 x 4 level): per-sample blocks of 16 rows -- every kernel with the wide epilogue, the small-tile kernel and the
+    // split-K reduce emit them; 32-pixel maps only the latter two
+    const bool small_or_split = halo_split_factor(dt, a, z) > 1 || small_tile(dt, a, z) >= 0;
+    const bool wide16 = (NOPE_ENV("NOPE_STATS16", -1) != 0);      // (A/B switch: 0 = the 128 x 192 / ping-pong kernels leave 16-pixel maps to gn_stats)
+    if (HW == 16 && z.M % 16 == 0 && (small_or_split || (wide16 && takes_dma(a, z)))) return 16;
+    if (HW == 32 && z.M % 32 == 0 && small_or_split) return 32;
+    return 0;
+}
+int conv_stat_rows(int dt, const ConvArgs& a) { return stat_rows(dt_base(dt), a, conv_sizes(dt_base(dt), a)); }
+
 // workgroups of a streaming launch: one per CU (NOPE_STREAM_GRID: the tests walk small grids; a multiple of 8)
 static int stream_grid() { const int g = NOPE_ENV("NOPE_STREAM_GRID", 256); return g >= 8 && g % 8 == 0 ? g : 256; }
 
-static ConvPlan plan_conv(int dt, const ConvArgs& a) {
-    dt = dt_base(dt);      // (NOPE_F16X2 plans as NOPE_BF16X3: same storage, same tiles)
+// Which kernel a conv asks for.  NOPE_CONV_PP (tuning; default 3): bit 0 = the 256 x 192 ping-pong kernels for launches with
+// at least one 256-row tile per CU, bit 1 = also for the small-map 3x3 convs that would otherwise run position-major on
+// the 128 x 192 kernel (they then run in standard row order, all 9 taps, on the tap-resident kernel: 239 vs 257 us for
+// 1536 -> 1536 at 4 x 4 x 512 although it executes the 31 % of MACs the position-major order skips), bit 2 = those run position-major on the
+// ping-pong kernel (needs nhyp % 256 == 0), bit 3 = no minimum tile count (tests: small shapes on the ping-pong kernel),
+// bit 4 = 3x3 convs per tap on the ping-pong kernel instead of the tap-resident (halo) kernel.
+struct KernelChoice { bool dma, pp, posmajor, halo; int small; int hsplit; bool stream; };      // hsplit > 1: tap-resident kernel with that many K splits; stream: granted by conv_plan only if the grid fits
+static KernelChoice choose_kernel(int dt, const ConvArgs& a, const ConvSizes& z) {
     // (read per launch: the tests toggle it.  f32 -- the parity mode -- stays on the 128 x 192 kernel unless asked: its MFMA phase is
     //  16x longer per K step, loads were never its bound, and two workgroups per CU beat one: 126 vs 135 ms per 512-template step)
     const int pp_mode = NOPE_ENV("NOPE_CONV_PP", (dt != NOPE_F32 ? 3 : 0));
     const int variant = NOPE_ENV("NOPE_CONV_VARIANT", 0);
-    ConvPlan pl{false, false, false, false, -1, 1, false};
-    const int vec = dt_vec(dt), es = dt_es(dt), bk = 8 * vec;
-    const int Cin = a.C1 + a.C2;
-    const unsigned long long lim = 0x7fffffffULL;
-    const bool phased = a.mode == NOPE_CONV_UP2P;
-    const unsigned long long b1 = (unsigned long long)cdiv(a.nhyp, a.rep1) * a.Hs * a.Ws * a.C1 * es;
-    const unsigned long long b2 = a.C2 ? (unsigned long long)cdiv(a.nhyp, a.rep2) * a.Hs * a.Ws * a.C2 * es : 0;
-    const unsigned long long bw = (unsigned long long)a.Cout * a.ntaps * Cin * es;
-    // LDS-DMA kernels: a K step (128 B of channels) never straddles sources and 32-bit offsets suffice
-    // (the 4x4 stride-2 conv of the non-default soft downsampling runs on the generic kernel: its tap geometry is not a 3x3 mask)
-    pl.dma = !a.force_generic && a.ntaps != 16 && Cin % bk == 0 && (a.C2 == 0 || (a.C1 % bk == 0 && a.mode == NOPE_CONV_PLAIN)) && b1 < lim && b2 < lim && bw < lim;
+    KernelChoice pl{false, false, false, false, -1, 1, false};
+    pl.dma = takes_dma(a, z);
     if (!pl.dma || a.geglu) return pl;          // (GEGLU epilogue: an instantiation of the 128 x 192 kernel only)
     if (a.splitk_ws) {
-        const int hs = halo_split_factor(dt, a);
-        const long long Mr = (long long)a.nhyp * a.Ho * a.Wo;
-        if (hs > 1 && (size_t)hs * (size_t)Mr * a.Cout * 4 <= a.splitk_bytes) { pl.pp = pl.halo = true; pl.hsplit = hs; return pl; }
+        const int hs = halo_split_factor(dt, a, z);
+        if (hs > 1 && (size_t)hs * (size_t)z.M * a.Cout * 4 <= a.splitk_bytes) { pl.pp = pl.halo = true; pl.hsplit = hs; return pl; }
     }
-    pl.small = plan_small(dt, a, pl.dma);
+    pl.small = small_tile(dt, a, z);
     if (pl.small >= 0) return pl;
     const bool small3x3 = a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && !a.colstats && !a.pn_ms && !a.out_nchw && !a.splitk_ws &&
                           a.Hs * a.Ws <= POSMAJOR_MAX_HW;
     const bool posmajor128 = small3x3 && a.nhyp % BM == 0 && !(variant & 8) && variant != 4;
-    const long long M = (long long)a.nhyp * (phased ? a.Hs * a.Ws : a.Ho * a.Wo);
     // (short K loops -- the 1x1 convs around the attention blocks, 2-3 K steps per tile -- stay on the 128 x 192 kernel, whose two
     //  workgroups per CU cover each other's prologue and epilogue: measured 193 vs 234 us for 192 -> 384 at 32 x 32)
     // (long 3x3 launches take the tap-resident kernel from 128 tiles on -- NOPE_HALO_MIN_TILES: the 768 -> 768 convs of the 4 x 4
     //  level at 512 hypotheses have 128 tiles of 108 K steps; on half the CUs they still beat the position-major 128 x 192 launch,
     //  one workgroup per CU: 20.26 -> 20.19 ms per step, profiles/r03d_defaults_ab.txt)
     const int halo_min_tiles = NOPE_ENV("NOPE_HALO_MIN_TILES", 128);
-    const long long min_tiles = (a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && a.ntaps * (Cin / bk) >= 54) ? halo_min_tiles : 256;
-    const bool pp_shape = (a.mode == NOPE_CONV_PLAIN || a.mode == NOPE_CONV_DOWN2 || phased) && !a.out_nchw && a.Cout % vec == 0 &&
-                          ((pp_mode & 8) || a.ntaps * (Cin / bk) >= 12) &&
-                          ((pp_mode & 8) || (long long)cdiv((int)M, 256) * cdiv(a.Cout, BN) * (phased ? 4 : 1) >= min_tiles) && variant == 0;
+    const long long min_tiles = (a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && a.ntaps * (z.Cin / z.bk) >= 54) ? halo_min_tiles : 256;
+    const bool pp_shape = (a.mode == NOPE_CONV_PLAIN || a.mode == NOPE_CONV_DOWN2 || z.phased) && !a.out_nchw && a.Cout % z.vec == 0 &&
+                          ((pp_mode & 8) || a.ntaps * (z.Cin / z.bk) >= 12) &&
+                          ((pp_mode & 8) || (long long)cdiv((int)z.M, 256) * cdiv(a.Cout, BN) * (z.phased ? 4 : 1) >= min_tiles) && variant == 0;
     if (pp_shape && (pp_mode & 1)) {
         if (!posmajor128) pl.pp = true;
         else if ((pp_mode & 4) && a.nhyp % 256 == 0) { pl.pp = true; pl.posmajor = true; }
@@ -389,8 +428,8 @@ static ConvPlan plan_conv(int dt, const ConvArgs& a) {
     // passes per step: the per-tap kernel's LOAD phase is hidden) it is +-2 % per launch: per tap stays.  NOPE_UP2P_HALO: 0 = per tap, 2 = bf16x3 too.
     {
         const int uh = NOPE_ENV("NOPE_UP2P_HALO", 1);
-        const bool x2_layer = a.w_x2 && !a.pn_ms && !a.geglu && Cin % 32 == 0;
-        if (pl.pp && phased && !pl.posmajor && a.ntaps == 4 && dt == NOPE_BF16X3 && a.C2 == 0 && a.Ws <= 30 && a.rep1 == 1 && !(pp_mode & 16) &&      // (Ws <= 30: at most five A pieces per wave)
+        const bool x2_layer = a.w_x2 && !a.pn_ms && !a.geglu && z.Cin % 32 == 0;
+        if (pl.pp && z.phased && !pl.posmajor && a.ntaps == 4 && dt == NOPE_BF16X3 && a.C2 == 0 && a.Ws <= 30 && a.rep1 == 1 && !(pp_mode & 16) &&      // (Ws <= 30: at most five A pieces per wave)
             (uh == 2 || (uh == 1 && x2_layer)))
             pl.halo = true;
     }
@@ -403,9 +442,9 @@ static ConvPlan plan_conv(int dt, const ConvArgs& a) {
     // would take, bit 1 = also the long 1x1 convs of the per-tap ping-pong kernel; NOPE_STREAM_MIN_ITERS = tiles per workgroup from which on.
     {
         const int sm = NOPE_ENV("NOPE_CONV_STREAM", 0);
-        const long long tm = M / BM, tn = cdiv(a.Cout, BN);
-        if (sm && dt != NOPE_F32 && a.mode == NOPE_CONV_PLAIN && a.ntaps == 1 && !pl.posmajor && !a.out_nchw && a.Cout % vec == 0 && a.w &&
-            a.rep1 == 1 && a.rep2 == 1 && variant == 0 && (!pl.pp || (sm & 2)) && M % BM == 0 && (tn == 1 || tn == 2 || tn == 4 || tn == 8) &&
+        const long long tm = z.M / BM, tn = cdiv(a.Cout, BN);
+        if (sm && dt != NOPE_F32 && a.mode == NOPE_CONV_PLAIN && a.ntaps == 1 && !pl.posmajor && !a.out_nchw && a.Cout % z.vec == 0 && a.w &&
+            a.rep1 == 1 && a.rep2 == 1 && variant == 0 && (!pl.pp || (sm & 2)) && z.M % BM == 0 && (tn == 1 || tn == 2 || tn == 4 || tn == 8) &&
             tm % 8 == 0 && (tm * tn) % stream_grid() == 0 && (tm * tn) / stream_grid() >= NOPE_ENV("NOPE_STREAM_MIN_ITERS", 2)) {
             pl.stream = true; pl.pp = false; pl.halo = false;
         }
@@ -413,138 +452,76 @@ static ConvPlan plan_conv(int dt, const ConvArgs& a) {
     return pl;
 }
 
-// ConvArgs::geglu: a plain 1x1 conv on the 128 x 192 LDS-DMA kernel's wide epilogue (no residual / statistics / PreNorm / activation / split):
-// 16-bit storage on the packed path, column pairs whole inside a lane's 8-column chunk and 8-byte output rows; f32 storage (round 6; NOPE_GEGLU_FUSED_F32=0:
-// A/B switch) in the generic row loop, two pairs per 4-column chunk
-static bool geglu_shape_ok(int dt, const ConvArgs& a, const ConvPlan& pl) {
-    const int variant = NOPE_ENV("NOPE_CONV_VARIANT", 0);
-    return (dt_es(dt) == 2 || NOPE_ENV("NOPE_GEGLU_FUSED_F32", 1)) && a.mode == NOPE_CONV_PLAIN && a.ntaps == 1 && !a.resid && !a.colstats && !a.pn_ms && !a.out_nchw && !a.act && !a.splitk_ws &&
-           a.Cout % 16 == 0 && pl.dma && !pl.pp && pl.small < 0 && !pl.posmajor && variant == 0;
-}
-bool conv_geglu_fusable(int dt, const ConvArgs& a0) {
-    const int mode = NOPE_ENV("NOPE_GEGLU_FUSED", 1);      // (A/B switch; 2: only launches the 128 x 192 kernel would get anyway)
-    if (mode == 0) return false;
-    if (mode == 2) { const ConvPlan q = plan_conv(dt, a0); if (q.pp || q.small >= 0) return false; }
+ConvLaunch conv_plan(int dt, const ConvArgs& a0) {
+    ConvLaunch L;
+    ConvParams& p = L.p;
+    const auto fail = [&L](int e) -> ConvLaunch& { L.err = e; return L; };
+    // ---- the two argument rewrites
     ConvArgs a = a0;
-    a.geglu = 1;
-    return geglu_shape_ok(dt, a, plan_conv(dt, a));
-}
-
-// Would launch_conv run this conv in position-major row order?
-bool conv_is_posmajor(int dt, const ConvArgs& a) { return plan_conv(dt, a).posmajor; }
-
-// Fused GroupNorm column statistics, rows per block (0: this conv cannot emit them): 64 wherever samples are whole 64-row blocks; 16 on
-// 16-pixel maps (the 4 x 4 level: per-sample blocks, every LDS-DMA kernel's wide epilogue, the small-tile kernel, the split-K reduce) -- which
-// removes that level's gn_stats passes; 32 on 32-pixel maps from the small-tile kernel and the split-K reduce.
-int conv_stat_rows(int dt, const ConvArgs& a) {
-    dt = dt_base(dt);      // (NOPE_F16X2 plans as NOPE_BF16X3: same storage, same tiles)
-    const int vec = dt_vec(dt);
-    if (a.mode == NOPE_CONV_UP2P || a.resid || a.out_nchw || a.Cout % vec || a.Cout > 2048) return 0;
-    const long long HW = (long long)a.Ho * a.Wo, M = (long long)a.nhyp * HW;
-    if (HW % 64 == 0) return 64;
-    // 16-pixel maps (the 4 x 4 level): per-sample blocks of 16 rows -- every kernel with the wide epilogue, the small-tile kernel and the
-    // split-K reduce emit them; 32-pixel maps only the latter two
-    ConvArgs b = a;
-    b.colstats = nullptr;
-    const bool small_or_split = halo_split_factor(dt, b) > 1 || plan_conv(dt, b).small >= 0;
-    const bool wide16 = (NOPE_ENV("NOPE_STATS16", -1) != 0);      // (A/B switch: 0 = the 128 x 192 / ping-pong kernels leave 16-pixel maps to gn_stats)
-    if (HW == 16 && M % 16 == 0 && (small_or_split || (wide16 && plan_conv(dt, b).dma))) return 16;
-    if (HW == 32 && M % 32 == 0 && small_or_split) return 32;
-    return 0;
-}
-
-// the f16 + MX-fp8 tile: launches of a layer that carries the second pack on a ping-pong kernel (tap-resident or per-tap) or -- round 6 -- on the
-// small-tile kernel (reference-sized banks, an 8-way shard).  NOPE_X2_PP=0: tap-resident only.  NOPE_X2_SMALL=1: also on the small-tile kernel
-// -- built, bit-identical to the ping-pong kernels, measured SLOWER than its bf16x3 form there (26 / 64 / 91 templates 7.29 / 9.13 / 11.47 ms
-// against 6.52 / 8.59 / 11.05, same box, profiles/r06c_small_tile_x2_ab.txt: a 64 x 64 tile's wave holds ONE accumulator, so its three MFMAs per
-// K step are a dependent chain either way and the register split costs more VALU than the third pass costs matrix time): off by default
-static bool plan_takes_x2(const ConvArgs& a, const ConvPlan& plan) {
-    if (!a.w_x2 || a.pn_ms || a.geglu || (a.C1 + a.C2) % 32) return false;
-    if (plan.small >= 0) return NOPE_ENV("NOPE_X2_SMALL", 0) != 0;
-    return plan.pp && (plan.halo || NOPE_ENV("NOPE_X2_PP", 1) != 0);
-}
-// the wide NHWC epilogue (epilogue_wide) of a 4-byte element type, whole launch in one pass: the 128 x 192 LDS-DMA kernel and the ping-pong kernels
-static bool plan_records_out_amax(int dt, const ConvArgs& a, const ConvPlan& plan) {
-    return dt_es(dt_base(dt)) == 4 && plan.dma && plan.small < 0 && plan.hsplit <= 1 && !a.out_nchw && !a.geglu && a.Cout % 4 == 0 &&
-           (plan.pp || !a.splitk_ws || conv_splitk_factor(dt, a) <= 1);
-}
-bool conv_records_out_amax(int dt, const ConvArgs& a) { return a.out_amax && plan_records_out_amax(dt, a, plan_conv(dt, a)); }
-bool conv_takes_x2(int dt, const ConvArgs& a) { return dt_base(dt) == NOPE_BF16X3 && plan_takes_x2(a, plan_conv(dt, a)); }
-
-int conv_kernel_kind(int dt, const ConvArgs& a) {
-    const ConvPlan pl = plan_conv(dt, a);
-    return pl.small >= 0 ? NOPE_CONV_KERNEL_SMALL : pl.stream ? NOPE_CONV_KERNEL_STREAM : pl.halo ? NOPE_CONV_KERNEL_HALO256 : pl.pp ? NOPE_CONV_KERNEL_PP256 : pl.dma ? NOPE_CONV_KERNEL_DMA128 : NOPE_CONV_KERNEL_GENERIC;
-}
-
-// Multiply-adds x2 the launch actually executes (position-major launches skip the taps that lie in the padding:
-// (3H-2)(3W-2) of the 9 H W tap instances remain).
-double conv_executed_flops(int dt, const ConvArgs& a) {
-    dt = dt_base(dt);      // (NOPE_F16X2 plans as NOPE_BF16X3: same storage, same tiles)
-    double taps = (double)a.ntaps;
-    if (conv_is_posmajor(dt, a)) taps = (double)(3 * a.Hs - 2) * (3 * a.Ws - 2) / ((double)a.Hs * a.Ws);
-    return 2.0 * (double)a.nhyp * a.Ho * a.Wo * a.Cout * taps * (a.C1 + a.C2);
-}
-
-int conv_splitk_factor(int dt, const ConvArgs& a) {
-    dt = dt_base(dt);      // (NOPE_F16X2 plans as NOPE_BF16X3: same storage, same tiles)
-    {
-        const int hs = halo_split_factor(dt, a);      // long 3x3 convs with few tiles: split-K on the tap-resident kernel (its reduce kernel
-        if (hs > 1) return hs;                        // also serves a colstats request)
-    }
-    if (a.colstats || a.pn_ms || a.mode == NOPE_CONV_UP2P || a.mode == NOPE_CONV_UP2) return 1;
-    const int vec = dt_vec(dt);
-    const int Cin = a.C1 + a.C2;
-    if (Cin % (8 * vec)) return 1;
-    if (plan_conv(dt, a).small >= 0) return 1;        // the small-tile kernel has enough workgroups without splitting K
-    const long long M = (long long)a.nhyp * a.Ho * a.Wo;
-    const long long tiles = (long long)cdiv((int)M, BM) * cdiv(a.Cout, BN);
-    const int nk = a.ntaps * (Cin / (8 * vec));
-    if (tiles > 128 || nk < 8) return 1;
-    int S = (int)((512 + tiles - 1) / tiles);
-    if (S > nk / 4) S = nk / 4;
-    if (S > 16) S = 16;
-    return S < 2 ? 1 : S;
-}
-
-int launch_conv(int dt, const ConvArgs& a, hipStream_t s) {
     if (a.mode == NOPE_CONV_STRIDE2_PAD01) {      // Downsample2D(padding=0) / CompVis Downsample: pad (0, 1, 0, 1), 3x3, stride 2, no padding --
         // the STRIDE2 tiles with the centre tap one source pixel down and right; the bottom / right taps of the last row / column read the padding
-        if (a.ntaps != 9 || a.C2 != 0 || a.s2_off != 0) return NOPE_ERR_ARG;
-        ConvArgs b = a;
-        b.mode = NOPE_CONV_STRIDE2; b.s2_off = 1;
-        return launch_conv(dt, b, s);
+        if (a.ntaps != 9 || a.C2 != 0 || a.s2_off != 0) return fail(NOPE_ERR_ARG);
+        a.mode = NOPE_CONV_STRIDE2; a.s2_off = 1;
     }
-    if (a.s2_off && (a.mode != NOPE_CONV_STRIDE2 || a.ntaps != 9 || a.s2_off != 1)) return NOPE_ERR_ARG;
+    if (a.s2_off && (a.mode != NOPE_CONV_STRIDE2 || a.ntaps != 9 || a.s2_off != 1)) return fail(NOPE_ERR_ARG);
     if (dt == NOPE_F16X2) {      // as an element type (nope_op_conv): `w` is in the NOPE_F16X2 layout, which only the ping-pong kernels read
-        if (a.w_x2) return NOPE_ERR_ARG;
-        ConvArgs b = a;
-        b.w_x2 = a.w; b.w = nullptr;
-        return launch_conv(NOPE_BF16X3, b, s);
+        if (a.w_x2) return fail(NOPE_ERR_ARG);
+        a.w_x2 = a.w; a.w = nullptr;
+        dt = NOPE_BF16X3;
     }
-    if (a.w_x2 && dt != NOPE_BF16X3) return NOPE_ERR_ARG;
-    if (!a.src1 || (!a.w && !a.w_x2) || !a.out || a.C1 <= 0 || a.Cout <= 0 || a.nhyp <= 0) return NOPE_ERR_ARG;
-    if (a.C2 > 0 && !a.src2) return NOPE_ERR_ARG;
-    const int vec = dt_vec(dt);
-    if (!dt_is_compute(dt)) return NOPE_ERR_UNSUPPORTED;
-    if (a.C1 % vec || a.C2 % vec) return NOPE_ERR_UNSUPPORTED;
-    if (dt == NOPE_BF16X3 && (a.C1 % 8 || a.C2 % 8)) return NOPE_ERR_UNSUPPORTED;     // (hi, lo) weight groups hold 8 channels
-    if (a.rep1 < 1 || a.rep2 < 1) return NOPE_ERR_ARG;
-    if (a.mode == NOPE_CONV_PLAIN) {
-        if ((a.ntaps != 1 && a.ntaps != 9) || a.Hs != a.Ho || a.Ws != a.Wo) return NOPE_ERR_ARG;
-    } else if (a.mode == NOPE_CONV_UP2) {
-        if (a.ntaps != 9 || a.Ho != 2 * a.Hs || a.Wo != 2 * a.Ws) return NOPE_ERR_ARG;
-    } else if (a.mode == NOPE_CONV_DOWN2) {
-        if (a.ntaps != 4 || a.Hs != 2 * a.Ho || a.Ws != 2 * a.Wo) return NOPE_ERR_ARG;
-    } else if (a.mode == NOPE_CONV_UP2P) {
-        if (a.ntaps != 4 || a.Ho != 2 * a.Hs || a.Wo != 2 * a.Ws || a.C2 != 0 || a.out_nchw) return NOPE_ERR_ARG;
-    } else if (a.mode == NOPE_CONV_STRIDE2) {
-        if ((a.ntaps != 1 && a.ntaps != 9 && a.ntaps != 16) || a.Hs != 2 * a.Ho || a.Ws != 2 * a.Wo || a.C2 != 0) return NOPE_ERR_ARG;
-    } else return NOPE_ERR_ARG;
-    const bool phased = a.mode == NOPE_CONV_UP2P;
-    const long long M = phased ? (long long)a.nhyp * a.Hs * a.Ws : (long long)a.nhyp * a.Ho * a.Wo;
-    if (M > 0x7fffffffLL) return NOPE_ERR_UNSUPPORTED;
-
-    ConvParams p;
+    L.dt = dt;
+    // ---- validation
+    if (a.w_x2 && dt != NOPE_BF16X3) return fail(NOPE_ERR_ARG);
+    if (!a.src1 || (!a.w && !a.w_x2) || !a.out || a.C1 <= 0 || a.Cout <= 0 || a.nhyp <= 0) return fail(NOPE_ERR_ARG);
+    if (a.C2 > 0 && !a.src2) return fail(NOPE_ERR_ARG);
+    if (!dt_is_compute(dt)) return fail(NOPE_ERR_UNSUPPORTED);
+    if (a.C1 % dt_vec(dt) || a.C2 % dt_vec(dt)) return fail(NOPE_ERR_UNSUPPORTED);
+    if (dt == NOPE_BF16X3 && (a.C1 % 8 || a.C2 % 8)) return fail(NOPE_ERR_UNSUPPORTED);     // (hi, lo) weight groups hold 8 channels
+    if (a.rep1 < 1 || a.rep2 < 1) return fail(NOPE_ERR_ARG);
+    const bool same = a.Hs == a.Ho && a.Ws == a.Wo, up = a.Ho == 2 * a.Hs && a.Wo == 2 * a.Ws, down = a.Hs == 2 * a.Ho && a.Ws == 2 * a.Wo;
+    if (!(a.mode == NOPE_CONV_PLAIN ? (a.ntaps == 1 || a.ntaps == 9) && same
+          : a.mode == NOPE_CONV_UP2 ? a.ntaps == 9 && up
+          : a.mode == NOPE_CONV_DOWN2 ? a.ntaps == 4 && down
+          : a.mode == NOPE_CONV_UP2P ? a.ntaps == 4 && up && a.C2 == 0 && !a.out_nchw
+          : a.mode == NOPE_CONV_STRIDE2 && (a.ntaps == 1 || a.ntaps == 9 || a.ntaps == 16) && down && a.C2 == 0)) return fail(NOPE_ERR_ARG);
+    const ConvSizes z = conv_sizes(dt, a);
+    const int vec = z.vec, es = z.es, Cin = z.Cin;
+    const bool phased = z.phased;
+    const long long M = z.M;
+    if (M > 0x7fffffffLL) return fail(NOPE_ERR_UNSUPPORTED);
+    const bool wide_out = !a.out_nchw && a.Cout % vec == 0;
+    if (a.pn_ms && (!a.pn_c0 || !a.pn_c1 || a.mode != NOPE_CONV_PLAIN || a.ntaps != 1 || a.colstats)) return fail(NOPE_ERR_ARG);
+    if (a.colstats && (!wide_out || phased || a.resid || a.act || a.stat_rows != stat_rows(dt, a, z))) return fail(NOPE_ERR_ARG);      // (act: the epilogues take the
+                                                                                                      // statistics before an activation, the split-K reduce after it -- nobody needs the pair)
+    // ---- kernel, tile, precision
+    const KernelChoice pick = choose_kernel(dt, a, z);
+    const bool dma = pick.dma;
+    L.small = pick.small;
+    L.posmajor = pick.posmajor;
+    // the f16 + MX-fp8 tile: launches of a layer that carries the second pack on a ping-pong kernel (tap-resident or per-tap) or -- round 6 -- on the
+    // small-tile kernel (reference-sized banks, an 8-way shard).  NOPE_X2_PP=0: tap-resident only.  NOPE_X2_SMALL=1: also on the small-tile kernel
+    // -- built, bit-identical to the ping-pong kernels, measured SLOWER than its bf16x3 form there (26 / 64 / 91 templates 7.29 / 9.13 / 11.47 ms
+    // against 6.52 / 8.59 / 11.05, same box, profiles/r06c_small_tile_x2_ab.txt: a 64 x 64 tile's wave holds ONE accumulator, so its three MFMAs per
+    // K step are a dependent chain either way and the register split costs more VALU than the third pass costs matrix time): off by default
+    L.x2 = a.w_x2 && !a.pn_ms && !a.geglu && Cin % 32 == 0 &&
+           (pick.small >= 0 ? NOPE_ENV("NOPE_X2_SMALL", 0) != 0 : pick.pp && (pick.halo || NOPE_ENV("NOPE_X2_PP", 1) != 0));
+    if (!L.x2 && !a.w) return fail(NOPE_ERR_UNSUPPORTED);       // (NOPE_F16X2 as an element type on a shape the ping-pong kernels do not take)
+    // ConvArgs::geglu: a plain 1x1 conv on the 128 x 192 LDS-DMA kernel's wide epilogue (no residual / statistics / PreNorm / activation / split):
+    // 16-bit storage on the packed path, column pairs whole inside a lane's 8-column chunk and 8-byte output rows; f32 storage (round 6; NOPE_GEGLU_FUSED_F32=0:
+    // A/B switch) in the generic row loop, two pairs per 4-column chunk
+    const int variant = NOPE_ENV("NOPE_CONV_VARIANT", 0);
+    if (a.geglu && !((es == 2 || NOPE_ENV("NOPE_GEGLU_FUSED_F32", 1)) && a.mode == NOPE_CONV_PLAIN && a.ntaps == 1 && !a.resid && !a.colstats && !a.pn_ms && !a.out_nchw &&
+                     !a.act && !a.splitk_ws && a.Cout % 16 == 0 && dma && !pick.pp && pick.small < 0 && !pick.posmajor && variant == 0))
+        return fail(NOPE_ERR_UNSUPPORTED);
+    if (a.colstats && a.stat_rows == 32 && pick.small < 0 && pick.hsplit <= 1) return fail(NOPE_ERR_ARG);   // 32-row blocks: small-tile kernel or split-K reduce only
+    if (a.colstats && a.stat_rows == 16 && pick.small < 0 && pick.hsplit <= 1 && (!dma || pick.posmajor)) return fail(NOPE_ERR_ARG);
+    // NOPE_CONV_VARIANT=4 selects the 256x192 / 8-wave tile (measured on par with the default 128x192 / 4-wave
+    // tile in round 1; kept for tuning, see DESIGN.md section 4 for the other variants that were tried).
+    const int bm = pick.small >= 0 ? (pick.small == 1 ? 128 : 64)
+                   : (pick.pp || (dma && variant == 4 && M >= 256 * 256 && (dt == NOPE_F32 || dt == NOPE_BF16))) ? 256 : BM;
+    const int bn = pick.small >= 0 ? (pick.small == 1 ? 128 : 64) : BN;
+    L.bm = bm;
+    // ---- the kernels' parameters
     p.src1 = (const unsigned char*)a.src1; p.src2 = (const unsigned char*)a.src2;
     p.C1 = a.C1; p.C2 = a.C2; p.rep1 = a.rep1; p.rep2 = a.rep2;
     p.Hs = a.Hs; p.Ws = a.Ws; p.Ho = a.Ho; p.Wo = a.Wo;
@@ -554,52 +531,29 @@ int launch_conv(int dt, const ConvArgs& a, hipStream_t s) {
     p.out = (unsigned char*)a.out; p.Cout = a.Cout; p.M = (int)M;
     p.out_nchw = a.out_nchw; p.out_dt = a.out_dt;
     p.act = a.act;
-    p.wide_out = (!a.out_nchw && a.Cout % vec == 0) ? 1 : 0;
+    p.wide_out = wide_out ? 1 : 0;
     p.nchw_staged = (a.out_nchw && !a.resid && !a.pn_ms && M % 64 == 0 && ((long long)a.Ho * a.Wo) % 64 == 0 &&
                      (NOPE_ENV("NOPE_NCHW_STAGED", -1) != 0)) ? 1 : 0;
     p.colstats = a.colstats;
     p.stat_rows = a.stat_rows;
     p.pn_ms = a.pn_ms; p.pn_c0 = a.pn_c0; p.pn_c1 = a.pn_c1;
-    if (a.pn_ms && (!a.pn_c0 || !a.pn_c1 || a.mode != NOPE_CONV_PLAIN || a.ntaps != 1 || a.colstats)) return NOPE_ERR_ARG;
-    if (a.colstats && (!p.wide_out || phased || a.resid || a.act || a.stat_rows != conv_stat_rows(dt, a))) return NOPE_ERR_ARG;      // (act: the epilogues take the
-                                                                                                      // statistics before an activation, the split-K reduce after it -- nobody needs the pair)
-    const int es = dt_es(dt);
-    const int Cin = a.C1 + a.C2;
-    const unsigned long long b1 = (unsigned long long)cdiv(a.nhyp, a.rep1) * a.Hs * a.Ws * a.C1 * es;
-    const unsigned long long b2 = a.C2 ? (unsigned long long)cdiv(a.nhyp, a.rep2) * a.Hs * a.Ws * a.C2 * es : 0;
-    const unsigned long long bw = (unsigned long long)a.Cout * a.ntaps * Cin * es;     // one phase's weights
-    p.w_phase_bytes = phased ? (unsigned)bw : 0u;
-    const ConvPlan plan = plan_conv(dt, a);
-    const bool dma = plan.dma;
-    const bool x2 = plan_takes_x2(a, plan);
-    if (!x2 && !a.w) return NOPE_ERR_UNSUPPORTED;               // (NOPE_F16X2 as an element type on a shape the ping-pong kernels do not take)
-    p.x2_scale = nullptr; p.x2_amax = x2 ? a.x2_amax : nullptr; p.x2_t_zero = x2 ? a.x2_t_zero : 0;
-    p.out_amax = (a.out_amax && plan_records_out_amax(dt, a, plan)) ? a.out_amax : nullptr;
-    if (x2) { p.w = (const unsigned char*)a.w_x2; p.x2_scale = reinterpret_cast<const int*>(p.w + bw * (phased ? 4 : 1)); }
-    if (a.geglu && !geglu_shape_ok(dt, a, plan)) return NOPE_ERR_UNSUPPORTED;
+    p.w_phase_bytes = phased ? (unsigned)z.bw : 0u;
+    p.x2_amax = L.x2 ? a.x2_amax : nullptr; p.x2_t_zero = L.x2 ? a.x2_t_zero : 0;
+    if (L.x2) { p.w = (const unsigned char*)a.w_x2; p.x2_scale = reinterpret_cast<const int*>(p.w + z.bw * (phased ? 4 : 1)); }
     p.geglu = a.geglu;
-    if (a.colstats && a.stat_rows == 32 && plan.small < 0 && plan.hsplit <= 1) return NOPE_ERR_ARG;   // 32-row blocks: small-tile kernel or split-K reduce only
-    if (a.colstats && a.stat_rows == 16 && plan.small < 0 && plan.hsplit <= 1 && (!dma || plan.posmajor)) return NOPE_ERR_ARG;
-    p.bytes1 = (unsigned)(dma ? b1 : 0); p.bytes2 = (unsigned)(dma ? b2 : 0); p.bytesw = (unsigned)(dma ? bw : 0);
-    // NOPE_CONV_VARIANT=4 selects the 256x192 / 8-wave tile (measured on par with the default 128x192 / 4-wave
-    // tile in round 1; kept for tuning, see DESIGN.md section 4 for the other variants that were tried).
-    const int variant = NOPE_ENV("NOPE_CONV_VARIANT", 0);
+    p.bytes1 = (unsigned)(dma ? z.b1 : 0); p.bytes2 = (unsigned)(dma ? z.b2 : 0); p.bytesw = (unsigned)(dma ? z.bw : 0);
     p.variant = variant;
     p.d_hw = make_fastdiv((unsigned)(p.Hm * p.Wm)); p.d_w = make_fastdiv((unsigned)p.Wm);
     p.d_rep1 = make_fastdiv((unsigned)p.rep1); p.d_rep2 = make_fastdiv((unsigned)p.rep2);
-    const int bm = plan.small >= 0 ? (plan.small == 1 ? 128 : 64)
-                   : (plan.pp || (dma && variant == 4 && M >= 256 * 256 && (dt == NOPE_F32 || dt == NOPE_BF16))) ? 256 : BM;
-    const int bn = plan.small >= 0 ? (plan.small == 1 ? 128 : 64) : BN;
     p.tiles_m = cdiv((int)M, bm); p.tiles_n = cdiv(a.Cout, bn);
     const int tn = p.tiles_n;
-    p.xcd_map = plan.small < 0 && (tn == 1 || tn == 2 || tn == 4 || tn == 8) && (p.tiles_m % (8 / tn) == 0) ? 1 : 0;
+    p.xcd_map = pick.small < 0 && (tn == 1 || tn == 2 || tn == 4 || tn == 8) && (p.tiles_m % (8 / tn) == 0) ? 1 : 0;
     const long long nblocks = (long long)p.tiles_m * p.tiles_n;
-    if (nblocks > 0x7fffffffLL) return NOPE_ERR_UNSUPPORTED;
-    p.splits = 1; p.split_out = nullptr;
+    if (nblocks > 0x7fffffffLL) return fail(NOPE_ERR_UNSUPPORTED);
     // Position-major row order for small images: with 4x4 / 8x8 maps 31 % / 16 % of the 3x3 taps fall into the padding;
     // grouping the rows of a tile by pixel position makes those taps invalid for whole tiles, whose K steps then vanish.
     p.nhyp = a.nhyp; p.d_n = make_fastdiv((unsigned)a.nhyp);
-    p.posmajor = plan.posmajor ? 1 : 0;
+    p.posmajor = pick.posmajor ? 1 : 0;
     if (p.posmajor) {       // positions sorted by descending valid-tap count (stable)
         int cnt[64], n = a.Hs * a.Ws;
         for (int i = 0; i < n; ++i) {
@@ -612,22 +566,26 @@ int launch_conv(int dt, const ConvArgs& a, hipStream_t s) {
                 const unsigned char tmp = p.pos_order[j]; p.pos_order[j] = p.pos_order[j - 1]; p.pos_order[j - 1] = tmp;
             }
     }
-    if (plan.hsplit > 1) {
-        p.splits = plan.hsplit;
-        p.split_out = (float*)a.splitk_ws;
-    } else if (dma && !plan.pp && a.splitk_ws) {
-        p.splits = conv_splitk_factor(dt, a);
-        if ((size_t)p.splits * (size_t)M * a.Cout * 4 > a.splitk_bytes) p.splits = 1;
-        if (p.splits > 1) p.split_out = (float*)a.splitk_ws;
-    }
+    // ---- K splits: the tap-resident kernel's (chosen with the kernel), or the 128 x 192 kernel's where the scratch holds them
+    p.splits = 1;
+    const int want_splits = (dma && !pick.pp && a.splitk_ws) ? splitk_factor(dt, a, z) : 1;
+    if (pick.hsplit > 1) p.splits = pick.hsplit;
+    else if ((size_t)want_splits * (size_t)M * a.Cout * 4 <= a.splitk_bytes) p.splits = want_splits;
+    if (p.splits > 1) p.split_out = (float*)a.splitk_ws;
+    L.reduce = p.splits <= 1 ? CONV_REDUCE_NONE : a.colstats ? CONV_REDUCE_STATS : CONV_REDUCE_PLAIN;      // (statistics: the tap-resident split only)
+    // the wide NHWC epilogue (epilogue_wide) of a 4-byte element type, whole launch in one pass: the 128 x 192 LDS-DMA kernel and the ping-pong kernels
+    // (a 128 x 192 launch that WANTED to split but whose scratch was short records nothing either)
+    L.records_out_amax = es == 4 && dma && pick.small < 0 && pick.hsplit <= 1 && !a.out_nchw && !a.geglu && a.Cout % 4 == 0 && (pick.pp || want_splits <= 1);
+    p.out_amax = L.records_out_amax ? a.out_amax : nullptr;
+    // ---- workgroup -> tile map
     // LDS-DMA launches with several weight panels: split the panels over gn XCD columns and the M tiles over 8 / gn XCD rows
     // so that the bytes crossing the fabric, gn x activations + (8 / gn) x weights, are fewest (tile_coords, map 2).
     // NOPE_XCD_MAP=1 keeps one panel per XCD (gn = tiles_n).
     p.xcd_gn = tn;
-    if (plan.small >= 0) {
+    const double abytes = (double)z.b1 + (double)z.b2, wbytes = (double)z.bw * (phased ? 4 : 1);
+    if (pick.small >= 0) {
         // small tiles: an (8 / gn) x gn XCD grid over (runs of M tiles) x (groups of weight panels), gn chosen like below; at small
         // M the weights are most of the bytes, so they usually cross the fabric once (gn = 8) and the activations 8 times
-        const double abytes = (double)b1 + (double)b2, wbytes = (double)bw * (phased ? 4 : 1);
         double best = -1.0;
         for (int gn = 1; gn <= 8; gn *= 2)
             if (p.tiles_m % (8 / gn) == 0 && p.tiles_n % gn == 0 && (best < 0 || gn * abytes + (8 / gn) * wbytes < best)) {
@@ -635,7 +593,6 @@ int launch_conv(int dt, const ConvArgs& a, hipStream_t s) {
             }
     }
     if (dma && p.xcd_map && p.xcd_map != 3 && tn > 1 && (NOPE_ENV("NOPE_XCD_MAP", -1) != 1)) {
-        const double abytes = (double)b1 + (double)b2, wbytes = (double)bw * (phased ? 4 : 1);
         double best = tn * abytes + (8 / tn) * wbytes;
         for (int gn = 1; gn < tn; gn *= 2)
             if (p.tiles_m % (8 / gn) == 0 && gn * abytes + (8 / gn) * wbytes < best) { best = gn * abytes + (8 / gn) * wbytes; p.xcd_gn = gn; }
@@ -646,105 +603,129 @@ int launch_conv(int dt, const ConvArgs& a, hipStream_t s) {
         if (p.xcd_gn != tn) p.xcd_map = 2;
     }
     // Panel counts outside {1, 2, 4, 8} (no launch of the default U-Net; the LDM variant's linears): map 4 of tile_coords.  NOPE_XCD_ANY=0: off.
-    if (!p.xcd_map && plan.small < 0 && tn > 1 && p.tiles_m % 8 == 0 && (NOPE_ENV("NOPE_XCD_ANY", -1) != 0)) p.xcd_map = 4;
+    if (!p.xcd_map && pick.small < 0 && tn > 1 && p.tiles_m % 8 == 0 && (NOPE_ENV("NOPE_XCD_ANY", -1) != 0)) p.xcd_map = 4;
+    // ---- tile walks
     // Persistent walk: 512 workgroups (2 per CU), each `iters` tiles 64 / span tile_m apart (same XCD, same weight panel; span =
     // panels an XCD interleaves under map 2).
-    p.persist_iters = 1; p.persist_d1 = p.persist_d2 = 0; p.persist_dm = 0; p.timeline = nullptr;
+    p.persist_iters = 1;
     unsigned gx = (unsigned)nblocks;
+    const long long hw = (long long)a.Hs * a.Ws;
+    const int span = p.xcd_map == 2 ? tn / p.xcd_gn : 1;     // workgroups of one XCD that share an M tile
+    const auto walk128 = [&](int g) {      // g workgroups of the 128-row tiles, each walking tiles g / 8 / span tile_m apart
+        p.persist_iters = (int)(nblocks / g);
+        p.persist_dm = (g / 8 / span) * BM;
+        p.persist_d1 = (unsigned)((long long)p.persist_dm * a.C1 * es);
+        p.persist_d2 = (unsigned)((long long)p.persist_dm * a.C2 * es);
+        gx = (unsigned)g;
+    };
     {
-        const long long hw = (long long)a.Hs * a.Ws;
         const int persist_on = NOPE_ENV("NOPE_CONV_PERSIST", 1);
-        const int span = p.xcd_map == 2 ? tn / p.xcd_gn : 1;
         const int pg = NOPE_ENV("NOPE_PERSIST_GRID", 512) == 256 ? 256 : 512;      // (tuning: 256 = one workgroup per CU)
-        if (persist_on && dma && plan.small < 0 && bm == BM && dt != NOPE_F32 && a.mode == NOPE_CONV_PLAIN && !p.posmajor && p.splits == 1 && p.xcd_map && p.xcd_map != 4 &&
+        if (persist_on && dma && pick.small < 0 && bm == BM && dt != NOPE_F32 && a.mode == NOPE_CONV_PLAIN && !p.posmajor && p.splits == 1 && p.xcd_map && p.xcd_map != 4 &&
             p.wide_out && a.rep1 == 1 && a.rep2 == 1 && M % BM == 0 && nblocks > pg && nblocks % pg == 0 && (pg / 8) % span == 0 &&
-            ((long long)(pg / 8 / span) * BM) % hw == 0 && !(variant & 2)) {
-            p.persist_iters = (int)(nblocks / pg);
-            p.persist_dm = (pg / 8 / span) * BM;
-            p.persist_d1 = (unsigned)((long long)p.persist_dm * a.C1 * es);
-            p.persist_d2 = (unsigned)((long long)p.persist_dm * a.C2 * es);
-            gx = (unsigned)pg;
-        }
+            ((long long)(pg / 8 / span) * BM) % hw == 0 && !(variant & 2))
+            walk128(pg);
     }
     // The tap-resident kernel walks tiles too (bf16): one workgroup per CU, tiles gx / 8 apart inside the XCD's run of M tiles,
     // the next tile's prologue in flight under the epilogue.  NOPE_HALO_PERSIST = workgroups (default 256, 0 = one tile per
     // workgroup; the tests use small grids).
-    if (plan.halo && !phased && dt != NOPE_F32 && p.xcd_map && p.xcd_map != 4 && p.splits == 1) {      // (the split-K instantiation returns after its first tile; the phase-conv form walks no tiles)
+    if (pick.halo && !phased && dt != NOPE_F32 && p.xcd_map && p.xcd_map != 4 && p.splits == 1) {      // (the split-K instantiation returns after its first tile; the phase-conv form walks no tiles)
         const int want = NOPE_ENV("NOPE_HALO_PERSIST", 256);
-        const long long hw = (long long)a.Hs * a.Ws;
-        const int span = p.xcd_map == 2 ? tn / p.xcd_gn : 1;     // workgroups of one XCD that share an M tile
         if (want >= 8 && want % (8 * span) == 0 && nblocks > want && nblocks % want == 0 && ((long long)(want / 8 / span) * 256) % hw == 0) {
             gx = (unsigned)want;
             p.persist_iters = (int)(nblocks / want);
         }
     }
     // The streaming 1x1 kernel: 256 workgroups (one per CU), each `iters` tiles 32 / span tile_m apart (same XCD, same weight panel).
-    const int sgrid = stream_grid(), sspan = p.xcd_map == 2 ? tn / p.xcd_gn : 1;
-    const bool stream = plan.stream && p.splits == 1 && (p.xcd_map == 1 || p.xcd_map == 2) && nblocks % sgrid == 0 && (sgrid / 8) % sspan == 0;
-    if (stream) {
-        p.persist_iters = (int)(nblocks / sgrid);
-        p.persist_dm = (sgrid / 8 / sspan) * BM;
-        p.persist_d1 = (unsigned)((long long)p.persist_dm * a.C1 * es);
-        p.persist_d2 = (unsigned)((long long)p.persist_dm * a.C2 * es);
-        gx = (unsigned)sgrid;
-    }
+    // A launch that asked for it keeps the 128 x 192 kernel unless it is unsplit, on map 1 or 2, and the grid divides.
+    const int sgrid = stream_grid();
+    const bool stream = pick.stream && p.splits == 1 && (p.xcd_map == 1 || p.xcd_map == 2) && nblocks % sgrid == 0 && (sgrid / 8) % span == 0;
+    if (stream) walk128(sgrid);
     // The lean wide epilogue (epilogue_wide, LEANM = 1): f32 storage on the 32 x 32 tiles, EVERY wave tile of the launch whole along M and in whole 32-column passes along N, rows in NHWC order,
     // one sample per wave tile under a fused PreNorm, 32-bit byte offsets.  NOPE_EPILOGUE_LEAN=0: the generic row loop everywhere (A/B).
-    p.lean = (dt == NOPE_BF16X3 && dma && plan.small < 0 && p.wide_out && !p.posmajor && !phased && p.splits == 1 && !a.geglu && M % bm == 0 && a.Cout % 32 == 0 &&
+    p.lean = (dt == NOPE_BF16X3 && dma && pick.small < 0 && p.wide_out && !p.posmajor && !phased && p.splits == 1 && !a.geglu && M % bm == 0 && a.Cout % 32 == 0 &&
               (!a.pn_ms || ((long long)p.Hm * p.Wm) % 64 == 0) && (unsigned long long)M * a.Cout * 4ull < 0xffffffffull && NOPE_ENV("NOPE_EPILOGUE_LEAN", 1) != 0) ? 1 : 0;
-    if (p.splits > 1) p.out_amax = nullptr;        // (raw partials: the reduce kernel writes the tensor)
-    const dim3 grid(gx, phased ? 4u : 1u, (unsigned)p.splits), block(NT);
-    const bool trace = NOPE_ENV_SET("NOPE_CONV_TRACE");     // tuning aid: one line per launch
-    if (trace && plan.small >= 0) fprintf(stderr, "conv small%d mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u xcd %d/%d\n", plan.small, a.mode, a.ntaps, Cin, a.Cout, M,
-                                        p.tiles_m, p.tiles_n, grid.x, grid.y, grid.z, p.xcd_map, p.xcd_gn);
-    else if (trace) fprintf(stderr, "conv %s mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u posmajor %d persist %d xcd %d/%d%s%s\n",
-                       stream ? "stream128" : plan.halo ? "halo256" : plan.pp ? "pp256" : dma ? "dma128" : "generic", a.mode, a.ntaps, Cin, a.Cout, M, p.tiles_m, p.tiles_n, grid.x, grid.y, grid.z,
-                       p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, a.geglu ? " geglu" : x2 ? " x2" : "", p.lean ? " lean" : "");
-    if (plan.small >= 0) {
-        launch_conv_small(dt, &p, plan.small, grid, s);
-    } else if (stream) {
-        launch_conv_stream(dt, &p, grid, s);
-    } else if (plan.pp) {
-        if (NOPE_ENV_SET("NOPE_PP_VARIANT")) p.variant = NOPE_ENV("NOPE_PP_VARIANT", 0);      // tuning ablations of the ping-pong kernel
-        if (plan.halo) launch_conv_halo(x2 ? NOPE_F16X2 : dt, &p, grid, s);
-        else launch_conv_pp(x2 ? NOPE_F16X2 : dt, &p, grid, s);
-    } else if (dt == NOPE_F32) {
-        if (dma) launch_conv_dma_f32(&p, bm, grid, s);
-        else if (p.pn_ms) hipLaunchKernelGGL((conv_gemm_kernel<float, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((conv_gemm_kernel<float, false>), grid, block, 0, s, p);
-    } else if (dt == NOPE_BF16X3) {
-        if (dma) launch_conv_dma_bf16x3(&p, grid, s);
-        else if (p.pn_ms) hipLaunchKernelGGL((conv_gemm_kernel<f32s_t, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((conv_gemm_kernel<f32s_t, false>), grid, block, 0, s, p);
-    } else if (dt == NOPE_F16) {
-        if (dma) launch_conv_dma_f16(&p, grid, s);
-        else if (p.pn_ms) hipLaunchKernelGGL((conv_gemm_kernel<f16_t, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((conv_gemm_kernel<f16_t, false>), grid, block, 0, s, p);
-    } else {
-        if (dma && (bm == 256 || (variant & 2))) launch_conv_dma_bf16_variant(&p, bm, grid, s);
-        else if (dma) launch_conv_dma_bf16(&p, grid, s);
-        else if (p.pn_ms) hipLaunchKernelGGL((conv_gemm_kernel<bf16_t, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((conv_gemm_kernel<bf16_t, false>), grid, block, 0, s, p);
-    }
+    L.grid = dim3(gx, phased ? 4u : 1u, (unsigned)p.splits);
+    L.kind = pick.small >= 0 ? NOPE_CONV_KERNEL_SMALL : stream ? NOPE_CONV_KERNEL_STREAM : pick.halo ? NOPE_CONV_KERNEL_HALO256 : pick.pp ? NOPE_CONV_KERNEL_PP256
+             : dma ? NOPE_CONV_KERNEL_DMA128 : NOPE_CONV_KERNEL_GENERIC;
+    if ((L.kind == NOPE_CONV_KERNEL_HALO256 || L.kind == NOPE_CONV_KERNEL_PP256) && NOPE_ENV_SET("NOPE_PP_VARIANT")) p.variant = NOPE_ENV("NOPE_PP_VARIANT", 0);      // tuning ablations of the ping-pong kernel
+    // executed multiply-adds x2 (position-major launches skip the taps that lie in the padding: (3H-2)(3W-2) of the 9 H W tap instances remain)
+    const double taps = L.posmajor ? (double)(3 * a.Hs - 2) * (3 * a.Ws - 2) / ((double)a.Hs * a.Ws) : (double)a.ntaps;
+    L.flops = 2.0 * (double)a.nhyp * a.Ho * a.Wo * a.Cout * taps * Cin;
+    return L;
+}
+
+// ---- the queries: what would launch_conv do with this layer?  Each reads the plan (of a launch conv_plan rejects: false / generic / 0).
+// Asked per compute mode, as they always were: NOPE_F16X2 is answered as NOPE_BF16X3 (the runtimes launch under that type, with ConvArgs::w_x2).
+static ConvLaunch query(int dt, const ConvArgs& a) { return conv_plan(dt_base(dt), a); }
+bool conv_is_posmajor(int dt, const ConvArgs& a) { return query(dt, a).posmajor; }
+int conv_kernel_kind(int dt, const ConvArgs& a) { return query(dt, a).kind; }
+bool conv_takes_x2(int dt, const ConvArgs& a) { return query(dt, a).x2; }
+bool conv_records_out_amax(int dt, const ConvArgs& a) { return query(dt, a).p.out_amax != nullptr; }
+double conv_executed_flops(int dt, const ConvArgs& a) { return query(dt, a).flops; }
+bool conv_geglu_fusable(int dt, const ConvArgs& a0) {
+    const int mode = NOPE_ENV("NOPE_GEGLU_FUSED", 1);      // (A/B switch of the CALLER's choice; 2: only launches the 128 x 192 kernel would get anyway)
+    if (mode == 0) return false;
+    if (mode == 2) { const int k = query(dt, a0).kind; if (k == NOPE_CONV_KERNEL_PP256 || k == NOPE_CONV_KERNEL_HALO256 || k == NOPE_CONV_KERNEL_SMALL) return false; }
+    ConvArgs a = a0;
+    a.geglu = 1;
+    return query(dt, a).err == NOPE_OK;
+}
+
+// one line per launch (NOPE_CONV_TRACE: tuning aid, and what the tests read)
+static void trace_conv(const ConvLaunch& L) {
+    static const char* const names[] = {"generic", "dma128", "pp256", "halo256", "small", "stream128"};
+    const ConvParams& p = L.p;
+    const int Cin = p.C1 + p.C2;
+    if (L.kind == NOPE_CONV_KERNEL_SMALL) fprintf(stderr, "conv small%d mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u xcd %d/%d\n", L.small, p.mode, p.ntaps, Cin, p.Cout, (long long)p.M,
+                                                 p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z, p.xcd_map, p.xcd_gn);
+    else fprintf(stderr, "conv %s mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u posmajor %d persist %d xcd %d/%d%s%s\n",
+                 names[L.kind], p.mode, p.ntaps, Cin, p.Cout, (long long)p.M, p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z,
+                 p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, p.geglu ? " geglu" : L.x2 ? " x2" : "", p.lean ? " lean" : "");
+}
+
+#define LAUNCH_GENERIC(T) \
+    do { if (p.pn_ms) hipLaunchKernelGGL((conv_gemm_kernel<T, true>), grid, block, 0, s, p); else hipLaunchKernelGGL((conv_gemm_kernel<T, false>), grid, block, 0, s, p); } while (0)
+int launch_conv(const ConvLaunch& L, hipStream_t s) {
+    if (L.err != NOPE_OK) return L.err;
+    if (NOPE_ENV_SET("NOPE_CONV_TRACE")) trace_conv(L);
+    const ConvParams& p = L.p;
+    const int dt = L.dt;
+    const dim3 grid = L.grid, block(NT);
+    if (L.kind == NOPE_CONV_KERNEL_SMALL) launch_conv_small(dt, &p, L.small, grid, s);
+    else if (L.kind == NOPE_CONV_KERNEL_STREAM) launch_conv_stream(dt, &p, grid, s);
+    else if (L.kind == NOPE_CONV_KERNEL_HALO256) launch_conv_halo(L.x2 ? NOPE_F16X2 : dt, &p, grid, s);
+    else if (L.kind == NOPE_CONV_KERNEL_PP256) launch_conv_pp(L.x2 ? NOPE_F16X2 : dt, &p, grid, s);
+    else if (L.kind == NOPE_CONV_KERNEL_DMA128) {
+        if (dt == NOPE_F32) launch_conv_dma_f32(&p, L.bm, grid, s);
+        else if (dt == NOPE_BF16X3) launch_conv_dma_bf16x3(&p, grid, s);
+        else if (dt == NOPE_F16) launch_conv_dma_f16(&p, grid, s);
+        else if (L.bm == 256 || (p.variant & 2)) launch_conv_dma_bf16_variant(&p, L.bm, grid, s);
+        else launch_conv_dma_bf16(&p, grid, s);
+    } else if (dt == NOPE_F32) LAUNCH_GENERIC(float);      // any channel counts: the register-staged kernel
+    else if (dt == NOPE_BF16X3) LAUNCH_GENERIC(f32s_t);
+    else if (dt == NOPE_F16) LAUNCH_GENERIC(f16_t);
+    else LAUNCH_GENERIC(bf16_t);
     NOPE_CHECK_LAUNCH();
-    if (p.splits > 1 && a.colstats) {          // (tap-resident split-K only: plan.hsplit)
-        const dim3 rg((unsigned)(M / a.stat_rows), (unsigned)cdiv(a.Cout, 64));      // (splits <= 16, stat_rows in {16, 32, 64})
-        if (dt_es(dt) == 4) hipLaunchKernelGGL((splitk_reduce_stats_kernel<float>), rg, dim3(256), 0, s, p.split_out, p.splits, (int)M, a.Cout, a.bias, a.act, (float*)a.out, a.colstats, a.stat_rows);
-        else if (dt == NOPE_F16) hipLaunchKernelGGL((splitk_reduce_stats_kernel<f16_t>), rg, dim3(256), 0, s, p.split_out, p.splits, (int)M, a.Cout, a.bias, a.act, (f16_t*)a.out, a.colstats, a.stat_rows);
-        else hipLaunchKernelGGL((splitk_reduce_stats_kernel<bf16_t>), rg, dim3(256), 0, s, p.split_out, p.splits, (int)M, a.Cout, a.bias, a.act, (bf16_t*)a.out, a.colstats, a.stat_rows);
+    if (L.reduce == CONV_REDUCE_STATS) {
+        const dim3 rg((unsigned)(p.M / p.stat_rows), (unsigned)cdiv(p.Cout, 64));      // (splits <= 16, stat_rows in {16, 32, 64})
+        if (dt_es(dt) == 4) hipLaunchKernelGGL((splitk_reduce_stats_kernel<float>), rg, dim3(256), 0, s, p.split_out, p.splits, p.M, p.Cout, p.bias, p.act, (float*)p.out, p.colstats, p.stat_rows);
+        else if (dt == NOPE_F16) hipLaunchKernelGGL((splitk_reduce_stats_kernel<f16_t>), rg, dim3(256), 0, s, p.split_out, p.splits, p.M, p.Cout, p.bias, p.act, (f16_t*)p.out, p.colstats, p.stat_rows);
+        else hipLaunchKernelGGL((splitk_reduce_stats_kernel<bf16_t>), rg, dim3(256), 0, s, p.split_out, p.splits, p.M, p.Cout, p.bias, p.act, (bf16_t*)p.out, p.colstats, p.stat_rows);
         NOPE_CHECK_LAUNCH();
-    } else if (p.splits > 1) {
-        const size_t MN = (size_t)M * a.Cout;
-        const unsigned rb = (unsigned)((MN + 255) / 256 < 4096 ? (MN + 255) / 256 : 4096);
-        if (dt_es(dt) == 4) hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3(rb), dim3(256), 0, s, p.split_out, p.splits, (int)M, a.Cout,
-                                               a.bias, (const float*)a.resid, a.act, (float*)a.out, a.out_nchw, a.Ho * a.Wo);
-        else if (dt == NOPE_F16) hipLaunchKernelGGL((splitk_reduce_kernel<f16_t>), dim3(rb), dim3(256), 0, s, p.split_out, p.splits, (int)M, a.Cout,
-                                a.bias, (const f16_t*)a.resid, a.act, (f16_t*)a.out, a.out_nchw, a.Ho * a.Wo);
-        else hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(rb), dim3(256), 0, s, p.split_out, p.splits, (int)M, a.Cout,
-                                a.bias, (const bf16_t*)a.resid, a.act, (bf16_t*)a.out, a.out_nchw, a.Ho * a.Wo);
+    } else if (L.reduce == CONV_REDUCE_PLAIN) {
+        const size_t MN = (size_t)p.M * p.Cout;
+        const dim3 rg((unsigned)((MN + 255) / 256 < 4096 ? (MN + 255) / 256 : 4096));
+        const int HWo = p.Ho * p.Wo;
+        if (dt_es(dt) == 4) hipLaunchKernelGGL((splitk_reduce_kernel<float>), rg, dim3(256), 0, s, p.split_out, p.splits, p.M, p.Cout, p.bias, (const float*)p.resid, p.act, (float*)p.out, p.out_nchw, HWo);
+        else if (dt == NOPE_F16) hipLaunchKernelGGL((splitk_reduce_kernel<f16_t>), rg, dim3(256), 0, s, p.split_out, p.splits, p.M, p.Cout, p.bias, (const f16_t*)p.resid, p.act, (f16_t*)p.out, p.out_nchw, HWo);
+        else hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), rg, dim3(256), 0, s, p.split_out, p.splits, p.M, p.Cout, p.bias, (const bf16_t*)p.resid, p.act, (bf16_t*)p.out, p.out_nchw, HWo);
         NOPE_CHECK_LAUNCH();
     }
     return NOPE_OK;
 }
+#undef LAUNCH_GENERIC
+
+int launch_conv(int dt, const ConvArgs& a, hipStream_t s) { return launch_conv(conv_plan(dt, a), s); }
 
 }  // namespace nope

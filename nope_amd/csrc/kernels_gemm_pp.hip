@@ -1194,7 +1194,7 @@ void launch_conv_halo(int dt, const void* params, dim3 grid, hipStream_t s) {
             }
         return;
     }
-    if (p.mode == NOPE_CONV_UP2P) {                    // the four phase convs of an up-sampling (plan_conv: f32 storage only)
+    if (p.mode == NOPE_CONV_UP2P) {                    // the four phase convs of an up-sampling (conv_plan: f32 storage only)
         if (dt == NOPE_F16X2 && p.x2_t_zero) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, false, false, false, true>), grid, block, 0, s, p);
         else if (dt == NOPE_F16X2) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, false, true, false, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((conv3x3_halo_kernel<f32s_t, false, false, true, false, true>), grid, block, 0, s, p);

@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256 * KG) void conv_gemm_small_kernel(ConvParams p)
             const int m = m0 + row, n = n0 + c;
             if (m >= p.M) continue;
             float v = pan[row * LDP + c] + (p.bias ? p.bias[n] : 0.f);
-            if (p.resid) v += Elt<T>::ld(reinterpret_cast<const T*>(p.resid) + (size_t)m * p.Cout + n);      // (NHWC residual, as the generic epilogue; a fused PreNorm never reaches this kernel with an NCHW output: plan_small)
+            if (p.resid) v += Elt<T>::ld(reinterpret_cast<const T*>(p.resid) + (size_t)m * p.Cout + n);      // (NHWC residual, as the generic epilogue; a fused PreNorm never reaches this kernel with an NCHW output: small_tile, kernels_gemm.hip)
             if (p.act) v = v > 0.f ? v : 0.f;
             const int b = m / HWo;
             const size_t o = ((size_t)b * p.Cout + n) * HWo + (m - b * HWo);
@@ -523,7 +523,7 @@ void launch_conv_small(int dt, const void* params, int tile, dim3 grid, hipStrea
         else launch_small_t<T, 1, 1, 3>(p, grid, s);                           \
     } while (0)
     if (dt == NOPE_F32) NOPE_SMALL_T(float);
-    else if (dt == NOPE_BF16X3 && p.x2_scale) NOPE_SMALL_T(f16x2_t);      // the layer's second pack: launch_conv took it (plan_takes_x2)
+    else if (dt == NOPE_BF16X3 && p.x2_scale) NOPE_SMALL_T(f16x2_t);      // the layer's second pack: launch_conv took it (conv_plan)
     else if (dt == NOPE_BF16X3) NOPE_SMALL_T(f32s_t);
     else if (dt == NOPE_F16) NOPE_SMALL_T(f16_t);
     else NOPE_SMALL_T(bf16_t);

@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "nope_common.h"
+#include "conv_plan.h"      // (nope_common.h; ConvLaunch)
 #include "x2_range.h"
 
 namespace nope {
@@ -170,14 +170,15 @@ template <class N> struct FwdCore {
         ca.nhyp = n < 0 ? nhyp : n; ca.out_nchw = out_nchw; ca.out_dt = out_dt;
         if (a.C != c.Cin) { chk(NOPE_ERR_ARG); return; }
         if (c.w_x2 && !net->x2r.off) { ca.w_x2 = c.w_x2; ca.x2_t_zero = net->x2r.t_zero(c.x2_id) ? 1 : 0; }
+        const ConvLaunch L = conv_plan(net->dt, ca);
         if (tracking()) {
-            if (ca.w_x2 && conv_takes_x2(net->dt, ca)) {      // the two-pass tile: the layer's range shift follows its input's maximum
+            if (L.x2) {      // the two-pass tile: the layer's range shift follows its input's maximum
                 x2.consumes(c.x2_id, x2.slot_for(a.p, (size_t)(ca.nhyp / rep) * a.H * a.W * a.C));
                 chk(x2.err);
             }
             x2.overwritten(out);           // (conv epilogues record no maximum here: a two-pass consumer of `out` takes an absmax pass)
         }
-        chk(launch_conv(net->dt, ca, s));
+        chk(launch_conv(L, s));
     }
     // y = [silu](GroupNorm(G, eps)(x))
     void gn(const NormW& nm, int G, const void* x, void* y, int HW, int act, float eps, const float* film = nullptr, int film_stride = 0) {

@@ -178,8 +178,9 @@ struct Fwd : rt::FwdCore<nope_unet> {
         }
         struct Release { Arena& a; size_t m; ~Release() { a.off = m; } } release{ar, sk_mark};
         if (!live()) return;               // workspace-size query: only the arena bookkeeping above matters
+        ConvLaunch L = conv_plan(net->dt, ca);      // planned once: the range tracking, the profile and the launch read the same decisions
         if (tracking()) {
-            if (ca.w_x2 && c.x2_id >= 0 && conv_takes_x2(net->dt, ca)) {      // this launch runs the two-pass tile: its layer's shift follows its inputs' maxima
+            if (L.x2 && c.x2_id >= 0) {      // this launch runs the two-pass tile: its layer's shift follows its inputs' maxima
                 x2.consumes(c.x2_id, x2.slot_for(a.p, (size_t)(n / rep1) * a.H * a.W * a.C));
                 if (b) x2.consumes(c.x2_id, x2.slot_for(b->p, (size_t)(n / rep2) * b->H * b->W * b->C));
                 chk(x2.err);
@@ -187,29 +188,26 @@ struct Fwd : rt::FwdCore<nope_unet> {
             // `track_out`: this conv's output goes straight into f16x2 convs (the resampling convs, the bottleneck attention's output
             // projection): its epilogue records max |out| when it is one that can (the wide NHWC epilogue); otherwise a later f16x2
             // consumer of `out` takes an absmax pass over it
-            ConvArgs probe = ca;
-            probe.out_amax = net->x2r.amax;
-            if (track_out && conv_records_out_amax(net->dt, probe)) {
+            if (track_out && L.records_out_amax) {
                 const int sl = x2.produce(out);
-                if (sl >= 0) ca.out_amax = x2.slot_ptr(sl);
+                if (sl >= 0) L.record_out_amax(x2.slot_ptr(sl));
             } else x2.overwritten(out);
         }
         if (net->profile) {
             nope_unet::Ev ev;
             hipEventCreate(&ev.a); hipEventCreate(&ev.b);
-            ev.flops = conv_executed_flops(net->dt, ca);   // executed MACs (UP2P: 4 taps per output pixel; padding taps of small maps skipped)
+            ev.flops = L.flops;   // executed MACs (UP2P: 4 taps per output pixel; padding taps of small maps skipped)
             // algorithmic HBM bytes: every input, weight and output element exactly once
             ev.bytes = ((double)(n / rep1) * a.H * a.W * a.C + (b ? (double)(n / rep2) * a.H * a.W * b->C : 0.0) +
                         (double)c.Cout * c.ntaps * c.Cin * (c.mode == NOPE_CONV_UP2P ? 4 : 1) + (double)n * Ho * Wo * c.Cout) * (double)es;
-            ev.info = nope_conv_launch_info{0.0, ev.flops, ev.bytes, conv_kernel_kind(net->dt, ca), c.mode, c.ntaps, c.Cin, c.Cout, a.H, a.W, n,
-                                            net->dt != NOPE_BF16X3 ? 1 : conv_takes_x2(net->dt, ca) ? 2 : 3,
-                                            conv_is_posmajor(net->dt, ca) ? 1 : 0};
+            ev.info = nope_conv_launch_info{0.0, ev.flops, ev.bytes, L.kind, c.mode, c.ntaps, c.Cin, c.Cout, a.H, a.W, n,
+                                            net->dt != NOPE_BF16X3 ? 1 : L.x2 ? 2 : 3, L.posmajor ? 1 : 0};
             hipEventRecord(ev.a, s);
-            chk(launch_conv(net->dt, ca, s));
+            chk(launch_conv(L, s));
             hipEventRecord(ev.b, s);
             net->evs.push_back(ev);
         } else {
-            chk(launch_conv(net->dt, ca, s));
+            chk(launch_conv(L, s));
         }
     }
     // y = act(GN(x)) [+emb] [+resid]; x holds n_x = nhyp / x_rep samples; `colstats` != null: statistics were

@@ -113,7 +113,7 @@ def run_x2(hip, dev, tiles=(0, 1, 3)):
     d = lambda x: x.to(dev)
     C = 32
     worst = 0.0
-    os.environ["NOPE_X2_SMALL"] = "1"          # (off by default: measured slower than bf16x3 on this kernel, kernels_gemm.hip: plan_takes_x2)
+    os.environ["NOPE_X2_SMALL"] = "1"          # (off by default: measured slower than bf16x3 on this kernel, kernels_gemm.hip: conv_plan)
 
     def both(fn, what, want, want32):
         nonlocal worst

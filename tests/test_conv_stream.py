@@ -1,6 +1,6 @@
 """Round 6: (i) the lean wide epilogue of the f32-storage modes (epilogue_wide, LEANM = 1; LEAN instantiations of the 128 x 192, streaming,
 per-tap and tap-resident kernels) -- bit-identical to the generic row loop it replaces; (ii) the streaming 1x1 kernel
-(kernels_gemm_stream.hip; off by default, see plan_conv) -- bit-identical to the 128 x 192 kernel.  Reference operators: the 1x1 convs of
+(kernels_gemm_stream.hip; off by default, see conv_plan) -- bit-identical to the 128 x 192 kernel.  Reference operators: the 1x1 convs of
 LinearAttention / Attention / ResnetBlock.res_conv (model_utils.py:269,373-374,399-401) and every 3x3 conv of Block (:240).
 
 CPU: the kernel sources run under tests/hipemu in its adversarial settings (LDS-DMA landing as late as the counted vmcnt waits allow, waves
