@@ -84,9 +84,10 @@ typedef void* nope_stream_t;
  * 11: nope_op_conv_stat_rows, nope_op_conv_ex, nope_op_group_norm_ex, nope_op_gn_apply_blocks, nope_op_gn_finalize, nope_op_absmax_f32,
  *     nope_op_amax_slot_words -- the fused GroupNorm statistics / PreNorm / range-slot plumbing at operator level;
  * 12: nope_vis_column, nope_op_vis_grid, nope_op_vis_sheet, NOPE_VIS_*;
- * 13: nope_op_crop_frames).  Callers compare nope_abi_version() against the header they were
+ * 13: nope_op_crop_frames;
+ * 14: nope_op_group_norm_shared, nope_op_conv_class_weights).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 13
+#define NOPE_ABI_VERSION 14
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -500,6 +501,20 @@ int nope_op_group_norm_ex(int dtype, const void* x, void* y, float* partial, con
                           int emb_stride, const float* film, int film_stride, const void* resid, int x_rep, int resid_rep, float* out_stats,
                           float eps, int fast_silu, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
 int nope_op_gn_finalize(const float* partial, float* ms, int n_hyp, int nchunk, float count, float eps, nope_stream_t s);
+/* nope_op_group_norm_shared: nope_op_group_norm_ex with a shared addend -- the value that is normalised is
+ *     x_eff[j][p][c] = x[j][p][c] + sh_s[j / sh_rep][p][c] + sh_e[j][cls(p)][c],   j in [0, n_hyp), p = y W + x,
+ *   cls(p) = 3 (y == 0 ? 0 : y == H - 1 ? 2 : 1) + (x == 0 ? 0 : x == W - 1 ? 2 : 1), the border class of the pixel; sh_s f32 NHWC
+ *   [n_hyp / sh_rep][H W][C], sh_e f32 [n_hyp][9][C], both 16-byte aligned.  Two forms exist, the ones the U-Net's schedule launches under
+ *   NOPE_SHARED_SPLIT: sh_s + sh_e with x = NULL (H, W >= 2), and x + sh_s with sh_e = NULL; SiLU on (act_silu = 1); any other combination is
+ *   NOPE_ERR_UNSUPPORTED.  x_eff is never stored: a statistics pass forms it into `partial` (n_hyp * nope_op_gn_chunks() * G * 2 floats), the
+ *   apply pass forms it again and continues as nope_op_group_norm_ex does (emb, resid / resid_rep, out_stats, fast_silu, the range maximum).
+ * nope_op_conv_class_weights: w [Cout][Cin][3][3] f32 -> out [9][Cout][Cin] f32, out[cls][co][ci] = the sum of w[co][ci] over the taps a
+ *   zero-padded 3x3 conv has inside the map at a pixel of border class cls: conv(u + e 1) = conv(u) + out[cls(p)] e for e constant over the map. */
+int nope_op_group_norm_shared(int dtype, const void* x, void* y, float* partial, const float* sh_s, int sh_rep, const float* sh_e, int H, int W,
+                              const float* gamma, const float* beta, int n_hyp, int C, int G, int act_silu, const float* emb, int emb_stride,
+                              const void* resid, int resid_rep, float* out_stats, float eps, int fast_silu, uint32_t* amax_slot, float* amax_out,
+                              nope_stream_t s);
+int nope_op_conv_class_weights(const float* w, float* out, int Cout, int Cin, nope_stream_t s);
 /* max |x[i]| over n f32 values (NaNs ignored; 0 for n = 0 or all zeros): what the runtimes run over conv-produced tensors in NOPE_F16X2. */
 int nope_op_absmax_f32(const float* x, size_t n, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
 /* LinearAttention core (model_utils.py:403-416) and Attention core (:376-389) on a fused

@@ -240,6 +240,28 @@ int nope_op_group_norm_ex(int dtype, const void* x, void* y, float* partial, con
     return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
 }
 
+int nope_op_group_norm_shared(int dtype, const void* x, void* y, float* partial, const float* sh_s, int sh_rep, const float* sh_e, int H, int W,
+                              const float* gamma, const float* beta, int n_hyp, int C, int G, int act_silu, const float* emb, int emb_stride,
+                              const void* resid, int resid_rep, float* out_stats, float eps, int fast_silu, uint32_t* amax_slot, float* amax_out,
+                              nope_stream_t s) {
+    if (n_hyp <= 0 || H <= 0 || W <= 0 || (amax_slot != nullptr) != (amax_out != nullptr) || !partial) return NOPE_ERR_ARG;
+    if (!sh_s && !sh_e) return NOPE_ERR_ARG;          // (nope_op_group_norm_ex is the entry without a shared addend)
+    GnApplyArgs a;
+    a.x = x; a.y = y; a.partial = partial; a.gamma = gamma; a.beta = beta;
+    a.nhyp = n_hyp; a.HW = H * W; a.C = C; a.G = G; a.act = act_silu; a.emb = emb; a.emb_stride = emb_stride;
+    a.resid = resid; a.resid_rep = resid_rep; a.out_stats = out_stats; a.eps = eps; a.fast_silu = fast_silu; a.amax_out = amax_slot;
+    a.sh_s = sh_s; a.sh_rep = sh_rep; a.sh_e = sh_e; a.sh_H = H; a.sh_W = W;
+    a.nchunk = gn_stats_chunks(a.HW, C, dtype);
+    if (const int e = launch_gn_stats_shared(dtype, a, partial, a.nchunk, (hipStream_t)s)) return e;
+    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
+    if (const int e = launch_gn_apply(dtype, a, (hipStream_t)s)) return e;
+    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
+}
+
+int nope_op_conv_class_weights(const float* w, float* out, int Cout, int Cin, nope_stream_t s) {
+    return launch_pack_conv_classes(w, out, Cout, Cin, (hipStream_t)s);
+}
+
 int nope_op_linear_attention(int dtype, const void* qkv, void* out, int n_hyp, int HW, int heads, int dim_head, nope_stream_t s) {
     return launch_linattn(dtype, qkv, out, n_hyp, HW, heads, dim_head, (hipStream_t)s);
 }

@@ -286,6 +286,20 @@ __global__ __launch_bounds__(NT) void linear_naive_kernel(const float* __restric
     }
 }
 
+// out[cls][co][ci] = sum of w[co][ci][ky][kx] over the taps a zero-padded 3x3 conv has inside the map at a pixel of border class
+// cls = cy * 3 + cx (c* = 0: first row / column, tap 0 outside; 2: last, tap 2 outside; 1: all three inside), in tap order.
+__global__ __launch_bounds__(NT) void pack_conv_classes_kernel(const float* __restrict__ w, float* __restrict__ out, size_t rows) {
+    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < 9 * rows; i += (size_t)gridDim.x * NT) {
+        const int cls = (int)(i / rows), cy = cls / 3, cx = cls % 3;
+        const float* t = w + (i % rows) * 9;
+        float a = 0.f;
+        for (int ky = 0; ky < 3; ++ky)
+            for (int kx = 0; kx < 3; ++kx)
+                if (!(cy == 0 && ky == 0) && !(cy == 2 && ky == 2) && !(cx == 0 && kx == 0) && !(cx == 2 && kx == 2)) a += t[ky * 3 + kx];
+        out[i] = a;
+    }
+}
+
 inline unsigned grid_for(size_t n) {
     size_t g = (n + NT - 1) / NT;
     if (g > 8192) g = 8192;
@@ -339,6 +353,14 @@ int launch_pack_conv_w(int dt, const float* w, void* out, int Cout, int Cin, int
     }
     const size_t total = (size_t)Cout * ntaps * Cin;
     NOPE_DISPATCH_W(dt, T, hipLaunchKernelGGL((pack_conv_w_kernel<T>), dim3(grid_for(total)), dim3(NT), 0, s, w, (T*)out, Cin, ntaps, mode, total, cin_scale, cout_scale, csrc));
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
+int launch_pack_conv_classes(const float* w, float* out, int Cout, int Cin, hipStream_t s) {
+    if (!w || !out || Cout <= 0 || Cin <= 0) return NOPE_ERR_ARG;
+    const size_t rows = (size_t)Cout * Cin;
+    hipLaunchKernelGGL(pack_conv_classes_kernel, dim3(grid_for(9 * rows)), dim3(NT), 0, s, w, out, rows);
     NOPE_CHECK_LAUNCH();
     return NOPE_OK;
 }

@@ -8,6 +8,9 @@
 // follows block1 (:274-276), the residual add of ResnetBlock (:279), PreNorm's
 // GroupNorm(1, C) (:226-234) and Residual (:198-204).  Both passes are pure streaming
 // (16-byte loads, every byte touched once), i.e. HBM-bound.
+// Shared addend (GnApplyArgs::sh_*, template parameter SH of both kernels): x is not loaded whole but formed as x + S[n / s_rep] + E[n][cls(p)]
+// from f32 tensors shared between hypotheses -- the U-Net's NOPE_SHARED_SPLIT schedule, which convolves pose-independent inputs once per
+// reference image (unet_runtime.hip).  Both passes form the same value; everything behind it is the code of the plain form.
 #include "nope_common.h"
 
 namespace nope {
@@ -16,13 +19,40 @@ namespace {
 
 constexpr int NT = 256;
 
+// Which taps of a zero-padded 3x3 conv fall inside an H x W map at pixel (y, x): {top, middle, bottom} x {left, middle, right}, H, W >= 2.
+__device__ __forceinline__ int border_class(int y, int x, int H, int W) {
+    return (y == 0 ? 0 : (y == H - 1 ? 2 : 1)) * 3 + (x == 0 ? 0 : (x == W - 1 ? 2 : 1));
+}
+
+// The VEC values of x_eff at element offset o = pix * C + coff of a sample (gn_apply_kernel's SH forms; sb / eb9: this sample's S and E rows)
+template <class T, int SH>
+__device__ __forceinline__ void shared_x_eff(float* v, const T* xb, const float* sb, const float* eb9, size_t o, size_t coff, int pix, int C, int H, int W) {
+    constexpr int VEC = Elt<T>::VEC;
+    if (SH == 2) Elt<T>::unpack(ld16(xb + o), v);
+    const float* ep = nullptr;
+    if (SH == 1) { const int y = pix / W; ep = eb9 + (size_t)border_class(y, pix - y * W, H, W) * C + coff; }
+#pragma unroll
+    for (int k = 0; k < VEC; k += 4) {
+        const f32x4 s4 = *reinterpret_cast<const f32x4*>(sb + o + k);
+        if (SH == 1) {
+            const f32x4 e4 = *reinterpret_cast<const f32x4*>(ep + k);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[k + i] = s4[i] + e4[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[k + i] += s4[i];
+        }
+    }
+}
+
 // Each thread owns one 16-byte channel vector (tid % tpr) and walks the chunk's pixels with
 // stride `rows`.  FASTG: C/VEC <= 256 and channels-per-group is a multiple of VEC, so a
 // vector belongs to exactly one group; partials are folded by two fixed-shape LDS trees
 // (over pixel rows, then over the vectors of a group) -- deterministic, no atomics.
-template <class T, bool FASTG>
+// SH != 0: the statistics of x_eff, the shared form gn_apply_kernel<SH> normalises (one entry of `partial` per hypothesis).
+template <class T, bool FASTG, int SH = 0>
 __global__ __launch_bounds__(NT) void gn_stats_kernel(const T* __restrict__ x, float* __restrict__ partial, int HW, int C,
-                                                      int G, int nchunk) {
+                                                      int G, int nchunk, GnShared sh) {
     constexpr int VEC = Elt<T>::VEC;
     __shared__ float red_s[FASTG ? NT : 2048];
     __shared__ float red_q[FASTG ? NT : 2048];
@@ -33,6 +63,8 @@ __global__ __launch_bounds__(NT) void gn_stats_kernel(const T* __restrict__ x, f
     const int p1 = (p0 + pchunk < HW) ? p0 + pchunk : HW;
     const int cpg = C / G;
     const T* xb = x + (size_t)hyp * HW * C;
+    const float* sb = SH != 0 ? sh.S + (size_t)(hyp / sh.s_rep) * HW * C : nullptr;
+    const float* eb9 = SH == 1 ? sh.E + (size_t)hyp * 9 * C : nullptr;
     float* outp = partial + ((size_t)hyp * nchunk + chunk) * G * 2;
 
     if (FASTG) {
@@ -44,7 +76,8 @@ __global__ __launch_bounds__(NT) void gn_stats_kernel(const T* __restrict__ x, f
         if (row < rows) {
             for (int pix = p0 + row; pix < p1; pix += rows) {
                 float v[VEC];
-                Elt<T>::unpack(ld16(xb + (size_t)pix * C + lc * VEC), v);
+                if constexpr (SH != 0) shared_x_eff<T, SH>(v, xb, sb, eb9, (size_t)pix * C + lc * VEC, (size_t)lc * VEC, pix, C, sh.H, sh.W);
+                else Elt<T>::unpack(ld16(xb + (size_t)pix * C + lc * VEC), v);
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) { s += v[e]; q += v[e] * v[e]; }
             }
@@ -77,7 +110,12 @@ __global__ __launch_bounds__(NT) void gn_stats_kernel(const T* __restrict__ x, f
         for (int c = tid; c < C; c += NT) {
             float s = 0.f, q = 0.f;
             for (int pix = p0; pix < p1; ++pix) {
-                const float v = Elt<T>::ld(xb + (size_t)pix * C + c);
+                float v;
+                if constexpr (SH != 0) {
+                    v = sb[(size_t)pix * C + c];
+                    if (SH == 2) v = Elt<T>::ld(xb + (size_t)pix * C + c) + v;
+                    else { const int y = pix / sh.W; v += eb9[(size_t)border_class(y, pix - y * sh.W, sh.H, sh.W) * C + c]; }
+                } else v = Elt<T>::ld(xb + (size_t)pix * C + c);
                 s += v; q += v * v;
             }
             red_s[c] = s; red_q[c] = q;
@@ -158,13 +196,18 @@ template <bool FAST> __device__ __forceinline__ f32x2 silu2(f32x2 t) {
 // FOLD: `partial` holds the producing conv's column statistics [x sample][nchunk row blocks][C][2] and every workgroup folds its
 // sample's itself, in gn_fold_kernel's order (same bits) -- for small batches, where a separate fold launch costs more than the
 // few KiB every workgroup re-reads.
-template <class T, bool FAST, bool OS, bool FILM, bool ACT, bool RES, int U, bool FOLD>
+// SH (the shared addend, GnShared): the value that is normalised is formed here instead of loaded whole --
+//   SH = 1: x_eff[n][p][c] = S[n / s_rep][p][c] + E[n][cls(p)][c]   (x is not read)
+//   SH = 2: x_eff[n][p][c] = x[n][p][c] + S[n / s_rep][p][c]
+// S and E are f32; cls(p) = border_class(y, x, H, W).  Everything after x_eff is the code of SH = 0 (apply_v below); the statistics
+// come from gn_stats_shared_kernel, which forms the same x_eff.
+template <class T, bool FAST, bool OS, bool FILM, bool ACT, bool RES, int U, bool FOLD, int SH = 0>
 __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ partial,
                                                       int nchunk, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       int HW, int C, int G, const float* __restrict__ emb, int emb_stride,
                                                       const T* __restrict__ resid, float eps, int blocks_per_hyp, int x_rep, int resid_rep,
                                                       float* __restrict__ out_stats, const float* __restrict__ film, int film_stride,
-                                                      unsigned* __restrict__ amax_out) {
+                                                      unsigned* __restrict__ amax_out, GnShared shd) {
     constexpr int VEC = Elt<T>::VEC, V2 = VEC / 2;
     // AMAX (the f32-storage instantiations with the fast SiLU = the split-precision modes): max |y| over what this workgroup writes, for the
     // range shifts of the NOPE_F16X2 convs that consume y (unet_runtime.hip) -- one v_max3_f32 per two values in a kernel that waits for HBM
@@ -263,9 +306,8 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
 #pragma unroll
             for (int e = 0; e < VEC; ++e) coeff(e, (cv * VEC + e) / cpg);
         }
-        auto apply = [&](const u32x4 xa, const u32x4 xr) -> u32x4 {
-            float v[VEC], r[VEC];
-            Elt<T>::unpack(xa, v);
+        auto apply_v = [&](float* v, const u32x4 xr) -> u32x4 {      // v: the VEC values to normalise (x, or x_eff of the shared form)
+            float r[VEC];
             if (RES) Elt<T>::unpack(xr, r);
 #pragma unroll
             for (int q = 0; q < V2; ++q) {
@@ -279,8 +321,36 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
             }
             return Elt<T>::pack(v);
         };
+        auto apply = [&](const u32x4 xa, const u32x4 xr) -> u32x4 {
+            float v[VEC];
+            Elt<T>::unpack(xa, v);
+            return apply_v(v, xr);
+        };
         const size_t coff = (size_t)cv * VEC;
         int pix = p0 + row;
+        if constexpr (SH != 0) {
+            const float* sb = shd.S + (size_t)(hyp / shd.s_rep) * HW * C;
+            const float* eb9 = SH == 1 ? shd.E + (size_t)hyp * 9 * C : nullptr;
+            for (; pix + (U - 1) * rows < p1; pix += U * rows) {
+                float v[U][VEC];
+                u32x4 xr[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const size_t o = (size_t)(pix + u * rows) * C + coff;
+                    shared_x_eff<T, SH>(v[u], xb, sb, eb9, o, coff, pix + u * rows, C, shd.H, shd.W);
+                    xr[u] = RES ? ld16(rb + o) : u32x4{0u, 0u, 0u, 0u};
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) st16(yb + (size_t)(pix + u * rows) * C + coff, apply_v(v[u], xr[u]));
+            }
+            for (; pix < p1; pix += rows) {
+                const size_t o = (size_t)pix * C + coff;
+                float v[VEC];
+                shared_x_eff<T, SH>(v, xb, sb, eb9, o, coff, pix, C, shd.H, shd.W);
+                const u32x4 xr = RES ? ld16(rb + o) : u32x4{0u, 0u, 0u, 0u};
+                st16(yb + o, apply_v(v, xr));
+            }
+        } else
         for (; pix + (U - 1) * rows < p1; pix += U * rows) {       // U pixels in flight per thread
             u32x4 xa[U], xr[U];
 #pragma unroll
@@ -356,8 +426,35 @@ int launch_gn_stats(int dt, const void* x, float* partial, int nhyp, int HW, int
     const bool fast = (cpg % vec == 0) && (cvecs <= NT);
     if (!fast && C > 2048) return NOPE_ERR_UNSUPPORTED;
     dim3 grid((unsigned)(nhyp * nchunk)), block(NT);
-    if (fast) NOPE_DISPATCH_T(dt, T, hipLaunchKernelGGL((gn_stats_kernel<T, true>), grid, block, 0, s, (const T*)x, partial, HW, C, G, nchunk));
-    else NOPE_DISPATCH_T(dt, T, hipLaunchKernelGGL((gn_stats_kernel<T, false>), grid, block, 0, s, (const T*)x, partial, HW, C, G, nchunk));
+    if (fast) NOPE_DISPATCH_T(dt, T, hipLaunchKernelGGL((gn_stats_kernel<T, true>), grid, block, 0, s, (const T*)x, partial, HW, C, G, nchunk, GnShared()));
+    else NOPE_DISPATCH_T(dt, T, hipLaunchKernelGGL((gn_stats_kernel<T, false>), grid, block, 0, s, (const T*)x, partial, HW, C, G, nchunk, GnShared()));
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
+// 0: no shared addend; 1: S + E without x; 2: x + S; -1: a combination no kernel has
+static int gn_shared_form(const GnApplyArgs& a) {
+    if (!a.sh_s && !a.sh_e) return 0;
+    if (!a.sh_s || a.sh_rep < 1 || a.nhyp % a.sh_rep || a.x_rep != 1 || a.sh_H < 1 || a.sh_W < 1 || (long long)a.sh_H * a.sh_W != a.HW) return -1;
+    if (((uintptr_t)a.sh_s | (uintptr_t)a.sh_e) & 15 || a.C % 4) return -1;
+    if (a.sh_e) return (a.x || a.sh_H < 2 || a.sh_W < 2) ? -1 : 1;
+    return a.x ? 2 : -1;
+}
+
+int launch_gn_stats_shared(int dt, const GnApplyArgs& a, float* partial, int nchunk, hipStream_t s) {
+    const int form = gn_shared_form(a);
+    if (form <= 0 || !partial || a.nhyp <= 0 || a.HW <= 0 || a.C <= 0 || a.G <= 0 || a.C % a.G || nchunk < 1) return NOPE_ERR_ARG;
+    const int vec = dt_vec(dt);
+    if (a.C % vec || a.G > 64) return NOPE_ERR_UNSUPPORTED;
+    const int cpg = a.C / a.G, cvecs = a.C / vec;
+    const bool fast = (cpg % vec == 0) && (cvecs <= NT);
+    if (!fast && a.C > 2048) return NOPE_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)(a.nhyp * nchunk)), block(NT);
+    const GnShared sh{a.sh_s, a.sh_e, a.sh_rep, a.sh_H, a.sh_W};
+#define NOPE_GN_STATS_SH(FASTG, SH) NOPE_DISPATCH_T(dt, T, hipLaunchKernelGGL((gn_stats_kernel<T, FASTG, SH>), grid, block, 0, s, (const T*)a.x, partial, a.HW, a.C, a.G, nchunk, sh))
+    if (form == 1) { if (fast) NOPE_GN_STATS_SH(true, 1); else NOPE_GN_STATS_SH(false, 1); }
+    else           { if (fast) NOPE_GN_STATS_SH(true, 2); else NOPE_GN_STATS_SH(false, 2); }
+#undef NOPE_GN_STATS_SH
     NOPE_CHECK_LAUNCH();
     return NOPE_OK;
 }
@@ -558,7 +655,9 @@ int launch_gn_finalize(const float* partial, float* ms, int nhyp, int nchunk, fl
 
 int launch_gn_apply(int dt, const GnApplyArgs& a, hipStream_t s) {
     const bool fold = a.colstats != nullptr;
-    if (!a.x || !a.y || (!a.partial && !fold) || !a.gamma || !a.beta || a.nhyp <= 0 || a.C % a.G) return NOPE_ERR_ARG;
+    const int form = gn_shared_form(a);
+    if (form < 0) return NOPE_ERR_UNSUPPORTED;
+    if ((!a.x && form != 1) || !a.y || (!a.partial && !fold) || !a.gamma || !a.beta || a.nhyp <= 0 || a.C % a.G) return NOPE_ERR_ARG;
     if (fold && (a.stat_blocks < 1 || a.C > 2048 || a.film)) return NOPE_ERR_ARG;
     const int vec = dt_vec(dt);
     if (a.C % vec || a.G > 64) return NOPE_ERR_UNSUPPORTED;
@@ -569,7 +668,7 @@ int launch_gn_apply(int dt, const GnApplyArgs& a, hipStream_t s) {
 #define NOPE_GN_APPLY_F(T, FAST, OS, FILM, ACT, RES, U, FOLD)                                                                    \
     hipLaunchKernelGGL((gn_apply_kernel<T, FAST, OS, FILM, ACT, RES, U, FOLD>), grid, block, 0, s, (const T*)a.x, (T*)a.y,       \
                        FOLD ? a.colstats : a.partial, FOLD ? a.stat_blocks : a.nchunk, a.gamma, a.beta, a.HW, a.C, a.G, a.emb,   \
-                       a.emb_stride, (const T*)a.resid, a.eps, bph, a.x_rep, a.resid_rep, a.out_stats, a.film, a.film_stride, a.amax_out)
+                       a.emb_stride, (const T*)a.resid, a.eps, bph, a.x_rep, a.resid_rep, a.out_stats, a.film, a.film_stride, a.amax_out, GnShared())
 #define NOPE_GN_APPLY_U(T, FAST, OS, FILM, ACT, RES, U)                                                                          \
     do { if (!FILM && fold) NOPE_GN_APPLY_F(T, FAST, OS, false, ACT, RES, U, true); else NOPE_GN_APPLY_F(T, FAST, OS, FILM, ACT, RES, U, false); } while (0)
 #define NOPE_GN_APPLY_AR(T, FAST, OS, FILM, ACT, RES) NOPE_GN_APPLY_U(T, FAST, OS, FILM, ACT, RES, 2)   /* (4 in flight: +-0) */
@@ -579,6 +678,30 @@ int launch_gn_apply(int dt, const GnApplyArgs& a, hipStream_t s) {
         else     { if (res) NOPE_GN_APPLY_AR(T, FAST, OS, FILM, false, true); else NOPE_GN_APPLY_AR(T, FAST, OS, FILM, false, false); } \
     } while (0)
     if (a.film && a.out_stats) return NOPE_ERR_UNSUPPORTED;
+    if (form > 0) {
+        // the shared addend: the forms the U-Net's schedule launches -- SiLU, statistics from gn_stats_shared (`partial`), no FiLM
+        if (!act || fold || a.film || !a.partial) return NOPE_ERR_UNSUPPORTED;
+        const GnShared sh{a.sh_s, a.sh_e, a.sh_rep, a.sh_H, a.sh_W};
+#define NOPE_GN_SH_F(T, FAST, OS, RES, SH)                                                                                       \
+    hipLaunchKernelGGL((gn_apply_kernel<T, FAST, OS, false, true, RES, 2, false, SH>), grid, block, 0, s, (const T*)a.x, (T*)a.y, \
+                       a.partial, a.nchunk, a.gamma, a.beta, a.HW, a.C, a.G, a.emb, a.emb_stride, (const T*)a.resid, a.eps, bph,   \
+                       1, a.resid_rep, a.out_stats, nullptr, 0, a.amax_out, sh)
+#define NOPE_GN_SH(T, FAST)                                                                                                      \
+    do {                                                                                                                         \
+        if (form == 1) { if (a.out_stats) { if (res) NOPE_GN_SH_F(T, FAST, true, true, 1); else NOPE_GN_SH_F(T, FAST, true, false, 1); }    \
+                         else             { if (res) NOPE_GN_SH_F(T, FAST, false, true, 1); else NOPE_GN_SH_F(T, FAST, false, false, 1); } } \
+        else           { if (a.out_stats) { if (res) NOPE_GN_SH_F(T, FAST, true, true, 2); else NOPE_GN_SH_F(T, FAST, true, false, 2); }    \
+                         else             { if (res) NOPE_GN_SH_F(T, FAST, false, true, 2); else NOPE_GN_SH_F(T, FAST, false, false, 2); } } \
+    } while (0)
+        if (dt == NOPE_F32) { if (a.fast_silu) NOPE_GN_SH(float, true); else NOPE_GN_SH(float, false); }
+        else if (dt == NOPE_BF16) NOPE_GN_SH(bf16_t, true);
+        else if (dt == NOPE_F16) NOPE_GN_SH(f16_t, true);
+        else return NOPE_ERR_UNSUPPORTED;
+#undef NOPE_GN_SH
+#undef NOPE_GN_SH_F
+        NOPE_CHECK_LAUNCH();
+        return NOPE_OK;
+    }
     if (dt == NOPE_F32 && a.fast_silu && !a.film) {
         if (a.out_stats) NOPE_GN_APPLY(float, true, true, false); else NOPE_GN_APPLY(float, true, false, false);
     } else if (dt == NOPE_F32) {
@@ -602,7 +725,7 @@ int launch_gn_apply(int dt, const GnApplyArgs& a, hipStream_t s) {
 // GnApplyArgs::proj_*: the fused tail above.  Eligible: f32 storage with the hardware SiLU (the split-precision modes), SiLU on, statistics folded
 // inline (colstats), no embedding / FiLM / output statistics / shared x, C <= 256 in whole 16-byte vectors, <= 8 output channels.
 bool gn_apply_proj_ok(int dt, const GnApplyArgs& a) {
-    return dt == NOPE_F32 && a.fast_silu && a.act && a.colstats && a.stat_blocks >= 1 && !a.emb && !a.film && !a.out_stats && a.x_rep == 1 &&
+    return dt == NOPE_F32 && a.fast_silu && a.act && a.colstats && a.stat_blocks >= 1 && !a.emb && !a.sh_s && !a.sh_e && !a.film && !a.out_stats && a.x_rep == 1 &&
            a.C % 4 == 0 && a.C <= 256 && a.G >= 1 && a.G <= 64 && a.C % a.G == 0 && a.proj_cout >= 1 && a.proj_cout <= 8 && a.proj_w && a.proj_out &&
            (a.proj_out_dt == NOPE_F32 || a.proj_out_dt == NOPE_F16 || a.proj_out_dt == NOPE_BF16) && NOPE_ENV("NOPE_FINAL_FUSED", 1) != 0;
 }

@@ -381,6 +381,8 @@ int conv_stat_rows(int dt, const ConvArgs& a);        // rows per block of the f
 double conv_executed_flops(int dt, const ConvArgs& a);
 
 int launch_gn_stats(int dt, const void* x, float* partial, int nhyp, int HW, int C, int G, int nchunk, hipStream_t s);
+// the shared addend as the GroupNorm kernels receive it (GnApplyArgs::sh_*)
+struct GnShared { const float* S = nullptr; const float* E = nullptr; int s_rep = 1, H = 0, W = 0; };
 struct GnApplyArgs {
     const void* x = nullptr; void* y = nullptr;
     const float* partial = nullptr; int nchunk = 1;
@@ -396,6 +398,13 @@ struct GnApplyArgs {
     int x_rep = 1;                     // x (and its statistics) shared by x_rep consecutive hypotheses
     int resid_rep = 1;                 // resid shared by resid_rep consecutive hypotheses
     float* out_stats = nullptr;        // optional [nhyp][gn_apply_blocks()][2]: (sum, sum sq) of the values written
+    // Shared addend: the value that is normalised is x_eff[n][p][c] = x[n][p][c] + sh_s[n / sh_rep][p][c] + sh_e[n][cls(p)][c], cls(p) the border class
+    // ({top, middle, bottom} x {left, middle, right}) of pixel p on the sh_H x sh_W map.  Two forms exist: sh_s + sh_e with x = null (a 3x3 conv of
+    // a per-reference map plus a per-hypothesis constant, unet_runtime.hip) and x + sh_s (a conv over a concat whose second half is per reference).
+    // SiLU on, x_rep = 1, statistics from launch_gn_stats_shared in `partial`.
+    const float* sh_s = nullptr; int sh_rep = 1;      // f32 NHWC [nhyp / sh_rep][HW][C]
+    const float* sh_e = nullptr;                      // f32 [nhyp][9][C]; needs sh_H, sh_W >= 2
+    int sh_H = 0, sh_W = 0;
     float eps = 1e-5f;
     unsigned* amax_out = nullptr;      // f32 storage + fast_silu only (the split-precision modes): a range slot (kX2SlotWords words, amax_publish) for max |y| of what this launch writes
     // gn_apply_proj only (kernels_norm.hip: GroupNorm + SiLU + residual + a 1x1 projection to <= 8 channels in one pass, NCHW out; y is not written):
@@ -408,6 +417,7 @@ struct GnApplyArgs {
                                        // IEEE division -- set by the runtimes in the split-precision modes (bf16x3, f16x2), whose bar is 1e-4, not bit parity
 };
 int launch_gn_apply(int dt, const GnApplyArgs& a, hipStream_t s);
+int launch_gn_stats_shared(int dt, const GnApplyArgs& a, float* partial, int nchunk, hipStream_t s);   // the statistics of x_eff, [nhyp][nchunk][G][2]
 bool gn_apply_proj_ok(int dt, const GnApplyArgs& a);          // would launch_gn_apply_proj take these arguments?
 int launch_gn_apply_proj(int dt, const GnApplyArgs& a, hipStream_t s);
 bool conv_records_out_amax(int dt, const ConvArgs& a);     // would launch_conv's kernel fill a.out_amax? (kernels_gemm.hip)
@@ -440,6 +450,9 @@ int launch_bn_fold(const float* gamma, const float* beta, const float* mean, con
 int launch_stem_pack(const float* w, const float* scale, float* out, hipStream_t s);
 int launch_stem_conv(int dt, const float* img, const float* w_packed, const float* shift, void* out, int n_img, int H, int W,
                      hipStream_t s);
+// the nine border-class weights of a 3x3 conv, w [Cout][Cin][3][3] f32 -> out [9][Cout][Cin] f32 (a 1x1 GEMM weight of 9 Cout rows): a
+// zero-padded conv of a map that is constant e[ci] gives sum_ci out[cls(p)][co][ci] e[ci] at pixel p (kernels_misc.hip)
+int launch_pack_conv_classes(const float* w, float* out, int Cout, int Cin, hipStream_t s);
 int launch_rowsum(int dt, const void* packed, float* out, int rows, int K, hipStream_t s);
 int launch_linear_naive(const float* in, const float* w, const float* bias, float* out, int M, int N, int K, int act_in,
                         int ldo, hipStream_t s);

@@ -13,6 +13,14 @@
 //     init_conv, the skip `r`, and conv+GroupNorm+SiLU of downs[0][0].block1 (the embedding is
 //     only added after that activation, model_utils.py:272-276) -- the reference re-runs all
 //     of it, and the ResNet encoder, N times (model.py:115,219);
+//   * NOPE_SHARED_SPLIT (read per forward; bit 0 | bit 1, default 3, 0 = neither; f32 activation storage, x_rep > 1, maps of >= 2 x 2):
+//     two 3x3 convs further down still multiplied per-reference data once per template.  Bit 0, downs[0][0].block2: its input is
+//     u + e_n 1 with u per reference and e_n the block's embedding row, so conv2 = S + E[n][border class of the pixel] with S = conv2(u) +
+//     bias per reference and E a 512 x 192 x 1728 f32 GEMM against the nine border-class weights; the per-template conv launch is gone and
+//     the block's last GroupNorm forms S + E itself (kernels_norm.hip, the shared addend).  Bit 1, final_res_block.block1: its input is
+//     cat(cur, r) with r per reference, so conv = conv(W[:, :C], cur) + Sr, Sr = conv(W[:, C:], r) + bias per reference; the per-template
+//     launch has half the K and the GroupNorm that follows forms cur' + Sr.  Summation order changes, nothing else: the shared parts run
+//     in f32 / bf16x3 even under NOPE_F16X2 (Fwd::resnet);
 //   * the 19 per-block `Linear(SiLU(c))` embeddings (model_utils.py:261-265,274-275) are one
 //     f32 GEMM against the row-concatenated weights;
 //   * a bump arena over caller-provided workspace: no allocation, no host sync, one stream.
@@ -34,7 +42,12 @@ using rt::PackedConv;
 
 namespace {
 
-struct Res { PackedConv c1, c2, res; NormW n1, n2; bool has_res = false; int emb_off = -1; };
+struct Res {
+    PackedConv c1, c2, res; NormW n1, n2; bool has_res = false; int emb_off = -1;
+    // NOPE_SHARED_SPLIT (see the file header), f32 activation storage only:
+    float* c2_cls = nullptr;       // downs[0][0]: block2's nine border-class weights [9 * Cout][Cout] f32 (launch_pack_conv_classes)
+    PackedConv c1_hyp, c1_ref;     // final_res_block: block1 split by input channels -- the up path's half (no bias) and the skip r's half (with the bias)
+};
 // PreNorm's GroupNorm(1) is folded into the qkv conv: gamma into the packed weights, c0 = W beta, c1 = W gamma
 // (f32 [3*heads*dim_head]); mean / rstd enter in the conv epilogue.
 struct LinAttn { NormW pre, post; PackedConv qkv, out; float *c0 = nullptr, *c1 = nullptr; };
@@ -74,6 +87,7 @@ struct nope_unet : rt::Net {      // (dt / sdt / x2 / x2r / allocs: rt::Net, run
     mutable std::vector<UGraph> graphs;
     mutable bool graphs_ok = true;           // cleared when capture is unavailable: direct launches from then on
     mutable std::mutex graph_mu;
+    mutable int graph_split = -1;            // NOPE_SHARED_SPLIT the cached graphs were captured under
     mutable int graph_replays = 0;           // forwards served by a graph replay since create (tests assert the path really ran)
     long long graph_max = 0;                 // largest n_hyp * H * W that replays a graph; 0 = off
 };
@@ -99,6 +113,25 @@ struct Loader : rt::LoaderCore {
                             (ksz == 3 || ksz == 1 || mode != NOPE_CONV_PLAIN) && !cin_scale && Csrc == Cin && Cin % 32 == 0;
         return pack_conv(d, pfx, Csrc, Cin, Cout, (mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_UP2P) ? 4 : ksz * ksz, mode, has_bias, second,
                          convT ? 16 : 0, -1, cin_scale);
+    }
+    // NOPE_SHARED_SPLIT, create time.  The nine border-class weights of a 3x3 conv as a 1x1 GEMM weight [9 * Cout][Cin] f32 (Res::c2_cls):
+    float* conv_classes(const std::string& pfx, int Cin, int Cout) {
+        const nope_tensor_desc* d = get(pfx + "weight", {Cout, Cin, 3, 3});
+        float* out = (float*)dmalloc((size_t)9 * Cout * Cin * 4);
+        if (d && out) chk(launch_pack_conv_classes(d->data, out, Cout, Cin, s));
+        return out;
+    }
+    // ... and a 3x3 conv over input channels [c0, c0 + Cin) of a stored [Cout][Ctot][3][3] weight (Res::c1_hyp / c1_ref): those rows are
+    // staged contiguously and packed like any conv's (`second`: with the NOPE_F16X2 pack and a layer id of its own)
+    PackedConv conv_cin_range(const std::string& pfx, int Ctot, int c0, int Cin, int Cout, bool has_bias, bool second) {
+        const nope_tensor_desc* d = get(pfx + "weight", {Cout, Ctot, 3, 3});
+        const size_t rb = (size_t)Cin * 9 * 4;
+        float* st = (float*)tmalloc((size_t)Cout * rb);
+        if (!d || !st) return PackedConv();
+        if (hipMemcpy2DAsync(st, rb, d->data + (size_t)c0 * 9, (size_t)Ctot * 9 * 4, rb, (size_t)Cout, hipMemcpyDeviceToDevice, s) != hipSuccess) chk(NOPE_ERR_LAUNCH);
+        nope_tensor_desc sd = *d;
+        sd.data = st;
+        return pack_conv(&sd, pfx, Cin, Cin, Cout, 9, NOPE_CONV_PLAIN, has_bias, second && net->x2 && Cin % 32 == 0);
     }
     // qkv conv of an attention block with its PreNorm folded in (see LinAttn)
     void prenorm_qkv(const std::string& p, int C, int N, NormW& pre, PackedConv& qkv, float*& c0, float*& c1) {
@@ -137,6 +170,12 @@ struct Fwd : rt::FwdCore<nope_unet> {
     float* pn_partial = nullptr;   // (sum, sum sq) partials of the tensor that feeds the next attention block
     float* pn_ms = nullptr;        // its per-hypothesis (mean, rstd)
     const float* emb_all = nullptr;
+    int split = 0;                 // NOPE_SHARED_SPLIT of this forward: bit 0 = downs[0][0].block2, bit 1 = final_res_block.block1
+
+    // run `fn` as a forward over n samples (the per-reference launches: profiled, traced and range-tracked like every other)
+    template <class F> void over(int n, F fn) { const int keep = nhyp; nhyp = n; fn(); nhyp = keep; }
+    // a conv's packed weights without the NOPE_F16X2 pack: the per-reference launches stay on the three-pass kernels
+    static PackedConv exact(PackedConv c) { c.w_x2 = nullptr; c.x2_id = -1; return c; }
 
     // out = conv(a [cat b]) (+bias) (+resid);  n = number of samples computed (nhyp or fewer).  `stats`: also emit the column
     // statistics of the output when this launch can (conv_stat_rows: whole 64-row blocks per sample on every kernel, 16 / 32-pixel
@@ -215,12 +254,19 @@ struct Fwd : rt::FwdCore<nope_unet> {
     // proj (with proj_out): GroupNorm + SiLU + residual + this 1x1 conv in one pass (launch_gn_apply_proj: y is not written) when the arguments
     // qualify; returns whether it did -- the caller launches the conv itself otherwise
     bool gn(const NormW& nm, int G, const void* x, int x_rep, void* y, int HW, int act, int emb_off, const void* resid,
-            int resid_rep, const Stats& st = Stats(), float* out_stats = nullptr, const PackedConv* proj = nullptr, void* proj_out = nullptr, int proj_out_dt = NOPE_F32) {
+            int resid_rep, const Stats& st = Stats(), float* out_stats = nullptr, const PackedConv* proj = nullptr, void* proj_out = nullptr, int proj_out_dt = NOPE_F32,
+            const GnShared* sh = nullptr) {
         if (!live()) return false;
         const int nx = nhyp / x_rep;
         int nch = 1;
         GnApplyArgs ga;
-        if (st.cs) {
+        ga.x = x; ga.nhyp = nhyp; ga.HW = HW; ga.C = nm.C; ga.G = G; ga.x_rep = x_rep;
+        if (sh) {
+            // the shared addend (GnApplyArgs::sh_*): x_eff = [x] + S [+ E] is formed by the statistics pass and by the apply pass, never stored
+            ga.sh_s = sh->S; ga.sh_e = sh->E; ga.sh_rep = sh->s_rep; ga.sh_H = sh->H; ga.sh_W = sh->W;
+            nch = gn_stats_chunks(HW, nm.C, net->sdt);
+            chk(launch_gn_stats_shared(net->sdt, ga, gn_partial, nch, s));
+        } else if (st.cs) {
             // Every gn_apply workgroup folds its sample's column statistics itself (st.blocks * C * 8 bytes out of L2 per workgroup; a
             // separate fold launch costs ~7 us + a kernel boundary).  Round 2 measured the inline fold +0.25 ms per 512-hypothesis step
             // (one thread per group then); with the wave-wide group sums of round 4 it is -0.02 .. -0.05 ms there and -0.2 ms at 64
@@ -233,10 +279,9 @@ struct Fwd : rt::FwdCore<nope_unet> {
             nch = gn_stats_chunks(HW, nm.C, net->sdt);
             chk(launch_gn_stats(net->sdt, x, gn_partial, nx, HW, nm.C, G, nch, s));
         }
-        ga.x = x; ga.y = y; ga.partial = gn_partial; ga.nchunk = nch; ga.gamma = nm.gamma; ga.beta = nm.beta;
-        ga.nhyp = nhyp; ga.HW = HW; ga.C = nm.C; ga.G = G; ga.act = act;
+        ga.y = y; ga.partial = gn_partial; ga.nchunk = nch; ga.gamma = nm.gamma; ga.beta = nm.beta; ga.act = act;
         if (emb_off >= 0) { ga.emb = emb_all + emb_off; ga.emb_stride = net->emb_total; }
-        ga.resid = resid; ga.x_rep = x_rep; ga.resid_rep = resid_rep; ga.out_stats = out_stats;
+        ga.resid = resid; ga.resid_rep = resid_rep; ga.out_stats = out_stats;
         if (tracking()) { const int sl = x2.produce(y); if (sl >= 0) ga.amax_out = x2.slot_ptr(sl); }
         ga.fast_silu = net->dt != NOPE_F32 ? 1 : 0;      // (f32 storage of the split-precision modes: hardware exp / rcp; the f32 mode keeps expf and the division)
         if (proj && proj_out && net->final_w_raw) {
@@ -261,9 +306,50 @@ struct Fwd : rt::FwdCore<nope_unet> {
         const int HW = a.H * a.W, G = net->cfg.groups;
         const size_t M = (size_t)nhyp * HW;
         const size_t mark = ar.off;
-        void* t1 = alloc_act(M * R.c1.Cout);
         const int emb_off = use_emb ? R.emb_off : -1;
-        if (a.rep > 1 && !b) {
+        const bool f32_acts = net->sdt == NOPE_F32 && a.H >= 2 && a.W >= 2;      // (S and E are f32; a 1-pixel-wide map has no nine border classes)
+        if (a.rep > 1 && !b && (split & 1) && !R.has_res && R.c2_cls && use_emb && f32_acts) {
+            // downs[0][0] with NOPE_SHARED_SPLIT bit 0: block2 convolves u + e_n 1, u = SiLU(GN(block1(x0))) per reference and e_n this block's
+            // embedding row, constant over the map.  By linearity conv2(u + e_n 1)[p] = S[p] + E[n][cls(p)]: S = conv2(u) + bias once per
+            // reference, E = e_n against the nine border-class weights (one small f32 GEMM).  The per-hypothesis conv, the pass that expanded
+            // u to nhyp copies and the read of the conv output by its GroupNorm are gone; x_eff is formed inside the two GroupNorm passes.
+            const int ns = nhyp / a.rep, C = R.c2.Cout;
+            void* t1s = alloc_act((size_t)ns * HW * C);
+            void* us = alloc_act((size_t)ns * HW * C);
+            float* S = (float*)alloc_act((size_t)ns * HW * C);
+            float* erows = alloc_f32((size_t)nhyp * C);
+            float* E = alloc_f32((size_t)nhyp * 9 * C);
+            over(ns, [&] {
+                Stats cs;
+                conv(R.c1, a, nullptr, t1s, a.H, a.W, ns, 1, 1, nullptr, 0, NOPE_F32, &cs);
+                gn(R.n1, G, t1s, 1, us, HW, 1, -1, nullptr, 1, cs);
+                Act u{us, C, a.H, a.W, 1};
+                conv(exact(R.c2), u, nullptr, S, a.H, a.W, ns, 1, 1);
+            });
+            if (live()) {
+                if (hipMemcpy2DAsync(erows, (size_t)C * 4, emb_all + emb_off, (size_t)net->emb_total * 4, (size_t)C * 4, (size_t)nhyp, hipMemcpyDeviceToDevice, s) != hipSuccess)
+                    chk(NOPE_ERR_LAUNCH);
+                ConvArgs ea;   // E[nhyp][9 * C] = e @ Wcls^T, exact-f32 MFMA as emb_all
+                ea.src1 = erows; ea.C1 = C; ea.w = R.c2_cls; ea.out = E; ea.Cout = 9 * C; ea.nhyp = nhyp;
+                chk(launch_conv(NOPE_F32, ea, s));
+            }
+            const GnShared sh{S, E, a.rep, a.H, a.W};
+            gn(R.n2, G, nullptr, 1, out, HW, 1, -1, a.p, a.rep, Stats(), next_is_attention ? pn_partial : nullptr, nullptr, nullptr, NOPE_F32, &sh);
+            ar.off = mark;
+            return false;
+        }
+        void* t1 = alloc_act(M * R.c1.Cout);
+        if (b && b->rep > 1 && a.rep == 1 && (split & 2) && R.c1_hyp.w && R.c1_ref.w && f32_acts) {
+            // final_res_block with NOPE_SHARED_SPLIT bit 1: block1 convolves cat(cur, r), r = x0 per reference.  By linearity over the input
+            // channels conv(W, cat(cur, r)) = conv(W[:, :C1], cur) + Sr, Sr = conv(W[:, C1:], r) + bias once per reference: the per-hypothesis
+            // launch has half the K.  The epilogue's column statistics no longer see the whole GroupNorm input: a statistics pass forms cur' + Sr.
+            const int ns = nhyp / b->rep;
+            float* Sr = (float*)alloc_act((size_t)ns * HW * R.c1.Cout);
+            over(ns, [&] { conv(exact(R.c1_ref), *b, nullptr, Sr, a.H, a.W, ns, 1, 1); });
+            conv(R.c1_hyp, a, nullptr, t1, a.H, a.W, nhyp, 1, 1);
+            const GnShared sh{Sr, nullptr, b->rep, a.H, a.W};
+            gn(R.n1, G, t1, 1, t1, HW, 1, emb_off, nullptr, 1, Stats(), nullptr, nullptr, nullptr, NOPE_F32, &sh);
+        } else if (a.rep > 1 && !b) {
             // pose-independent prefix: conv + GN statistics once per reference sample
             const int ns = nhyp / a.rep;
             void* t1s = alloc_act((size_t)ns * HW * R.c1.Cout);
@@ -333,11 +419,12 @@ struct Fwd : rt::FwdCore<nope_unet> {
 };
 
 int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, const float* pose, int n_hyp, int H, int W,
-                void* out, int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak) {
+                void* out, int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak, int split) {
     const nope_unet_config& cfg = net->cfg;
     const int L = cfg.n_levels;
     Fwd f;
     f.begin(net, n_hyp, ws, ws_bytes, s, dry);
+    f.split = split;
     const int HW = H * W;
     const int* dims = net->dims;
 
@@ -521,6 +608,7 @@ int nope_unet_create(const nope_unet_config* cfg, const nope_tensor_desc* tensor
         const std::string p = "downs." + std::to_string(l) + ".";
         Level& D = net->downs[l];
         D.r0 = ld.res(p + "0.", dims[l], dims[l], true, embs);
+        if (l == 0 && net->sdt == NOPE_F32) D.r0.c2_cls = ld.conv_classes(p + "0.block2.proj.", dims[0], dims[0]);
         D.r1 = ld.res(p + "1.", dims[l], dims[l], true, embs);
         D.attn = linattn(p + "2.", dims[l]);
         if (l < L - 1 && cfg->soft_up_down) D.resample = ld.conv(p + "3.", dims[l], dims[l + 1], 4, NOPE_CONV_STRIDE2, true);   // Conv2d(4, 2, 1)
@@ -543,6 +631,11 @@ int nope_unet_create(const nope_unet_config* cfg, const nope_tensor_desc* tensor
         else U.resample = ld.conv(p + "3.", dims[r + 1], dims[r], 3, NOPE_CONV_PLAIN, true);
     }
     net->final_res = ld.res("final_res_block.", cfg->u_net_dim * 2, cfg->u_net_dim, true, embs);
+    if (net->sdt == NOPE_F32) {
+        const int C = cfg->u_net_dim;
+        net->final_res.c1_hyp = ld.conv_cin_range("final_res_block.block1.proj.", 2 * C, 0, C, C, false, true);
+        net->final_res.c1_ref = ld.conv_cin_range("final_res_block.block1.proj.", 2 * C, C, C, C, true, false);
+    }
     net->final_conv0 = ld.res("final_conv.0.", cfg->u_net_dim, cfg->u_net_dim, false, embs);
     net->final_conv1 = ld.conv("final_conv.1.", cfg->u_net_dim, cfg->out_dim, 1, NOPE_CONV_PLAIN, true);
     net->final_w_raw = ld.copy_f32("final_conv.1.weight", {cfg->out_dim, cfg->u_net_dim, 1, 1});
@@ -664,7 +757,11 @@ size_t nope_unet_workspace_bytes(const nope_unet* net, int n_hyp, int n_src, int
     if (!net || n_src <= 0 || n_hyp % n_src) return 0;
     if (check_shape(net, n_hyp, n_src, n_hyp / n_src, H, W) != NOPE_OK) return 0;
     size_t peak = 0;
-    run_forward(net, nullptr, n_src, n_hyp / n_src, nullptr, n_hyp, H, W, nullptr, NOPE_F32, nullptr, 0, nullptr, true, &peak);
+    for (int split = 0; split <= 3; split += 3) {      // NOPE_SHARED_SPLIT is read per forward: the workspace holds either schedule
+        size_t pk = 0;
+        run_forward(net, nullptr, n_src, n_hyp / n_src, nullptr, n_hyp, H, W, nullptr, NOPE_F32, nullptr, 0, nullptr, true, &pk, split);
+        if (pk > peak) peak = pk;
+    }
     size_t xb, pb, ob;
     return unet_stage_bytes(net, n_hyp, n_src, H, W, xb, pb, ob) + align_up(peak, 256) + 256;
 }
@@ -687,9 +784,15 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
     const bool want_graph = net->graph_max > 0 && net->graphs_ok && !net->profile && avail > sb && (long long)n_hyp * H * W <= net->graph_max &&
                             !(net->x2 && net->x2r.active());
     rt::x2_poll_before_forward(net, stream);
+    const int split = NOPE_ENV("NOPE_SHARED_SPLIT", 3) & 3;
     if (!want_graph)
-        return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr);
+        return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr, split);
     std::lock_guard<std::mutex> lock(net->graph_mu);
+    if (net->graph_split != split) {           // the launch plan changes: cached graphs are stale (as in nope_unet_x2_enable)
+        for (const UGraph& g : net->graphs) hipGraphExecDestroy(g.exec);
+        net->graphs.clear();
+        net->graph_split = split;
+    }
 
     float* x_s = (float*)base;
     float* pose_s = (float*)(base + xb);
@@ -702,16 +805,16 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
     if (!hit) {
         {   // dry pass: fail on a too-small arena BEFORE a capture is open
             size_t peak = 0;
-            e = run_forward(net, nullptr, n_src, x_rep, nullptr, n_hyp, H, W, nullptr, out_dtype, nullptr, 0, nullptr, true, &peak);
+            e = run_forward(net, nullptr, n_src, x_rep, nullptr, n_hyp, H, W, nullptr, out_dtype, nullptr, 0, nullptr, true, &peak, split);
             if (e) return e;
             if (align_up(peak, 256) > arena_bytes) return NOPE_ERR_WORKSPACE;
         }
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
             (void)hipGetLastError();
             net->graphs_ok = false;
-            return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr);
+            return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr, split);
         }
-        e = run_forward(net, x_s, n_src, x_rep, pose_s, n_hyp, H, W, out_s, out_dtype, arena, arena_bytes, s, false, nullptr);
+        e = run_forward(net, x_s, n_src, x_rep, pose_s, n_hyp, H, W, out_s, out_dtype, arena, arena_bytes, s, false, nullptr, split);
         hipGraph_t graph = nullptr;
         const hipError_t ce = hipStreamEndCapture(s, &graph);
         hipGraphExec_t exec = nullptr;
@@ -719,7 +822,7 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
             if (graph) hipGraphDestroy(graph);
             (void)hipGetLastError();
             net->graphs_ok = false;
-            return e != NOPE_OK ? e : run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr);
+            return e != NOPE_OK ? e : run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr, split);
         }
         hipGraphDestroy(graph);
         if (net->graphs.size() >= 16) { hipGraphExecDestroy(net->graphs.front().exec); net->graphs.erase(net->graphs.begin()); }

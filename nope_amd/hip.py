@@ -15,7 +15,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 13                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 14                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -114,6 +114,9 @@ _PROTOS = {
     "nope_op_group_norm_ex": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, C.c_float, _i,
                                    _vp, _vp, _vp]),
     "nope_op_gn_finalize": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp]),
+    "nope_op_group_norm_shared": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_float, _i,
+                                       _vp, _vp, _vp]),
+    "nope_op_conv_class_weights": (_i, [_vp, _vp, _i, _i, _vp]),
     "nope_op_absmax_f32": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "nope_op_linear_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_op_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -1153,6 +1156,51 @@ def op_group_norm_ex(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.
     if want_amax:
         extras["amax"] = float(amax.item())
     return y, extras
+
+
+def op_group_norm_shared(dt: int, x: Optional[torch.Tensor], sh_s: torch.Tensor, sh_e: Optional[torch.Tensor], gamma: torch.Tensor,
+                         beta: torch.Tensor, groups: int, n_hyp: int, act_silu: bool = True, emb: Optional[torch.Tensor] = None,
+                         resid: Optional[torch.Tensor] = None, resid_rep: int = 1, out_stats: bool = False, eps: float = 1e-5,
+                         fast_silu: bool = False, want_amax: bool = False):
+    """GroupNorm of x_eff = x + sh_s[j / sh_rep] + sh_e[j][border class of the pixel] through nope_op_group_norm_shared (include/nope_hip.h).
+    sh_s f32 NHWC [n_s][h][w][C] shared by n_hyp / n_s consecutive hypotheses; sh_e f32 (n_hyp, 9, C) or None; x NHWC [n_hyp][h][w][C] of
+    the storage type, or None.  Returns y (storage type), or (y, extras) as op_group_norm_ex."""
+    ns, h, w, c = sh_s.shape
+    assert sh_s.dtype == torch.float32 and sh_s.is_contiguous() and n_hyp % ns == 0
+    assert sh_e is None or (sh_e.dtype == torch.float32 and sh_e.is_contiguous() and tuple(sh_e.shape) == (n_hyp, 9, c))
+    assert x is None or (tuple(x.shape) == (n_hyp, h, w, c) and x.is_contiguous())
+    l = lib()
+    dt = storage_code(dt)
+    g, b = _f32c(gamma), _f32c(beta)
+    e = None if emb is None else _f32c(emb)
+    partial = torch.empty((n_hyp, l.dll.nope_op_gn_chunks(dt, h * w, c), groups, 2), dtype=torch.float32, device=sh_s.device)
+    y = torch.empty((n_hyp, h, w, c), dtype=torch_dtype(dt), device=sh_s.device)
+    os_ = torch.empty((n_hyp, op_gn_apply_blocks(dt, h * w, c, n_hyp), 2), dtype=torch.float32, device=sh_s.device) if out_stats else None
+    slot, amax = _amax_scratch(sh_s.device) if want_amax else (None, None)
+    l.check(l.dll.nope_op_group_norm_shared(dt, _ptr(x), _ptr(y), _ptr(partial), _ptr(sh_s), n_hyp // ns, _ptr(sh_e), h, w, _ptr(g), _ptr(b),
+                                            n_hyp, c, groups, int(act_silu), _ptr(e), 0 if e is None else e.shape[1], _ptr(resid), resid_rep,
+                                            _ptr(os_), float(eps), int(fast_silu), _ptr(slot), _ptr(amax), _stream(sh_s)),
+            "nope_op_group_norm_shared")
+    if not (out_stats or want_amax):
+        return y
+    extras = {}
+    if out_stats:
+        extras["out_stats"] = os_
+    if want_amax:
+        extras["amax"] = float(amax.item())
+    return y, extras
+
+
+def op_conv_class_weights(w: torch.Tensor) -> torch.Tensor:
+    """The nine border-class weights [9][Cout][Cin] f32 of a 3x3 conv weight [Cout][Cin][3][3] (nope_op_conv_class_weights)."""
+    require_device(w)
+    w = _f32c(w)
+    cout, cin = w.shape[:2]
+    assert tuple(w.shape[2:]) == (3, 3)
+    out = torch.empty((9, cout, cin), dtype=torch.float32, device=w.device)
+    l = lib()
+    l.check(l.dll.nope_op_conv_class_weights(_ptr(w), _ptr(out), cout, cin, _stream(w)), "nope_op_conv_class_weights")
+    return out
 
 
 def op_gn_finalize(partial: torch.Tensor, count: float, eps: float = 1e-5) -> torch.Tensor:
