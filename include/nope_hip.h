@@ -85,9 +85,10 @@ typedef void* nope_stream_t;
  *     nope_op_amax_slot_words -- the fused GroupNorm statistics / PreNorm / range-slot plumbing at operator level;
  * 12: nope_vis_column, nope_op_vis_grid, nope_op_vis_sheet, NOPE_VIS_*;
  * 13: nope_op_crop_frames;
- * 14: nope_op_group_norm_shared, nope_op_conv_class_weights).  Callers compare nope_abi_version() against the header they were
+ * 14: nope_op_group_norm_shared, nope_op_conv_class_weights;
+ * 15: nope_op_refine_init / _normal_eq / _normal_eq_workspace_bytes / _step / _select, NOPE_REFINE_*).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 14
+#define NOPE_ABI_VERSION 15
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -144,6 +145,58 @@ int nope_topk_merge(const float* cand_vals, const int64_t* cand_idx, int64_t* id
  *             bit 1 = an index outside [0, N). */
 int nope_op_geodesic(const double* poses, int64_t pose_stride_b, int N, const int64_t* idx, const double* gt, const int* symmetry,
                      double* err_rad, int* status, int B, int k, nope_stream_t stream);
+
+/* (ABI 15) Sub-grid pose refinement: Gauss-Newton on SO(3) through the U-Net.  No reference counterpart: the reference's prediction is
+ * template_poses[nearest_idx] (src/model/model.py:352-354), a vertex of the template grid (26 templates: ~32 degrees apart).  The U-Net is a
+ * smooth function of a continuous rotation and its training loss is the distance between its output and the query's embedding
+ * (model.py:96-111), so a caller can descend on || u_net(reference_feat, dR) - query_feat ||^2 from the retrieved candidates.  There is no
+ * autograd behind this ABI: the Jacobian is a central difference over left-multiplied tangent steps, six extra hypotheses per candidate.
+ * A candidate (b, j) carries dR (3 x 3 row-major f64).  The caller's loop (nope_amd/model.py: PoseConditional.refine_from_feat):
+ *     nope_op_refine_init                                  dR = GramSchmidt(all_relativeR[b, idx[b, j]]), first seven poses
+ *     iters x { nope_unet_forward on poses (B, 7k, 6) -> maps (B, k, 7, C, h, w) f32;  nope_op_refine_normal_eq;  nope_op_refine_step }
+ *     nope_unet_forward on the k base poses;  nope_similarity of those maps;  nope_op_refine_select
+ * Nothing in it is read by the host.  The seven poses of a candidate, as 6-D f32 rows (the first two matrix rows, the U-Net's pose input,
+ * src/poses/rotation_conversions.py:490-503), h = fd_step radians:
+ *     [dR, exp(+h e_x) dR, exp(-h e_x) dR, exp(+h e_y) dR, exp(-h e_y) dR, exp(+h e_z) dR, exp(-h e_z) dR]
+ * Everything below is f64 arithmetic on the device and run-to-run deterministic. */
+enum { NOPE_REFINE_NONFINITE = 1,  /* step: a normal-equation entry (or the solution) is not finite: no step */
+       NOPE_REFINE_SINGULAR = 2,   /* step: det(A + damping diag A) <= 0: no step */
+       NOPE_REFINE_ZERO_STEP = 3,  /* step: the solution is exactly 0 (g = 0): no step */
+       NOPE_REFINE_CLAMPED = 4,    /* step: taken, |w| was cut to max_step_rad (direction kept) */
+       NOPE_REFINE_BAD_INDEX = 5   /* init: idx outside [0, N) (clamped into it) */ };
+/*   all_relativeR (B, N, 6) f32;  idx (B, k) int64 (nope_topk's);  fd_step > 0
+ *   dR, dR_init   (B, k, 3, 3) f64 out: the Gram-Schmidt matrix (b1 = a1 / |a1|, b2 = normalised a2 - (b1 . a2) b1, b3 = b1 x b2), twice
+ *   poses         (B, 7k, 6) f32 out, candidate-major: row (j * 7 + m) of sample b
+ *   status        (B, k) int32 out: 0 or NOPE_REFINE_BAD_INDEX */
+int nope_op_refine_init(const float* all_relativeR, int64_t N, const int64_t* idx, double* dR, double* dR_init, float* poses, int* status,
+                        int B, int k, double fd_step, nope_stream_t stream);
+/*   q (B, C, h, w) f32;  maps (B, k, 7, C, h, w) f32, the U-Net's outputs for `poses`
+ *   normal_eq (B, k, 10) f64 out: A00 A01 A02 A11 A12 A22 | g0 g1 g2 | cost, with r = t0 - q, J_a = (t_{+a} - t_{-a}) / (2 fd_step),
+ *             A = J^T J, g = J^T r, cost = r^T r.  Differences, products and sums in f64; sums of (t+ - t-) products, scaled once.
+ *   workspace nope_op_refine_normal_eq_workspace_bytes(B, k, h, w) bytes: the per-(candidate, pixel slice) partial sums, folded in slice order.
+ * h * w must be a multiple of 16 (NOPE_ERR_UNSUPPORTED otherwise; every network here needs that already); pointers 16-byte aligned. */
+size_t nope_op_refine_normal_eq_workspace_bytes(int B, int k, int H, int W);
+int nope_op_refine_normal_eq(const float* q, const float* maps, double* normal_eq, int B, int k, int C, int H, int W, double fd_step,
+                             void* workspace, size_t workspace_bytes, nope_stream_t stream);
+/*   Solves (A + damping diag A) w = -g, scales w to |w| = max_step_rad when it is longer, dR <- GramSchmidt(exp(w) dR) (exp: Rodrigues),
+ *   writes the next seven poses and status (B, k) int32: 0, NOPE_REFINE_CLAMPED (step taken), or NOPE_REFINE_NONFINITE / _SINGULAR /
+ *   _ZERO_STEP: no step, dR stays as it is bit for bit (the poses are written again all the same). */
+int nope_op_refine_step(const double* normal_eq, double* dR, float* poses, int* status, int B, int k, double fd_step, double max_step_rad,
+                        double damping, nope_stream_t stream);
+/*   score_refined (B, k) f32: nope_similarity of the query against the maps of the k refined poses (the reference's metric, model.py:257-262)
+ *   similarity    (B, N) f32, row stride similarity_ld: the retrieval scores; candidate j's is similarity[b, idx[b, j]]
+ *   A refined pose is kept iff score_refined > that score (Gauss-Newton minimises the plain L2 distance, the score is quartic: without this
+ *   guard a step could lower it); a NaN on either side is never an improvement.  A candidate that is not kept reverts to dR_init and its
+ *   retrieval score.  The candidates are then ordered by final score, descending; ties -> the lower retrieval rank; a NaN first, as nope_topk.
+ *   Outputs, all in the final order: out_dR (B, k, 3, 3) f64, out_6d (B, k, 6) f32 (its first two rows), out_score / out_score_init (B, k) f32,
+ *   out_accepted (B, k) int32, out_order (B, k) int64 (the retrieval rank of each entry), and -- with template_poses (B, N_t, 3, 3) f64, sample
+ *   stride template_stride_b elements (0 = one grid for every query), or both NULL --
+ *       pred_R (B, k, 3, 3) f64 = (dR dR_init^T) template_poses[b, idx[b, j]]   (a reverted candidate: the grid pose itself, bit for bit)
+ *   which nope_op_geodesic scores as a per-sample pose table (pose_stride_b = 9k, idx = NULL).  1 <= k <= 16. */
+int nope_op_refine_select(const double* dR, const double* dR_init, const float* score_refined, const float* similarity, int64_t similarity_ld,
+                          int64_t N, const int64_t* idx, const double* template_poses, int64_t template_stride_b, int64_t n_templates,
+                          double* out_dR, float* out_6d, float* out_score, float* out_score_init, int* out_accepted, int64_t* out_order,
+                          double* pred_R, int B, int k, nope_stream_t stream);
 
 /* (ABI 9) Depth rendering of object meshes for the VSD evaluation.  Replaces pyrenderer, src/poses/vsd.py:25-54 (pyrender's OpenGL
  * OffscreenRenderer with an IntrinsicsCamera, znear 0.05, zfar 100000, DEPTH_ONLY), as called by vsd_obj, vsd.py:79-90.

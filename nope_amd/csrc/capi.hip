@@ -69,6 +69,36 @@ int nope_op_geodesic(const double* poses, int64_t pose_stride_b, int N, const in
     return launch_geodesic(poses, (long long)pose_stride_b, N, (const long long*)idx, gt, symmetry, err_rad, status, B, k, (hipStream_t)stream);
 }
 
+int nope_op_refine_init(const float* all_relativeR, int64_t N, const int64_t* idx, double* dR, double* dR_init, float* poses, int* status,
+                        int B, int k, double fd_step, nope_stream_t stream) {
+    return launch_refine_init(all_relativeR, (long long)N, (const long long*)idx, dR, dR_init, poses, status, B, k, fd_step, (hipStream_t)stream);
+}
+
+size_t nope_op_refine_normal_eq_workspace_bytes(int B, int k, int H, int W) {
+    if (H <= 0 || W <= 0) return 0;
+    return refine_normal_eq_workspace_bytes(B, k, H * W);
+}
+
+int nope_op_refine_normal_eq(const float* q, const float* maps, double* normal_eq, int B, int k, int C, int H, int W, double fd_step,
+                             void* workspace, size_t workspace_bytes, nope_stream_t stream) {
+    if (H <= 0 || W <= 0) return NOPE_ERR_ARG;
+    return launch_refine_normal_eq(q, maps, normal_eq, B, k, C, H * W, fd_step, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int nope_op_refine_step(const double* normal_eq, double* dR, float* poses, int* status, int B, int k, double fd_step, double max_step_rad,
+                        double damping, nope_stream_t stream) {
+    return launch_refine_step(normal_eq, dR, poses, status, B, k, fd_step, max_step_rad, damping, (hipStream_t)stream);
+}
+
+int nope_op_refine_select(const double* dR, const double* dR_init, const float* score_refined, const float* similarity, int64_t similarity_ld,
+                          int64_t N, const int64_t* idx, const double* template_poses, int64_t template_stride_b, int64_t n_templates,
+                          double* out_dR, float* out_6d, float* out_score, float* out_score_init, int* out_accepted, int64_t* out_order,
+                          double* pred_R, int B, int k, nope_stream_t stream) {
+    return launch_refine_select(dR, dR_init, score_refined, similarity, (long long)similarity_ld, (long long)N, (const long long*)idx,
+                                template_poses, (long long)template_stride_b, (long long)n_templates, out_dR, out_6d, out_score, out_score_init,
+                                out_accepted, (long long*)out_order, pred_R, B, k, (hipStream_t)stream);
+}
+
 size_t nope_op_render_depth_workspace_bytes(int P, int max_faces) { return render_depth_workspace_bytes(P, max_faces); }
 
 int nope_op_render_depth(const float* verts, int V, const int* faces, int F, const int* face_off, const int* face_cnt, int max_faces,

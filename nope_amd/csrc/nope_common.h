@@ -481,6 +481,17 @@ int launch_topk(const float* scores, long long* idx, float* vals, int B, int N, 
 int launch_gather_topk(const float* gathered, int G, int B, int N, float* scores, long long* idx, float* vals, int k, hipStream_t s);
 int launch_geodesic(const double* poses, long long stride_b, int N, const long long* idx, const double* gt, const int* symmetry,
                     double* err, int* status, int B, int k, hipStream_t s);
+// sub-grid pose refinement (kernels_refine.hip)
+int launch_refine_init(const float* all_rel, long long N, const long long* idx, double* dR, double* dR0, float* poses, int* status, int B, int k,
+                       double h, hipStream_t s);
+size_t refine_normal_eq_workspace_bytes(int B, int k, int HW);
+int launch_refine_normal_eq(const float* q, const float* maps, double* ne, int B, int k, int C, int HW, double h, void* ws, size_t ws_bytes,
+                            hipStream_t s);
+int launch_refine_step(const double* ne, double* dR, float* poses, int* status, int B, int k, double h, double max_step_rad, double damping,
+                       hipStream_t s);
+int launch_refine_select(const double* dR, const double* dR0, const float* score_new, const float* sim, long long sim_ld, long long N,
+                         const long long* idx, const double* tpl, long long tpl_stride_b, long long n_tpl, double* out_R, float* out_6d,
+                         float* out_score, float* out_score0, int* out_accepted, long long* out_order, double* pred_R, int B, int k, hipStream_t s);
 size_t render_depth_workspace_bytes(int P, int max_faces);
 int launch_render_depth(const float* verts, int V, const int* faces, int F, const int* face_off, const int* face_cnt, int max_faces,
                         const double* poses, const double* K, int P, int H, int W, float* depth, unsigned* skipped, void* ws,

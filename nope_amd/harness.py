@@ -144,11 +144,13 @@ def geodesic_deg(predR: torch.Tensor, gtR: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False,
-                  errors_out: Optional[list] = None):
+                  errors_out: Optional[list] = None, refine_iters: int = 0):
     """The body of PoseConditional.eval_geodesic (model.py:268-376).  visualize (effective with a decoding encoder and model.save_dir only,
     model.py:269-274; needs batch["gt_templates"] (B, N, 3, S, S)): the three kinds of pictures and the video under save_dir/media
     (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions.  errors_out: a list that
-    receives this batch's (B,) top-1 errors in degrees (run_split pools them over a split)."""
+    receives this batch's (B,) top-1 errors in degrees (run_split pools them over a split).  refine_iters > 0 (no reference counterpart): the
+    retrieved candidates are refined below the grid spacing (PoseConditional.refine) and scored as well: the same metric keys under a
+    "refined/" prefix, and `refined_relR` (B, k, 3, 3) in the saved predictions; at 0 nothing changes."""
     visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
     if visualize and "gt_templates" not in batch:
         raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
@@ -177,8 +179,15 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
         errors_out.append(top1)
     res = {"loss": float(loss)}
     res.update({k: float(v) for k, v in metric.items()})
+    extra = {}
+    if refine_iters > 0:
+        ref = model.refine(query, reference, batch["all_relativeR"], nearest_idx, similarity, iters=refine_iters, template_poses=batch["template_poses"][:1])
+        # pred_R (B, k, 3, 3) is a per-sample pose table for the same launch: rows 0 .. k - 1 of sample b
+        _, refined = GeodesicError(list(thresholds))._topk_result(hip.op_geodesic(ref.pred_R, batch["query_pose"], sym))
+        res.update({f"refined/{k}": float(v) for k, v in refined.items()})
+        if save_path:
+            extra["refined_relR"] = ref.relR.cpu().numpy()
     if save_path:
-        extra = {}
         if visualize:       # model.py:334-339,367-375: the un-resized grid of the last picture
             extra["vis_imgs"] = hip.op_vis_grid(retrieved)[0].cpu().numpy()
         np.savez(save_path, **extra, query_pose=batch["query_pose"].cpu().numpy(), similarity=similarity.cpu().numpy())
@@ -248,8 +257,12 @@ def main(argv=None):
     ap.add_argument("--fast", action="store_true", help="with --data-root: fast_evaluation, the 26 level-0 viewpoints instead of the 341 of level 2")
     ap.add_argument("--limit", type=int, default=None, help="with --data-root: only the first N samples of the split")
     ap.add_argument("--u-net-dim", type=int, default=None, help="with --data-root: U-Net width (default: template_base.yaml's 192)")
+    ap.add_argument("--refine", type=int, default=0, metavar="ITERS",
+                    help="refine the retrieved poses with ITERS Gauss-Newton iterations through the U-Net and print their scores as well (refined/...)")
     a = ap.parse_args(argv)
     if a.data_root:
+        if a.refine:
+            ap.error("--refine applies to the synthetic batch (a split's pooled scores are not refined)")
         return main_dataset(a, ap)
     a.size = a.size or 128
     if a.visualize and (a.encoder != "vae" or not a.save_dir):
@@ -262,7 +275,7 @@ def main(argv=None):
     for name, batch in batches.items():                         # test_step, model.py:550-565
         t0 = time.time()
         save = os.path.join(a.save_dir, "predictions", f"pred_step0_rank{model.global_rank}") if a.save_dir else None
-        sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize)
+        sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize, refine_iters=a.refine)
         torch.cuda.synchronize()
         res.update(dataloader=name, seconds=time.time() - t0, nearest_idx=idx.tolist())
         print(json.dumps(res))

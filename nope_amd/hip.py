@@ -15,7 +15,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 14                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 15                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -84,6 +84,11 @@ _PROTOS = {
     "nope_gather_topk": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "nope_topk_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_geodesic": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "nope_op_refine_init": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp]),
+    "nope_op_refine_normal_eq_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "nope_op_refine_normal_eq": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _sz, _vp]),
+    "nope_op_refine_step": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double, _vp]),
+    "nope_op_refine_select": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "nope_op_render_depth_workspace_bytes": (_sz, [_i, _i]),
     "nope_op_render_depth": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "nope_op_vsd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
@@ -408,6 +413,109 @@ def op_geodesic(poses: torch.Tensor, gt: torch.Tensor, symmetry: Optional[torch.
     if st & 1:
         raise ValueError("A matrix has trace outside valid range [-1-eps,3+eps].")      # pytorch3d so3_rotation_angle's message
     return err
+
+
+
+# --------------------------------------------------------------------------------------------
+# sub-grid pose refinement (csrc/kernels_refine.hip; the loop is PoseConditional.refine_from_feat)
+# --------------------------------------------------------------------------------------------
+REFINE_NONFINITE, REFINE_SINGULAR, REFINE_ZERO_STEP, REFINE_CLAMPED, REFINE_BAD_INDEX = 1, 2, 3, 4, 5
+
+
+def op_refine_init(all_relativeR: torch.Tensor, idx: torch.Tensor, fd_step: float = 1e-2):
+    """all_relativeR (B,N,6), idx (B,k) int64 -> (dR (B,k,3,3) f64, dR_init (its copy), poses (B,7k,6) f32, status (B,k) int32): the
+    Gram-Schmidt matrix of all_relativeR[b, idx[b, j]] and the seven poses [dR, exp(+-h e_x) dR, exp(+-h e_y) dR, exp(+-h e_z) dR]."""
+    require_device(all_relativeR)
+    rel = _f32c(all_relativeR)
+    idx = idx.to(device=rel.device, dtype=torch.int64).contiguous()
+    if rel.dim() != 3 or rel.shape[2] != 6 or idx.dim() != 2 or idx.shape[0] != rel.shape[0]:
+        raise NopeError(f"all_relativeR {tuple(rel.shape)} / idx {tuple(idx.shape)}: expected (B, N, 6) and (B, k)")
+    B, N, k = rel.shape[0], rel.shape[1], idx.shape[1]
+    dR = torch.empty((B, k, 3, 3), dtype=torch.float64, device=rel.device)
+    dR0 = torch.empty_like(dR)
+    poses = torch.empty((B, 7 * k, 6), dtype=torch.float32, device=rel.device)
+    status = torch.empty((B, k), dtype=torch.int32, device=rel.device)
+    l = lib()
+    l.check(l.dll.nope_op_refine_init(_ptr(rel), N, _ptr(idx), _ptr(dR), _ptr(dR0), _ptr(poses), _ptr(status), B, k, float(fd_step), _stream(rel)),
+            "nope_op_refine_init")
+    return dR, dR0, poses, status
+
+
+def op_refine_normal_eq(q: torch.Tensor, maps: torch.Tensor, fd_step: float = 1e-2, out: Optional[torch.Tensor] = None,
+                        workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q (B,C,h,w) f32, maps (B,k,7,C,h,w) or (B,7k,C,h,w) f32 -> (B,k,10) f64: A00 A01 A02 A11 A12 A22 | g0 g1 g2 | cost."""
+    require_device(q)
+    if q.dtype != torch.float32 or maps.dtype != torch.float32:
+        raise NopeError("refinement reads f32 maps")
+    q, maps = q.contiguous(), maps.contiguous()
+    B, Cc, H, W = q.shape
+    if maps.dim() == 5:
+        maps = maps.view(B, -1, 7, Cc, H, W) if maps.shape[0] == B and maps.shape[1] % 7 == 0 and tuple(maps.shape[2:]) == (Cc, H, W) else maps
+    if maps.dim() != 6 or maps.shape[0] != B or maps.shape[2] != 7 or tuple(maps.shape[3:]) != (Cc, H, W):
+        raise NopeError(f"maps {tuple(maps.shape)} do not match the query {tuple(q.shape)}: expected (B, k, 7, C, h, w)")
+    k = maps.shape[1]
+    if out is None:
+        out = torch.empty((B, k, 10), dtype=torch.float64, device=q.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (B, k, 10)
+    l = lib()
+    need = int(l.dll.nope_op_refine_normal_eq_workspace_bytes(B, k, H, W))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=q.device)
+    l.check(l.dll.nope_op_refine_normal_eq(_ptr(q), _ptr(maps), _ptr(out), B, k, Cc, H, W, float(fd_step), _ptr(workspace),
+                                           workspace.numel() * workspace.element_size(), _stream(q)), "nope_op_refine_normal_eq")
+    return out
+
+
+def op_refine_step(normal_eq: torch.Tensor, dR: torch.Tensor, poses: torch.Tensor, fd_step: float = 1e-2, max_step_rad: float = 0.17453292519943295,
+                   damping: float = 1e-6, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One damped Gauss-Newton step IN PLACE on dR (B,k,3,3) f64 and poses (B,7k,6) f32 from normal_eq (B,k,10) f64; returns the
+    per-candidate status (B,k) int32 (REFINE_*; 0 and REFINE_CLAMPED are steps taken)."""
+    require_device(dR)
+    B, k = dR.shape[:2]
+    if (dR.dtype != torch.float64 or not dR.is_contiguous() or tuple(dR.shape[2:]) != (3, 3) or poses.dtype != torch.float32 or not poses.is_contiguous()
+            or poses.numel() != B * k * 42 or normal_eq.dtype != torch.float64 or not normal_eq.is_contiguous() or tuple(normal_eq.shape) != (B, k, 10)):
+        raise NopeError(f"refine step: dR {tuple(dR.shape)}, poses {tuple(poses.shape)}, normal_eq {tuple(normal_eq.shape)}")
+    if status is None:
+        status = torch.empty((B, k), dtype=torch.int32, device=dR.device)
+    assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B * k
+    l = lib()
+    l.check(l.dll.nope_op_refine_step(_ptr(normal_eq), _ptr(dR), _ptr(poses), _ptr(status), B, k, float(fd_step), float(max_step_rad), float(damping),
+                                      _stream(dR)), "nope_op_refine_step")
+    return status
+
+
+def op_refine_select(dR: torch.Tensor, dR_init: torch.Tensor, score_refined: torch.Tensor, similarity: torch.Tensor, idx: torch.Tensor,
+                     template_poses: Optional[torch.Tensor] = None) -> SimpleNamespace:
+    """Accept / revert against similarity[b, idx[b, j]] and order by final score (include/nope_hip.h).  Returns a namespace of tensors in the
+    final order: dR (B,k,3,3) f64, rot6d (B,k,6) f32, score, score_init (B,k) f32, accepted (B,k) bool, order (B,k) int64, and pred_R (B,k,3,3)
+    f64 = (dR dR_init^T) template_poses[b, idx] when template_poses (B|1,N,3,3) is given (None otherwise)."""
+    require_device(dR)
+    B, k = dR.shape[:2]
+    dev = dR.device
+    score_refined, similarity = _f32c(score_refined), _f32c(similarity)
+    idx = idx.to(device=dev, dtype=torch.int64).contiguous()
+    if (tuple(score_refined.shape) != (B, k) or tuple(idx.shape) != (B, k) or similarity.dim() != 2 or similarity.shape[0] != B
+            or dR.dtype != torch.float64 or dR_init.dtype != torch.float64 or dR_init.shape != dR.shape):
+        raise NopeError(f"refine select: dR {tuple(dR.shape)}, scores {tuple(score_refined.shape)}, similarity {tuple(similarity.shape)}, idx {tuple(idx.shape)}")
+    dR, dR_init = dR.contiguous(), dR_init.contiguous()
+    tpl, stride_b, n_tpl, pred = None, 0, 0, None
+    if template_poses is not None:
+        tpl = template_poses.to(device=dev, dtype=torch.float64).contiguous()
+        if tpl.dim() != 4 or tuple(tpl.shape[2:]) != (3, 3) or tpl.shape[0] not in (1, B):
+            raise NopeError(f"template_poses {tuple(tpl.shape)}: expected (B|1, N, 3, 3)")
+        n_tpl = tpl.shape[1]
+        stride_b = 0 if (tpl.shape[0] == 1 and B > 1) else n_tpl * 9
+        pred = torch.empty((B, k, 3, 3), dtype=torch.float64, device=dev)
+    r = SimpleNamespace(dR=torch.empty_like(dR), rot6d=torch.empty((B, k, 6), dtype=torch.float32, device=dev),
+                        score=torch.empty((B, k), dtype=torch.float32, device=dev), score_init=torch.empty((B, k), dtype=torch.float32, device=dev),
+                        order=torch.empty((B, k), dtype=torch.int64, device=dev), pred_R=pred)
+    accepted = torch.empty((B, k), dtype=torch.int32, device=dev)
+    l = lib()
+    l.check(l.dll.nope_op_refine_select(_ptr(dR), _ptr(dR_init), _ptr(score_refined), _ptr(similarity), similarity.shape[1], similarity.shape[1],
+                                        _ptr(idx), _ptr(tpl), stride_b, n_tpl, _ptr(r.dR), _ptr(r.rot6d), _ptr(r.score), _ptr(r.score_init),
+                                        _ptr(accepted), _ptr(r.order), _ptr(pred), B, k, _stream(dR)), "nope_op_refine_select")
+    r.accepted = accepted != 0
+    return r
 
 
 # --------------------------------------------------------------------------------------------

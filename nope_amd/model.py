@@ -20,13 +20,27 @@ from __future__ import annotations
 
 import inspect
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import nn
 
 from . import dist as ndist
 from . import hip
+
+
+class RefineResult(NamedTuple):
+    """What PoseConditional.refine_from_feat returns (its docstring has the shapes)."""
+    relR: torch.Tensor
+    rot6d: torch.Tensor
+    score: torch.Tensor
+    score_init: torch.Tensor
+    accepted: torch.Tensor
+    order: torch.Tensor
+    costs: torch.Tensor
+    status: torch.Tensor
+    trajectory: torch.Tensor
+    pred_R: Optional[torch.Tensor]
 
 
 def _cfg_get(cfg, key, default=None):
@@ -213,6 +227,10 @@ class PoseConditional(nn.Module):
         stream and runs underneath the reference encoder and the first U-Net kernels."""
         if self.similarity_metric != "l2":
             return None
+        return self._encode_generate_retrieve(query, reference, all_relativeR)[:3]
+
+    def _encode_generate_retrieve(self, query, reference, all_relativeR):
+        """The body of generate_and_retrieve; also hands out the two embeddings (predict_pose refines on them)."""
         if self.pipeline_encoders and query.is_cuda:
             with hip.overlap_stream(query, wait_current=False) as side:
                 reference_feat = self.u_net.encoder.encode_image(reference, mode="mode")
@@ -234,7 +252,7 @@ class PoseConditional(nn.Module):
         # When a layer had left its accurate window the forwards were just repeated into the same bank: score and rank again.
         if defer and self.u_net.finish_range_check():
             similarity, nearest_idx = self.retrieval_from_feat(query_feat, bank)
-        return similarity, nearest_idx, bank
+        return similarity, nearest_idx, bank, query_feat, reference_feat
 
     @torch.no_grad()
     def retrieval_topk_from_feat(self, query_feat, template_feat, k=5, shard=None):
@@ -283,6 +301,87 @@ class PoseConditional(nn.Module):
             similarity = hip.similarity(query_feat, template_feat)
         _, nearest_idx = hip.topk(similarity, k)
         return similarity, nearest_idx
+
+    # ---- sub-grid refinement (no reference counterpart: DESIGN.md section 4.9) --------------------------------------------------------
+    def _forward_poses(self, reference_feat, poses, out):
+        """out (B,n,C,h,w) f32 = u_net(reference_feat[b], poses[b, i]), chunked by max_hypotheses_per_launch as _generate_templates_from_feat
+        chunks a bank.  The range check (f16x2) is NOT deferred: the refinement rewrites `poses` before the step ends, and a deferred
+        repeat would replay the forward on the rewritten poses."""
+        B, n = poses.shape[:2]
+        if n <= self.max_hyp:
+            bs = max(1, self.max_hyp // n)
+            for b0 in range(0, B, bs):
+                self.u_net.forward_hypotheses(reference_feat[b0:b0 + bs], poses[b0:b0 + bs], out=out[b0:b0 + bs], defer_range_check=False)
+        else:
+            for b in range(B):
+                for s in range(0, n, self.max_hyp):
+                    e = min(n, s + self.max_hyp)
+                    self.u_net.forward_hypotheses(reference_feat[b:b + 1], poses[b:b + 1, s:e], out=out[b:b + 1, s:e], defer_range_check=False)
+        return out
+
+    @torch.no_grad()
+    def refine_from_feat(self, query_feat, reference_feat, all_relativeR, nearest_idx, similarity, iters=3, fd_step=1e-2, max_step_deg=10.0,
+                         damping=1e-6, template_poses=None):
+        """Gauss-Newton on SO(3) from the k retrieved candidates (include/nope_hip.h: nope_op_refine_*): per iteration ONE U-Net pass over
+        seven poses per candidate (the pose and its six central-difference neighbours), the 3x3 normal equations of
+        || u_net(reference_feat, dR) - query_feat ||^2 and a damped, clamped tangent step; then the reference's score (model.py:257-262) of
+        the refined poses decides, per candidate, between the refined pose (strictly better) and the grid pose.  Nothing is read by the
+        host (under f16x2 in "repeat" mode: the range checks of the forwards).
+        query_feat, reference_feat (B,C,h,w) f32; all_relativeR (B,N,6); nearest_idx (B,k); similarity (B,N) as `retrieval` returns them.
+        Returns a RefineResult, every per-candidate tensor in the final order (descending final score, ties -> the lower retrieval rank):
+        relR (B,k,3,3) f64, rot6d (B,k,6) f32, score, score_init (B,k) f32, accepted (B,k) bool, order (B,k) int64 (retrieval rank of each
+        entry), costs (iters,B,k) f64 (r^T r at the START of each iteration, in retrieval order), status (iters,B,k) int32 (hip.REFINE_*),
+        trajectory (iters+1,B,k,3,3) f64 (dR before the first and after every step, retrieval order) and, with template_poses (B|1,N,3,3),
+        pred_R (B,k,3,3) f64 = (dR dR_init^T) template_poses[nearest_idx]."""
+        import math
+        if iters < 1:
+            raise ValueError("refine_from_feat: iters >= 1 (predict_pose(refine_iters=0) is the unrefined answer)")
+        query_feat, reference_feat = query_feat.float().contiguous(), reference_feat.float().contiguous()
+        B, k = nearest_idx.shape
+        C, h, w = query_feat.shape[1:]
+        dR, dR0, poses, _ = hip.op_refine_init(all_relativeR, nearest_idx, fd_step)
+        dev = dR.device
+        maps = torch.empty((B, 7 * k, C, h, w), dtype=torch.float32, device=dev)
+        ne = torch.empty((iters, B, k, 10), dtype=torch.float64, device=dev)
+        status = torch.empty((iters, B, k), dtype=torch.int32, device=dev)
+        traj = torch.empty((iters + 1, B, k, 3, 3), dtype=torch.float64, device=dev)
+        ws = torch.empty(max(8, int(hip.lib().dll.nope_op_refine_normal_eq_workspace_bytes(B, k, h, w))) // 8, dtype=torch.float64, device=dev)
+        traj[0].copy_(dR)
+        for it in range(iters):
+            self._forward_poses(reference_feat, poses, maps)
+            hip.op_refine_normal_eq(query_feat, maps, fd_step, out=ne[it], workspace=ws)
+            hip.op_refine_step(ne[it], dR, poses, fd_step, math.radians(max_step_deg), damping, status=status[it])
+            traj[it + 1].copy_(dR)
+        base = poses.view(B, k, 7, 6)[:, :, 0].contiguous()
+        final_maps = self._forward_poses(reference_feat, base, torch.empty((B, k, C, h, w), dtype=torch.float32, device=dev))
+        score = hip.similarity(query_feat, final_maps)
+        r = hip.op_refine_select(dR, dR0, score, similarity, nearest_idx, template_poses)
+        return RefineResult(relR=r.dR, rot6d=r.rot6d, score=r.score, score_init=r.score_init, accepted=r.accepted, order=r.order,
+                            costs=ne[..., 9], status=status, trajectory=traj, pred_R=r.pred_R)
+
+    @torch.no_grad()
+    def refine(self, query, reference, all_relativeR, nearest_idx, similarity, **kw):
+        """Encode both images, then refine_from_feat (same keyword arguments)."""
+        enc = self.u_net.encoder
+        query_feat = enc.encode_image(query, mode="mode")
+        reference_feat = enc.encode_image(reference, mode="mode")
+        return self.refine_from_feat(query_feat, reference_feat, all_relativeR, nearest_idx, similarity, **kw)
+
+    @torch.no_grad()
+    def predict_pose(self, query, reference, all_relativeR, template_poses, refine_iters=0, **kw):
+        """(pred_R (B,k,3,3) f64, score (B,k) f32): the k best poses of the query.  refine_iters = 0: template_poses[nearest_idx]
+        (model.py:352-354) and the retrieval scores; above 0: those candidates refined below the grid spacing (refine_from_feat, whose
+        keyword arguments pass through), in ITS order.  template_poses (B|1,N,3,3).  None for a metric the reference does not implement."""
+        if self.similarity_metric != "l2":
+            return None
+        similarity, nearest_idx, _, query_feat, reference_feat = self._encode_generate_retrieve(query, reference, all_relativeR)
+        if refine_iters <= 0:
+            tp = template_poses.to(device=nearest_idx.device, dtype=torch.float64)
+            rows = torch.arange(nearest_idx.shape[0], device=nearest_idx.device)[:, None] if tp.shape[0] != 1 else 0
+            return tp[rows, nearest_idx], torch.gather(similarity, 1, nearest_idx)
+        r = self.refine_from_feat(query_feat, reference_feat, all_relativeR, nearest_idx, similarity, iters=refine_iters,
+                                  template_poses=template_poses, **kw)
+        return r.pred_R, r.score
 
     # ---- evaluation, model.py:268-565 --------------------------------------------------------------------------------------------------
     def load_mesh(self, cad_dir, obj_ids=range(1, 31)):
