@@ -98,14 +98,14 @@ struct Fwd : FwdBase {
         conv(A.qkv, Act{xn, C, x.H, x.W}, qkv, x.H, x.W);
         if (live()) chk(launch_token_attention(net->dt, qkv, o, nhyp, HW, C, A.dh, s));
         if (tracking()) x2.overwritten(o);
-        conv(A.proj, Act{o, C, x.H, x.W}, out, x.H, x.W, x.p);
+        conv(A.proj, Act{o, C, x.H, x.W}, out, x.H, x.W, with_resid(x.p));
         ar.off = mark;
     }
 };
 
-int run_forward(const nope_gd* net, const float* x, int n_src, int x_rep, const float* pose, int n_hyp, int H, int W, void* out,
-                int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak) {
+int run_forward(const nope_gd* net, const FwdReq& q, void* ws, size_t ws_bytes, hipStream_t s, bool dry = false, size_t* peak = nullptr) {
     const nope_gd_config& cfg = net->cfg;
+    const int n_src = q.n_src, n_hyp = q.n_hyp, H = q.H, W = q.W;
     Fwd f;
     f.begin(net, n_hyp, ws, ws_bytes, s, dry);
     const int HW = H * W;
@@ -118,20 +118,20 @@ int run_forward(const nope_gd* net, const float* x, int n_src, int x_rep, const 
     f.emb = emb;
     if (f.err) return f.err;
     if (f.live()) {
-        f.chk(launch_nchw_to_nhwc(net->sdt, x, x_in, n_src, cin_k, HW, s, cfg.in_channels));
+        f.chk(launch_nchw_to_nhwc(net->sdt, q.x, x_in, n_src, cin_k, HW, s, cfg.in_channels));
         // emb = pose_mlp(pose), adapt_u_net.py:62-78,87
-        if (cfg.pose_mlp == NOPE_GD_POSE_ENCODING) f.chk(launch_pos_emb(pose, emb, n_hyp, cfg.pose_dim, E, s));
+        if (cfg.pose_mlp == NOPE_GD_POSE_ENCODING) f.chk(launch_pos_emb(q.pose, emb, n_hyp, cfg.pose_dim, E, s));
         else if (cfg.pose_mlp == NOPE_GD_POSE_TWO_LAYERS) {
-            f.chk(launch_linear_naive(pose, net->pose_w0, net->pose_b0, e1, n_hyp, E, cfg.pose_dim, 0, E, s));
+            f.chk(launch_linear_naive(q.pose, net->pose_w0, net->pose_b0, e1, n_hyp, E, cfg.pose_dim, 0, E, s));
             f.chk(launch_linear_naive(e1, net->pose_w2, net->pose_b2, emb, n_hyp, E, E, 2, E, s));          // GELU (erf) on its input
-        } else f.chk(launch_linear_naive(pose, net->pose_w0, net->pose_b0, emb, n_hyp, E, cfg.pose_dim, 0, E, s));
+        } else f.chk(launch_linear_naive(q.pose, net->pose_w0, net->pose_b0, emb, n_hyp, E, cfg.pose_dim, 0, E, s));
     }
 
     std::vector<Act> hs;
     int curH = H, curW = W;
     // input_blocks[0]: the input conv, evaluated once per hypothesis from the shared latent (source broadcast)
     Act h{f.alloc_act((size_t)n_hyp * HW * net->conv_in.Cout), net->conv_in.Cout, H, W};
-    f.conv(net->conv_in, Act{x_in, cin_k, H, W}, h.p, H, W, nullptr, 0, NOPE_F32, x_rep);
+    f.conv(net->conv_in, Act{x_in, cin_k, H, W, q.x_rep}, h.p, H, W);
     hs.push_back(h);
     for (size_t b = 1; b < net->input_blocks.size(); ++b) {
         const GBlock& B = net->input_blocks[b];
@@ -200,10 +200,10 @@ int run_forward(const nope_gd* net, const float* x, int n_src, int x_rep, const 
     {
         void* t = f.alloc_act((size_t)n_hyp * HW * h.C);
         f.gn(net->norm_out, 32, h.p, t, HW, 1, 1e-5f);
-        f.conv(net->conv_out, Act{t, h.C, H, W}, out, H, W, nullptr, 1, out_dtype);
+        f.conv(net->conv_out, Act{t, h.C, H, W}, q.out, H, W, to_nchw(q.out_dtype));
     }
     if (f.tracking())      // the forward's verdict; NaNs over the output of a forward whose layers left their windows (x2_range.h)
-        f.chk(f.x2.finish(out, (size_t)n_hyp * cfg.out_channels * HW * (size_t)(out_dtype == NOPE_F32 ? 4 : 2), out_dtype));
+        f.chk(f.x2.finish(q.out, (size_t)n_hyp * cfg.out_channels * HW * (size_t)(q.out_dtype == NOPE_F32 ? 4 : 2), q.out_dtype));
     if (peak) *peak = f.ar.peak;
     return f.err;
 }
@@ -335,8 +335,9 @@ int nope_gd_x2_enable(nope_gd* net, int on) { return x2_enable(net, on); }
 size_t nope_gd_workspace_bytes(const nope_gd* net, int n_hyp, int n_src, int H, int W) {
     if (!net || n_src <= 0 || n_hyp % n_src) return 0;
     if (check_shape(net, n_hyp, n_src, n_hyp / n_src, H, W) != NOPE_OK) return 0;
+    FwdReq q; q.n_src = n_src; q.x_rep = n_hyp / n_src; q.n_hyp = n_hyp; q.H = H; q.W = W;
     size_t peak = 0;
-    run_forward(net, nullptr, n_src, n_hyp / n_src, nullptr, n_hyp, H, W, nullptr, NOPE_F32, nullptr, 0, nullptr, true, &peak);
+    run_forward(net, q, nullptr, 0, nullptr, true, &peak);
     return align_up(peak, 256) + 256;
 }
 
@@ -350,7 +351,9 @@ int nope_gd_forward(const nope_gd* net, const float* x, int n_src, int x_rep, co
     size_t cap;
     if (!workspace_base(workspace, workspace_bytes, base, cap)) return NOPE_ERR_WORKSPACE;
     x2_poll_before_forward(net, stream);
-    return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, cap, (hipStream_t)stream, false, nullptr);
+    FwdReq q; q.x = x; q.pose = pose; q.out = out; q.out_dtype = out_dtype;
+    q.n_src = n_src; q.x_rep = x_rep; q.n_hyp = n_hyp; q.H = H; q.W = W;
+    return run_forward(net, q, base, cap, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -157,7 +157,7 @@ struct Fwd : FwdBase {
             if (live()) chk(launch_layernorm(net->sdt, tok, a, B.ln1.gamma, B.ln1.beta, M, C, 1e-5f, s));
             conv(B.qkv, Act{a, C, x.H, x.W}, qkv, x.H, x.W);
             if (live()) chk(launch_token_attention(net->dt, qkv, o, nhyp, HW, C, T.dh, s));
-            conv(B.out1, Act{o, C, x.H, x.W}, tok1, x.H, x.W, tok);
+            conv(B.out1, Act{o, C, x.H, x.W}, tok1, x.H, x.W, with_resid(tok));
             // attn2 against the single pose token: + to_out(to_v(context)) for every token -- this block's slice of u_all
             if (live()) chk(launch_add_rowvec(net->sdt, tok1, tok1, u_all + B.u_off, M, HW, C, s, ldm->u_total));
             // feed-forward (GEGLU) + residual
@@ -177,16 +177,16 @@ struct Fwd : FwdBase {
                     chk(launch_geglu(net->sdt, g, gg, M, 4 * C, s, 1));
                 }
             }
-            conv(B.ff2, Act{gg, 4 * C, x.H, x.W}, tok, x.H, x.W, tok1);      // (tok is dead after the attn1 residual: the block's output)
+            conv(B.ff2, Act{gg, 4 * C, x.H, x.W}, tok, x.H, x.W, with_resid(tok1));      // (tok is dead after the attn1 residual: the block's output)
         }
-        conv(T.proj_out, Act{tok, C, x.H, x.W}, out, x.H, x.W, x.p);
+        conv(T.proj_out, Act{tok, C, x.H, x.W}, out, x.H, x.W, with_resid(x.p));
         ar.off = mark;
     }
 };
 
-int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const float* pose, int n_hyp, int H, int W, void* out,
-                int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak) {
+int run_forward(const nope_ldm* net, const FwdReq& q, void* ws, size_t ws_bytes, hipStream_t s, bool dry = false, size_t* peak = nullptr) {
     const nope_ldm_config& cfg = net->cfg;
+    const int n_src = q.n_src, n_hyp = q.n_hyp, H = q.H, W = q.W;
     Fwd f;
     f.begin(net, n_hyp, ws, ws_bytes, s, dry);
     f.ldm = net;
@@ -201,9 +201,9 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
     f.gn_partial = f.alloc_f32((size_t)n_hyp * 16 * 32 * 2);
     if (f.err) return f.err;
     if (f.live()) {
-        f.chk(launch_nchw_to_nhwc(net->sdt, x, x_in, n_src, cin_k, HW, s, cfg.in_channels));
+        f.chk(launch_nchw_to_nhwc(net->sdt, q.x, x_in, n_src, cin_k, HW, s, cfg.in_channels));
         // context = pose_mlp(pose), adapt_openaimodel.py:105-116,145
-        f.chk(launch_linear_naive(pose, net->pose_w0, net->pose_b0, ctx, n_hyp, cfg.context_dim, cfg.pose_dim, 0, cfg.context_dim, s));
+        f.chk(launch_linear_naive(q.pose, net->pose_w0, net->pose_b0, ctx, n_hyp, cfg.context_dim, cfg.pose_dim, 0, cfg.context_dim, s));
         if (cfg.pose_mlp_layers == 2) {
             f.chk(launch_linear_naive(ctx, net->pose_w2, net->pose_b2, ctx2, n_hyp, cfg.context_dim, cfg.context_dim, 2, cfg.context_dim, s));
             f.ctx = ctx2;
@@ -211,7 +211,7 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
         if (net->u_total > 0)     // attn2 of every transformer block at once (see the header)
             f.chk(launch_linear_naive(f.ctx, net->u_w, net->u_b, u_all, n_hyp, net->u_total, cfg.context_dim, 0, net->u_total, s));
         if (emb) {     // emb = pose_mlp_timesteps(pose), :119-123,141-142
-            f.chk(launch_linear_naive(pose, net->tw, net->tb, emb, n_hyp, net->emb_dim, cfg.pose_dim, 0, net->emb_dim, s));
+            f.chk(launch_linear_naive(q.pose, net->tw, net->tb, emb, n_hyp, net->emb_dim, cfg.pose_dim, 0, net->emb_dim, s));
             f.emb = emb;
         }
     } else if (emb) f.emb = emb;
@@ -221,7 +221,7 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
     int curH = H, curW = W;
     // input_blocks[0]: the input conv, evaluated once per hypothesis from the shared latent (source broadcast)
     Act h{f.alloc_act((size_t)n_hyp * HW * net->conv_in.Cout), net->conv_in.Cout, H, W};
-    f.conv(net->conv_in, Act{x_in, cin_k, H, W}, h.p, H, W, nullptr, 0, NOPE_F32, x_rep);
+    f.conv(net->conv_in, Act{x_in, cin_k, H, W, q.x_rep}, h.p, H, W);
     hs.push_back(h);
     for (size_t b = 1; b < net->input_blocks.size(); ++b) {
         const LBlock& B = net->input_blocks[b];
@@ -289,10 +289,10 @@ int run_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, const
     {
         void* t = f.alloc_act((size_t)n_hyp * HW * h.C);
         f.gn(net->norm_out, 32, h.p, t, HW, 1, 1e-5f);
-        f.conv(net->conv_out, Act{t, h.C, H, W}, out, H, W, nullptr, 1, out_dtype);
+        f.conv(net->conv_out, Act{t, h.C, H, W}, q.out, H, W, to_nchw(q.out_dtype));
     }
     if (f.tracking())      // the forward's verdict; NaNs over the output of a forward whose layers left their windows (x2_range.h)
-        f.chk(f.x2.finish(out, (size_t)n_hyp * net->cfg.out_channels * HW * (size_t)(out_dtype == NOPE_F32 ? 4 : 2), out_dtype));
+        f.chk(f.x2.finish(q.out, (size_t)n_hyp * net->cfg.out_channels * HW * (size_t)(q.out_dtype == NOPE_F32 ? 4 : 2), q.out_dtype));
     if (peak) *peak = f.ar.peak;
     return f.err;
 }
@@ -433,8 +433,9 @@ int nope_ldm_x2_enable(nope_ldm* net, int on) { return x2_enable(net, on); }
 size_t nope_ldm_workspace_bytes(const nope_ldm* net, int n_hyp, int n_src, int H, int W) {
     if (!net || n_src <= 0 || n_hyp % n_src) return 0;
     if (check_shape(net, n_hyp, n_src, n_hyp / n_src, H, W) != NOPE_OK) return 0;
+    FwdReq q; q.n_src = n_src; q.x_rep = n_hyp / n_src; q.n_hyp = n_hyp; q.H = H; q.W = W;
     size_t peak = 0;
-    run_forward(net, nullptr, n_src, n_hyp / n_src, nullptr, n_hyp, H, W, nullptr, NOPE_F32, nullptr, 0, nullptr, true, &peak);
+    run_forward(net, q, nullptr, 0, nullptr, true, &peak);
     return align_up(peak, 256) + 256;
 }
 
@@ -448,7 +449,9 @@ int nope_ldm_forward(const nope_ldm* net, const float* x, int n_src, int x_rep, 
     size_t cap;
     if (!workspace_base(workspace, workspace_bytes, base, cap)) return NOPE_ERR_WORKSPACE;
     x2_poll_before_forward(net, stream);
-    return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, cap, (hipStream_t)stream, false, nullptr);
+    FwdReq q; q.x = x; q.pose = pose; q.out = out; q.out_dtype = out_dtype;
+    q.n_src = n_src; q.x_rep = x_rep; q.n_hyp = n_hyp; q.H = H; q.W = W;
+    return run_forward(net, q, base, cap, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -116,7 +116,7 @@ struct FwdBase : FwdCore<RtNet> {
             conv(R.skip, x, sk, x.H, x.W);
             resid = sk;
         }
-        conv(R.c2, Act{t2, R.Cout, x.H, x.W}, out, x.H, x.W, resid);
+        conv(R.c2, Act{t2, R.Cout, x.H, x.W}, out, x.H, x.W, with_resid(resid));
         ar.off = mark;
     }
 };

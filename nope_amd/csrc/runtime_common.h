@@ -4,8 +4,12 @@
 //   * Net: what the shared code reads of a network handle (compute / storage dtype, NOPE_F16X2 state, device allocations);
 //   * LoaderCore: the state-dict table of a create call, device / staging allocations, copies, and the conv-packing skeleton every
 //     network's conv() calls with its own shape rule.  Bound to the handle's `allocs` vector, not to a handle type;
-//   * Arena / Act / FwdCore: the bump arena over the caller's workspace, an NHWC activation, and a forward's bookkeeping with the conv
-//     and GroupNorm launches under the NOPE_F16X2 range tracking (x2_range.h);
+//   * Arena / Act / FwdCore: the bump arena over the caller's workspace, an NHWC activation (with how many hypotheses share each of its
+//     samples), and a forward's bookkeeping.  FwdCore holds the ONE copy of what every conv launch and every GroupNorm ends with under
+//     the NOPE_F16X2 range tracking (x2_range.h): conv_args (sources, the second pack) and conv_tracked (conv_plan, consumes / produce /
+//     overwritten), gn_apply (SiLU form, max |y| slot, launch, the fused 1x1 tail).  conv() / gn() are those and nothing more; the
+//     U-Net's own conv / gn put a second source, statistics and split-K scratch, PreNorm and profile events between the same halves;
+//   * ConvOpts / FwdReq: the optional inputs of a conv launch and one forward request, as structs whose fields are set by name;
 //   * the bodies the extern "C" entry points share: workspace base alignment, the x2 poll / range-check / enable trio, the poll in
 //     front of a forward, the tail of a create call, freeing a handle's device memory.
 // ResBlock networks (LDM, guided diffusion) add resblock_runtime.h on top.
@@ -131,7 +135,26 @@ struct Arena {
     }
 };
 
-struct Act { void* p = nullptr; int C = 0, H = 0, W = 0; };
+// rep: the tensor holds nhyp / rep samples, each shared by rep hypotheses of the forward that reads it
+struct Act { void* p = nullptr; int C = 0, H = 0, W = 0, rep = 1; };
+
+// The optional inputs of a conv launch, set by name.
+struct ConvOpts {
+    const void* resid = nullptr;            // added to the output (same layout)
+    int out_nchw = 0, out_dt = NOPE_F32;    // the network's output conv: NCHW of type out_dt
+    bool track_out = false;                 // the output goes straight into f16x2 convs: its epilogue records max |out| when it is one that can
+                                            // (the wide NHWC epilogue); otherwise a later f16x2 consumer of `out` takes an absmax pass over it
+};
+inline ConvOpts with_resid(const void* resid) { ConvOpts o; o.resid = resid; return o; }
+inline ConvOpts to_nchw(int out_dt) { ConvOpts o; o.out_nchw = 1; o.out_dt = out_dt; return o; }
+
+// One forward of a pose-conditioned network, as its entry point received it: out[j] = net(x[j / x_rep], pose[j]), n_hyp = n_src * x_rep.
+// Filled once per entry point (a workspace-size query leaves the pointers null).
+struct FwdReq {
+    const float* x = nullptr; const float* pose = nullptr; void* out = nullptr;
+    int out_dtype = NOPE_F32, n_src = 0, x_rep = 1, n_hyp = 0, H = 0, W = 0;
+    int split = 0;      // the U-Net's NOPE_SHARED_SPLIT of this forward
+};
 
 // One forward over `nhyp` samples.  N: the handle, a Net.
 template <class N> struct FwdCore {
@@ -161,26 +184,55 @@ template <class N> struct FwdCore {
         if (!p) chk(NOPE_ERR_WORKSPACE);
         return p;
     }
-    void conv(const PackedConv& c, const Act& a, void* out, int Ho, int Wo, const void* resid = nullptr, int out_nchw = 0, int out_dt = NOPE_F32,
-              int rep = 1, int n = -1) {
-        if (!live()) return;
-        ConvArgs ca;
-        ca.src1 = a.p; ca.C1 = a.C; ca.rep1 = rep; ca.Hs = a.H; ca.Ws = a.W; ca.Ho = Ho; ca.Wo = Wo;
-        ca.mode = c.mode; ca.ntaps = c.ntaps; ca.w = c.w; ca.bias = c.bias; ca.resid = resid; ca.out = out; ca.Cout = c.Cout;
-        ca.nhyp = n < 0 ? nhyp : n; ca.out_nchw = out_nchw; ca.out_dt = out_dt;
-        if (a.C != c.Cin) { chk(NOPE_ERR_ARG); return; }
-        if (c.w_x2 && !net->x2r.off) { ca.w_x2 = c.w_x2; ca.x2_t_zero = net->x2r.t_zero(c.x2_id) ? 1 : 0; }
-        const ConvLaunch L = conv_plan(net->dt, ca);
+    // First half of every conv launch: the ConvArgs of out = conv(a [cat b]) (+bias) (+o.resid) over nhyp samples, on the layer's NOPE_F16X2
+    // pack when it has one.  False (error latched, nothing else touched): the sources' channels are not the layer's.
+    bool conv_args(ConvArgs& ca, const PackedConv& c, const Act& a, const Act* b, void* out, int Ho, int Wo, const ConvOpts& o) {
+        if (a.C + (b ? b->C : 0) != c.Cin) { chk(NOPE_ERR_ARG); return false; }
+        ca.src1 = a.p; ca.C1 = a.C; ca.rep1 = a.rep;
+        if (b) { ca.src2 = b->p; ca.C2 = b->C; ca.rep2 = b->rep; }
+        ca.Hs = a.H; ca.Ws = a.W; ca.Ho = Ho; ca.Wo = Wo;
+        ca.mode = c.mode; ca.ntaps = c.ntaps; ca.w = c.w; ca.bias = c.bias; ca.resid = o.resid;
+        ca.out = out; ca.Cout = c.Cout; ca.nhyp = nhyp; ca.out_nchw = o.out_nchw; ca.out_dt = o.out_dt;
+        if (c.w_x2 && c.x2_id >= 0 && !net->x2r.off) { ca.w_x2 = c.w_x2; ca.x2_t_zero = net->x2r.t_zero(c.x2_id) ? 1 : 0; }
+        return true;
+    }
+    // Second half: the plan of the filled ConvArgs (made once: the tracking, a profile and launch_conv read the same decisions), tracked -- a
+    // two-pass launch makes its layer's shift follow its sources' maxima, a then b; the epilogue records max |out| (track_out, where the plan
+    // can) or out's stale slot is dropped.  The caller launches what comes back.
+    ConvLaunch conv_tracked(const ConvArgs& ca, const PackedConv& c, const Act& a, const Act* b, bool track_out) {
+        ConvLaunch L = conv_plan(net->dt, ca);
         if (tracking()) {
-            if (L.x2) {      // the two-pass tile: the layer's range shift follows its input's maximum
-                x2.consumes(c.x2_id, x2.slot_for(a.p, (size_t)(ca.nhyp / rep) * a.H * a.W * a.C));
+            if (L.x2 && c.x2_id >= 0) {
+                x2.consumes(c.x2_id, x2.slot_for(a.p, (size_t)(ca.nhyp / a.rep) * a.H * a.W * a.C));
+                if (b) x2.consumes(c.x2_id, x2.slot_for(b->p, (size_t)(ca.nhyp / b->rep) * b->H * b->W * b->C));
                 chk(x2.err);
             }
-            x2.overwritten(out);           // (conv epilogues record no maximum here: a two-pass consumer of `out` takes an absmax pass)
+            if (track_out && L.records_out_amax) {
+                const int sl = x2.produce(ca.out);
+                if (sl >= 0) L.record_out_amax(x2.slot_ptr(sl));
+            } else x2.overwritten(ca.out);
         }
-        chk(launch_conv(L, s));
+        return L;
     }
-    // y = [silu](GroupNorm(G, eps)(x))
+    void conv(const PackedConv& c, const Act& a, void* out, int Ho, int Wo, const ConvOpts& o = ConvOpts()) {
+        if (!live()) return;
+        ConvArgs ca;
+        if (conv_args(ca, c, a, nullptr, out, Ho, Wo, o)) chk(launch_conv(conv_tracked(ca, c, a, nullptr, o.track_out), s));
+    }
+    // The end of every GroupNorm: the SiLU form, y's range slot (the apply kernel records max |y|; records_max false, the FiLM instantiation: it
+    // does not), the launch.  True: ga named a fused 1x1 tail (GnApplyArgs::proj_*) that qualified -- one pass, y not written, no maximum for it.
+    bool gn_apply(GnApplyArgs& ga, bool records_max = true) {
+        ga.fast_silu = net->dt != NOPE_F32 ? 1 : 0;      // (f32 storage of the split-precision modes: hardware exp / rcp; the f32 mode keeps expf and the division)
+        const bool proj = ga.proj_out && gn_apply_proj_ok(net->sdt, ga);
+        if (tracking()) {
+            const int sl = records_max ? x2.produce(ga.y) : -1;
+            if (sl >= 0) ga.amax_out = x2.slot_ptr(sl);
+            if (!records_max || proj) x2.overwritten(ga.y);
+        }
+        chk(proj ? launch_gn_apply_proj(net->sdt, ga, s) : launch_gn_apply(net->sdt, ga, s));
+        return proj;
+    }
+    // y = [silu](GroupNorm(G, eps)(x)) [FiLM]
     void gn(const NormW& nm, int G, const void* x, void* y, int HW, int act, float eps, const float* film = nullptr, int film_stride = 0) {
         if (!live()) return;
         const int nch = gn_stats_chunks(HW, nm.C, net->sdt);
@@ -189,12 +241,7 @@ template <class N> struct FwdCore {
         ga.x = x; ga.y = y; ga.partial = gn_partial; ga.nchunk = nch; ga.gamma = nm.gamma; ga.beta = nm.beta;
         ga.nhyp = nhyp; ga.HW = HW; ga.C = nm.C; ga.G = G; ga.act = act; ga.eps = eps;
         ga.film = film; ga.film_stride = film_stride;
-        ga.fast_silu = net->dt != NOPE_F32 ? 1 : 0;      // (f32 storage of the split-precision modes: hardware exp / rcp; the f32 mode keeps expf and the division)
-        if (tracking()) {                                // (the FiLM instantiation records no maximum: its consumer takes an absmax pass)
-            if (!film) { const int sl = x2.produce(y); if (sl >= 0) ga.amax_out = x2.slot_ptr(sl); }
-            else x2.overwritten(y);
-        }
-        chk(launch_gn_apply(net->sdt, ga, s));
+        gn_apply(ga, !film);
     }
 };
 

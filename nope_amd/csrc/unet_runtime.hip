@@ -37,6 +37,8 @@
 #include "runtime_common.h"
 
 using namespace nope;
+using rt::Act;
+using rt::FwdReq;
 using rt::NormW;
 using rt::PackedConv;
 
@@ -53,8 +55,6 @@ struct Res {
 struct LinAttn { NormW pre, post; PackedConv qkv, out; float *c0 = nullptr, *c1 = nullptr; };
 struct Attn { NormW pre; PackedConv qkv, out; float *c0 = nullptr, *c1 = nullptr; };
 struct Level { Res r0, r1; LinAttn attn; PackedConv resample; };
-
-struct Act : rt::Act { int rep = 1; };      // rep: the tensor holds nhyp / rep samples, each shared by rep hypotheses
 
 }  // namespace
 
@@ -163,8 +163,27 @@ struct Loader : rt::LoaderCore {
 // the GroupNorm takes its own statistics pass)
 struct Stats { float* cs = nullptr; int blocks = 0; };
 
-// The shared core's bookkeeping (arena, error state, range tracking); conv / gn are this network's own: two sources, fused statistics,
-// PreNorm, the tail fusion
+// The optional inputs of Fwd::conv over rt::ConvOpts (resid, out_nchw / out_dt, track_out), set by name.
+struct ConvOpts : rt::ConvOpts {
+    Stats* stats = nullptr;                          // also emit the column statistics of the output when this launch can
+    const float *c0 = nullptr, *c1 = nullptr;        // PreNorm folded into this (qkv) conv: see LinAttn
+};
+// The 1x1 conv that is the ONLY reader of a block's output (the U-Net's tail), for the block's last GroupNorm pass to take along.
+struct ProjTail { const PackedConv* proj = nullptr; void* out = nullptr; int out_dt = NOPE_F32; };
+// The optional inputs of Fwd::gn, set by name.
+struct GnOpts {
+    int x_rep = 1;                                   // x holds nhyp / x_rep samples
+    int act = 1;                                     // SiLU
+    int emb_off = -1;                                // + this block's row of the embedding (offset into emb_all)
+    const void* resid = nullptr; int resid_rep = 1;  // + resid, each of its samples shared by resid_rep hypotheses
+    Stats stats;                                     // the producing conv's column statistics: they only need folding
+    float* out_stats = nullptr;                      // also emit the GroupNorm(1) partials of y (the next attention block's PreNorm)
+    const GnShared* sh = nullptr;                    // the shared addend: x_eff = [x] + S [+ E]
+    ProjTail tail;
+};
+
+// The shared core's bookkeeping (arena, error state) and the two halves of every conv launch and the end of every GroupNorm with their range
+// tracking; conv / gn add what is this network's own: fused statistics, split-K scratch, PreNorm, profile events, the shared addend
 struct Fwd : rt::FwdCore<nope_unet> {
     using Arena = rt::Arena;
     float* pn_partial = nullptr;   // (sum, sum sq) partials of the tensor that feeds the next attention block
@@ -174,140 +193,105 @@ struct Fwd : rt::FwdCore<nope_unet> {
 
     // run `fn` as a forward over n samples (the per-reference launches: profiled, traced and range-tracked like every other)
     template <class F> void over(int n, F fn) { const int keep = nhyp; nhyp = n; fn(); nhyp = keep; }
+    // ... on this view of an activation that rep hypotheses share: its samples, one each
+    static Act per_ref(Act a) { a.rep = 1; return a; }
+    static ConvOpts with_stats(Stats& st) { ConvOpts o; o.stats = &st; return o; }
     // a conv's packed weights without the NOPE_F16X2 pack: the per-reference launches stay on the three-pass kernels
     static PackedConv exact(PackedConv c) { c.w_x2 = nullptr; c.x2_id = -1; return c; }
 
-    // out = conv(a [cat b]) (+bias) (+resid);  n = number of samples computed (nhyp or fewer).  `stats`: also emit the column
-    // statistics of the output when this launch can (conv_stat_rows: whole 64-row blocks per sample on every kernel, 16 / 32-pixel
-    // maps on the small-tile kernel); the scratch comes from the arena and lives until the caller's release.
-    void conv(const PackedConv& c, const Act& a, const Act* b, void* out, int Ho, int Wo, int n, int rep1, int rep2,
-              const void* resid = nullptr, int out_nchw = 0, int out_dt = NOPE_F32, Stats* stats = nullptr,
-              const float* pn_c0 = nullptr, const float* pn_c1 = nullptr, bool track_out = false) {
+    // out = conv(a [cat b]) (+bias) (+resid) over nhyp samples.  o.stats: the launch emits its output's column statistics when it can
+    // (conv_stat_rows: whole 64-row blocks per sample on every kernel, 16 / 32-pixel maps on the small-tile kernel); the scratch comes
+    // from the arena and lives until the caller's release.
+    void conv(const PackedConv& c, const Act& a, const Act* b, void* out, int Ho, int Wo, const ConvOpts& o = ConvOpts()) {
         if (err != NOPE_OK) return;
         ConvArgs ca;
-        if (pn_c0) { ca.pn_ms = pn_ms; ca.pn_c0 = pn_c0; ca.pn_c1 = pn_c1; }
-        ca.src1 = a.p; ca.C1 = a.C; ca.rep1 = rep1;
-        if (b) { ca.src2 = b->p; ca.C2 = b->C; ca.rep2 = rep2; }
-        ca.Hs = a.H; ca.Ws = a.W; ca.Ho = Ho; ca.Wo = Wo;
-        ca.mode = c.mode; ca.ntaps = c.ntaps; ca.w = c.w; ca.w_x2 = net->x2r.off ? nullptr : c.w_x2; ca.bias = c.bias; ca.resid = resid;
-        if (ca.w_x2 && c.x2_id >= 0) ca.x2_t_zero = net->x2r.t_zero(c.x2_id) ? 1 : 0;
-        ca.out = out; ca.Cout = c.Cout; ca.nhyp = n; ca.out_nchw = out_nchw; ca.out_dt = out_dt;
-        if (a.C + (b ? b->C : 0) != c.Cin) { chk(NOPE_ERR_ARG); return; }
-        float* colstats = nullptr;
-        if (stats) {
+        if (!conv_args(ca, c, a, b, out, Ho, Wo, o)) return;
+        if (o.c0) { ca.pn_ms = pn_ms; ca.pn_c0 = o.c0; ca.pn_c1 = o.c1; }
+        if (o.stats) {
             const int sr = conv_stat_rows(net->dt, ca);
             if (sr > 0) {
-                const int HWo = Ho * Wo;
-                colstats = (float*)ar.alloc((size_t)n * (HWo / sr) * c.Cout * 2 * sizeof(float));
-                if (!colstats) { chk(NOPE_ERR_WORKSPACE); return; }
-                ca.colstats = colstats; ca.stat_rows = sr;
-                stats->cs = colstats; stats->blocks = HWo / sr;
+                const int blocks = Ho * Wo / sr;
+                ca.colstats = (float*)ar.alloc((size_t)nhyp * blocks * c.Cout * 2 * sizeof(float));
+                if (!ca.colstats) { chk(NOPE_ERR_WORKSPACE); return; }
+                ca.stat_rows = sr; *o.stats = Stats{ca.colstats, blocks};
             }
         }
         // few output tiles + long K (small hypothesis batches at the 4x4 level): deterministic split-K through a
         // scratch taken from the arena for the duration of the launch
         const size_t sk_mark = ar.off;
-        if (!pn_c0 && !out_nchw) {
+        if (!o.c0 && !o.out_nchw) {
             const int S = conv_splitk_factor(net->dt, ca);      // (1 for a conv that emits its statistics itself)
             if (S > 1) {
-                ca.splitk_bytes = (size_t)S * n * Ho * Wo * c.Cout * 4;
+                ca.splitk_bytes = (size_t)S * nhyp * Ho * Wo * c.Cout * 4;
                 ca.splitk_ws = ar.alloc(ca.splitk_bytes);
                 if (!ca.splitk_ws) { chk(NOPE_ERR_WORKSPACE); return; }
             }
         }
         struct Release { Arena& a; size_t m; ~Release() { a.off = m; } } release{ar, sk_mark};
         if (!live()) return;               // workspace-size query: only the arena bookkeeping above matters
-        ConvLaunch L = conv_plan(net->dt, ca);      // planned once: the range tracking, the profile and the launch read the same decisions
-        if (tracking()) {
-            if (L.x2 && c.x2_id >= 0) {      // this launch runs the two-pass tile: its layer's shift follows its inputs' maxima
-                x2.consumes(c.x2_id, x2.slot_for(a.p, (size_t)(n / rep1) * a.H * a.W * a.C));
-                if (b) x2.consumes(c.x2_id, x2.slot_for(b->p, (size_t)(n / rep2) * b->H * b->W * b->C));
-                chk(x2.err);
-            }
-            // `track_out`: this conv's output goes straight into f16x2 convs (the resampling convs, the bottleneck attention's output
-            // projection): its epilogue records max |out| when it is one that can (the wide NHWC epilogue); otherwise a later f16x2
-            // consumer of `out` takes an absmax pass over it
-            if (track_out && L.records_out_amax) {
-                const int sl = x2.produce(out);
-                if (sl >= 0) L.record_out_amax(x2.slot_ptr(sl));
-            } else x2.overwritten(out);
-        }
-        if (net->profile) {
-            nope_unet::Ev ev;
-            hipEventCreate(&ev.a); hipEventCreate(&ev.b);
-            ev.flops = L.flops;   // executed MACs (UP2P: 4 taps per output pixel; padding taps of small maps skipped)
-            // algorithmic HBM bytes: every input, weight and output element exactly once
-            ev.bytes = ((double)(n / rep1) * a.H * a.W * a.C + (b ? (double)(n / rep2) * a.H * a.W * b->C : 0.0) +
-                        (double)c.Cout * c.ntaps * c.Cin * (c.mode == NOPE_CONV_UP2P ? 4 : 1) + (double)n * Ho * Wo * c.Cout) * (double)es;
-            ev.info = nope_conv_launch_info{0.0, ev.flops, ev.bytes, L.kind, c.mode, c.ntaps, c.Cin, c.Cout, a.H, a.W, n,
-                                            net->dt != NOPE_BF16X3 ? 1 : L.x2 ? 2 : 3, L.posmajor ? 1 : 0};
-            hipEventRecord(ev.a, s);
-            chk(launch_conv(L, s));
-            hipEventRecord(ev.b, s);
-            net->evs.push_back(ev);
-        } else {
-            chk(launch_conv(L, s));
-        }
+        const ConvLaunch L = conv_tracked(ca, c, a, b, o.track_out);
+        if (!net->profile) { chk(launch_conv(L, s)); return; }
+        nope_unet::Ev ev;
+        hipEventCreate(&ev.a); hipEventCreate(&ev.b);
+        ev.flops = L.flops;   // executed MACs (UP2P: 4 taps per output pixel; padding taps of small maps skipped)
+        // algorithmic HBM bytes: every input, weight and output element exactly once
+        ev.bytes = ((double)(nhyp / a.rep) * a.H * a.W * a.C + (b ? (double)(nhyp / b->rep) * a.H * a.W * b->C : 0.0) +
+                    (double)c.Cout * c.ntaps * c.Cin * (c.mode == NOPE_CONV_UP2P ? 4 : 1) + (double)nhyp * Ho * Wo * c.Cout) * (double)es;
+        ev.info = nope_conv_launch_info{0.0, ev.flops, ev.bytes, L.kind, c.mode, c.ntaps, c.Cin, c.Cout, a.H, a.W, nhyp,
+                                        net->dt != NOPE_BF16X3 ? 1 : L.x2 ? 2 : 3, L.posmajor ? 1 : 0};
+        hipEventRecord(ev.a, s);
+        chk(launch_conv(L, s));
+        hipEventRecord(ev.b, s);
+        net->evs.push_back(ev);
     }
-    // y = act(GN(x)) [+emb] [+resid]; x holds n_x = nhyp / x_rep samples; `colstats` != null: statistics were
-    // produced by the conv epilogue and only need folding.
-    // proj (with proj_out): GroupNorm + SiLU + residual + this 1x1 conv in one pass (launch_gn_apply_proj: y is not written) when the arguments
+    // y = act(GN(x)) [+emb] [+resid]; x holds nhyp / o.x_rep samples.
+    // o.tail: GroupNorm + SiLU + residual + that 1x1 conv in one pass (launch_gn_apply_proj: y is not written) when the arguments
     // qualify; returns whether it did -- the caller launches the conv itself otherwise
-    bool gn(const NormW& nm, int G, const void* x, int x_rep, void* y, int HW, int act, int emb_off, const void* resid,
-            int resid_rep, const Stats& st = Stats(), float* out_stats = nullptr, const PackedConv* proj = nullptr, void* proj_out = nullptr, int proj_out_dt = NOPE_F32,
-            const GnShared* sh = nullptr) {
+    bool gn(const NormW& nm, int G, const void* x, void* y, int HW, const GnOpts& o = GnOpts()) {
         if (!live()) return false;
-        const int nx = nhyp / x_rep;
+        const int nx = nhyp / o.x_rep;
         int nch = 1;
         GnApplyArgs ga;
-        ga.x = x; ga.nhyp = nhyp; ga.HW = HW; ga.C = nm.C; ga.G = G; ga.x_rep = x_rep;
-        if (sh) {
+        ga.x = x; ga.nhyp = nhyp; ga.HW = HW; ga.C = nm.C; ga.G = G; ga.x_rep = o.x_rep;
+        if (o.sh) {
             // the shared addend (GnApplyArgs::sh_*): x_eff = [x] + S [+ E] is formed by the statistics pass and by the apply pass, never stored
-            ga.sh_s = sh->S; ga.sh_e = sh->E; ga.sh_rep = sh->s_rep; ga.sh_H = sh->H; ga.sh_W = sh->W;
+            ga.sh_s = o.sh->S; ga.sh_e = o.sh->E; ga.sh_rep = o.sh->s_rep; ga.sh_H = o.sh->H; ga.sh_W = o.sh->W;
             nch = gn_stats_chunks(HW, nm.C, net->sdt);
             chk(launch_gn_stats_shared(net->sdt, ga, gn_partial, nch, s));
-        } else if (st.cs) {
-            // Every gn_apply workgroup folds its sample's column statistics itself (st.blocks * C * 8 bytes out of L2 per workgroup; a
+        } else if (o.stats.cs) {
+            // Every gn_apply workgroup folds its sample's column statistics itself (stats.blocks * C * 8 bytes out of L2 per workgroup; a
             // separate fold launch costs ~7 us + a kernel boundary).  Round 2 measured the inline fold +0.25 ms per 512-hypothesis step
             // (one thread per group then); with the wave-wide group sums of round 4 it is -0.02 .. -0.05 ms there and -0.2 ms at 64
             // hypotheses (profiles/r04o_fold_inline_ab.txt): always on.  NOPE_GN_FOLD_INLINE = most re-read bytes per launch (0 = never).
             const long long fold_inline_max = NOPE_ENV_LL("NOPE_GN_FOLD_INLINE", 1ll << 50);
-            const long long refold = (long long)nhyp * gn_apply_blocks(HW, nm.C, net->sdt, nhyp) * st.blocks * nm.C * 8;
-            if (refold <= fold_inline_max) { ga.colstats = st.cs; ga.stat_blocks = st.blocks; }
-            else chk(launch_gn_fold(st.cs, gn_partial, nx, st.blocks, nm.C, G, s));
+            const long long refold = (long long)nhyp * gn_apply_blocks(HW, nm.C, net->sdt, nhyp) * o.stats.blocks * nm.C * 8;
+            if (refold <= fold_inline_max) { ga.colstats = o.stats.cs; ga.stat_blocks = o.stats.blocks; }
+            else chk(launch_gn_fold(o.stats.cs, gn_partial, nx, o.stats.blocks, nm.C, G, s));
         } else {
             nch = gn_stats_chunks(HW, nm.C, net->sdt);
             chk(launch_gn_stats(net->sdt, x, gn_partial, nx, HW, nm.C, G, nch, s));
         }
-        ga.y = y; ga.partial = gn_partial; ga.nchunk = nch; ga.gamma = nm.gamma; ga.beta = nm.beta; ga.act = act;
-        if (emb_off >= 0) { ga.emb = emb_all + emb_off; ga.emb_stride = net->emb_total; }
-        ga.resid = resid; ga.resid_rep = resid_rep; ga.out_stats = out_stats;
-        if (tracking()) { const int sl = x2.produce(y); if (sl >= 0) ga.amax_out = x2.slot_ptr(sl); }
-        ga.fast_silu = net->dt != NOPE_F32 ? 1 : 0;      // (f32 storage of the split-precision modes: hardware exp / rcp; the f32 mode keeps expf and the division)
-        if (proj && proj_out && net->final_w_raw) {
-            ga.proj_w = net->final_w_raw; ga.proj_b = proj->bias; ga.proj_cout = proj->Cout; ga.proj_out = proj_out; ga.proj_out_dt = proj_out_dt;
-            if (gn_apply_proj_ok(net->sdt, ga)) {
-                if (tracking()) x2.overwritten(y);        // (y keeps whatever it held: no maximum recorded for it)
-                chk(launch_gn_apply_proj(net->sdt, ga, s));
-                return true;
-            }
+        ga.y = y; ga.partial = gn_partial; ga.nchunk = nch; ga.gamma = nm.gamma; ga.beta = nm.beta; ga.act = o.act;
+        if (o.emb_off >= 0) { ga.emb = emb_all + o.emb_off; ga.emb_stride = net->emb_total; }
+        ga.resid = o.resid; ga.resid_rep = o.resid_rep; ga.out_stats = o.out_stats;
+        if (o.tail.proj && o.tail.out && net->final_w_raw) {
+            ga.proj_w = net->final_w_raw; ga.proj_b = o.tail.proj->bias; ga.proj_cout = o.tail.proj->Cout; ga.proj_out = o.tail.out; ga.proj_out_dt = o.tail.out_dt;
         }
-        chk(launch_gn_apply(net->sdt, ga, s));
-        return false;
+        return gn_apply(ga);
     }
 
-    // ResnetBlock, model_utils.py:271-279.  `a` may be shared by a.rep hypotheses (rep > 1 only
-    // for the very first block, where b == nullptr).
+    // ResnetBlock, model_utils.py:271-279.  `a` may be shared by a.rep hypotheses (rep > 1 only for the very first block, where b == nullptr).
     // `next_is_attention`: also emit the GroupNorm(1) partials of the block's output into pn_partial.
-    // proj / proj_out: the 1x1 conv that is the ONLY reader of the block's output (the U-Net's tail), fused into the block's last pass where gn() can;
-    // returns whether it was (then `out` holds the un-normalised conv output and must not be read)
-    bool resnet(const Res& R, const Act& a, const Act* b, bool use_emb, void* out, bool next_is_attention = false, const PackedConv* proj = nullptr,
-                void* proj_out = nullptr, int proj_out_dt = NOPE_F32) {
+    // tail: fused into the block's last pass where gn() can; returns whether it was (then `out` holds the un-normalised conv output and
+    // must not be read)
+    bool resnet(const Res& R, const Act& a, const Act* b, bool use_emb, void* out, bool next_is_attention = false, const ProjTail& tail = ProjTail()) {
         const int HW = a.H * a.W, G = net->cfg.groups;
         const size_t M = (size_t)nhyp * HW;
         const size_t mark = ar.off;
         const int emb_off = use_emb ? R.emb_off : -1;
         const bool f32_acts = net->sdt == NOPE_F32 && a.H >= 2 && a.W >= 2;      // (S and E are f32; a 1-pixel-wide map has no nine border classes)
+        GnOpts g2;                     // the block's last GroupNorm: + the block's input (or res_conv of it)
+        g2.resid = a.p; g2.resid_rep = a.rep; g2.out_stats = next_is_attention ? pn_partial : nullptr;
         if (a.rep > 1 && !b && (split & 1) && !R.has_res && R.c2_cls && use_emb && f32_acts) {
             // downs[0][0] with NOPE_SHARED_SPLIT bit 0: block2 convolves u + e_n 1, u = SiLU(GN(block1(x0))) per reference and e_n this block's
             // embedding row, constant over the map.  By linearity conv2(u + e_n 1)[p] = S[p] + E[n][cls(p)]: S = conv2(u) + bias once per
@@ -320,11 +304,10 @@ struct Fwd : rt::FwdCore<nope_unet> {
             float* erows = alloc_f32((size_t)nhyp * C);
             float* E = alloc_f32((size_t)nhyp * 9 * C);
             over(ns, [&] {
-                Stats cs;
-                conv(R.c1, a, nullptr, t1s, a.H, a.W, ns, 1, 1, nullptr, 0, NOPE_F32, &cs);
-                gn(R.n1, G, t1s, 1, us, HW, 1, -1, nullptr, 1, cs);
-                Act u{us, C, a.H, a.W, 1};
-                conv(exact(R.c2), u, nullptr, S, a.H, a.W, ns, 1, 1);
+                GnOpts g1;
+                conv(R.c1, per_ref(a), nullptr, t1s, a.H, a.W, with_stats(g1.stats));
+                gn(R.n1, G, t1s, us, HW, g1);
+                conv(exact(R.c2), Act{us, C, a.H, a.W}, nullptr, S, a.H, a.W);
             });
             if (live()) {
                 if (hipMemcpy2DAsync(erows, (size_t)C * 4, emb_all + emb_off, (size_t)net->emb_total * 4, (size_t)C * 4, (size_t)nhyp, hipMemcpyDeviceToDevice, s) != hipSuccess)
@@ -334,44 +317,44 @@ struct Fwd : rt::FwdCore<nope_unet> {
                 chk(launch_conv(NOPE_F32, ea, s));
             }
             const GnShared sh{S, E, a.rep, a.H, a.W};
-            gn(R.n2, G, nullptr, 1, out, HW, 1, -1, a.p, a.rep, Stats(), next_is_attention ? pn_partial : nullptr, nullptr, nullptr, NOPE_F32, &sh);
+            g2.sh = &sh;
+            gn(R.n2, G, /*x: S + E alone*/ nullptr, out, HW, g2);
             ar.off = mark;
             return false;
         }
         void* t1 = alloc_act(M * R.c1.Cout);
+        GnOpts g1;                     // block1's GroupNorm: + the embedding row, in place
+        g1.emb_off = emb_off;
         if (b && b->rep > 1 && a.rep == 1 && (split & 2) && R.c1_hyp.w && R.c1_ref.w && f32_acts) {
             // final_res_block with NOPE_SHARED_SPLIT bit 1: block1 convolves cat(cur, r), r = x0 per reference.  By linearity over the input
             // channels conv(W, cat(cur, r)) = conv(W[:, :C1], cur) + Sr, Sr = conv(W[:, C1:], r) + bias once per reference: the per-hypothesis
             // launch has half the K.  The epilogue's column statistics no longer see the whole GroupNorm input: a statistics pass forms cur' + Sr.
             const int ns = nhyp / b->rep;
             float* Sr = (float*)alloc_act((size_t)ns * HW * R.c1.Cout);
-            over(ns, [&] { conv(exact(R.c1_ref), *b, nullptr, Sr, a.H, a.W, ns, 1, 1); });
-            conv(R.c1_hyp, a, nullptr, t1, a.H, a.W, nhyp, 1, 1);
+            over(ns, [&] { conv(exact(R.c1_ref), per_ref(*b), nullptr, Sr, a.H, a.W); });
+            conv(R.c1_hyp, a, nullptr, t1, a.H, a.W);
             const GnShared sh{Sr, nullptr, b->rep, a.H, a.W};
-            gn(R.n1, G, t1, 1, t1, HW, 1, emb_off, nullptr, 1, Stats(), nullptr, nullptr, nullptr, NOPE_F32, &sh);
+            g1.sh = &sh;
+            gn(R.n1, G, t1, t1, HW, g1);
         } else if (a.rep > 1 && !b) {
             // pose-independent prefix: conv + GN statistics once per reference sample
             const int ns = nhyp / a.rep;
             void* t1s = alloc_act((size_t)ns * HW * R.c1.Cout);
-            Stats cs;
-            conv(R.c1, a, nullptr, t1s, a.H, a.W, ns, 1, 1, nullptr, 0, NOPE_F32, &cs);
-            gn(R.n1, G, t1s, a.rep, t1, HW, 1, emb_off, nullptr, 1, cs);
+            over(ns, [&] { conv(R.c1, per_ref(a), nullptr, t1s, a.H, a.W, with_stats(g1.stats)); });
+            g1.x_rep = a.rep;
+            gn(R.n1, G, t1s, t1, HW, g1);
         } else {
-            Stats cs;
-            conv(R.c1, a, b, t1, a.H, a.W, nhyp, a.rep, b ? b->rep : 1, nullptr, 0, NOPE_F32, &cs);
-            gn(R.n1, G, t1, 1, t1, HW, 1, emb_off, nullptr, 1, cs);
+            conv(R.c1, a, b, t1, a.H, a.W, with_stats(g1.stats));
+            gn(R.n1, G, t1, t1, HW, g1);
         }
-        Act h{t1, R.c1.Cout, a.H, a.W, 1};
-        Stats cs2;
-        conv(R.c2, h, nullptr, out, a.H, a.W, nhyp, 1, 1, nullptr, 0, NOPE_F32, &cs2);
-        const void* resid = a.p;
-        int resid_rep = a.rep;
+        conv(R.c2, Act{t1, R.c1.Cout, a.H, a.W}, nullptr, out, a.H, a.W, with_stats(g2.stats));
         if (R.has_res) {
             void* t3 = alloc_act(M * R.res.Cout);
-            conv(R.res, a, b, t3, a.H, a.W, nhyp, a.rep, b ? b->rep : 1);
-            resid = t3; resid_rep = 1;
+            conv(R.res, a, b, t3, a.H, a.W);
+            g2.resid = t3; g2.resid_rep = 1;
         } else if (b) { chk(NOPE_ERR_ARG); }
-        const bool fused = gn(R.n2, G, out, 1, out, HW, 1, -1, resid, resid_rep, cs2, next_is_attention ? pn_partial : nullptr, proj, proj_out, proj_out_dt);
+        g2.tail = tail;
+        const bool fused = gn(R.n2, G, out, out, HW, g2);
         ar.off = mark;
         return fused;
     }
@@ -382,7 +365,8 @@ struct Fwd : rt::FwdCore<nope_unet> {
         if (!live()) return;
         const int HW = x.H * x.W;
         chk(launch_gn_finalize(pn_partial, pn_ms, nhyp, gn_apply_blocks(HW, x.C, net->sdt, nhyp), (float)HW * (float)x.C, 1e-5f, s));
-        conv(qkvw, x, nullptr, qkv, x.H, x.W, nhyp, 1, 1, nullptr, 0, NOPE_F32, nullptr, c0, c1);
+        ConvOpts o; o.c0 = c0; o.c1 = c1;
+        conv(qkvw, x, nullptr, qkv, x.H, x.W, o);
     }
 
     // Residual(PreNorm(LinearAttention)), model_utils.py:198-204,226-234,393-418.  x must come from
@@ -396,10 +380,10 @@ struct Fwd : rt::FwdCore<nope_unet> {
         void* a = alloc_act(M * heads * dh);
         qkv_prenorm(L.qkv, L.c0, L.c1, x, qkv);
         if (live()) { chk(launch_linattn(net->sdt, qkv, a, nhyp, HW, heads, dh, s)); x2.overwritten(a); }
-        Act aa{a, heads * dh, x.H, x.W, 1};
-        Stats cs;
-        conv(L.out, aa, nullptr, y, x.H, x.W, nhyp, 1, 1, nullptr, 0, NOPE_F32, &cs);
-        gn(L.post, 1, y, 1, out, HW, 0, -1, x.p, 1, cs);
+        GnOpts post;                   // GroupNorm(1) without SiLU, + x
+        conv(L.out, Act{a, heads * dh, x.H, x.W}, nullptr, y, x.H, x.W, with_stats(post.stats));
+        post.act = 0; post.resid = x.p;
+        gn(L.post, 1, y, out, HW, post);
         ar.off = mark;
     }
 
@@ -412,19 +396,19 @@ struct Fwd : rt::FwdCore<nope_unet> {
         void* a = alloc_act(M * heads * dh);
         qkv_prenorm(A.qkv, A.c0, A.c1, x, qkv);
         if (live()) { chk(launch_attn(net->sdt, qkv, a, nhyp, HW, heads, dh, s)); x2.overwritten(a); }
-        Act aa{a, heads * dh, x.H, x.W, 1};
-        conv(A.out, aa, nullptr, out, x.H, x.W, nhyp, 1, 1, /*resid=*/x.p, 0, NOPE_F32, nullptr, nullptr, nullptr, /*track_out=*/true);
+        ConvOpts o; o.resid = x.p; o.track_out = true;
+        conv(A.out, Act{a, heads * dh, x.H, x.W}, nullptr, out, x.H, x.W, o);
         ar.off = mark;
     }
 };
 
-int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, const float* pose, int n_hyp, int H, int W,
-                void* out, int out_dtype, void* ws, size_t ws_bytes, hipStream_t s, bool dry, size_t* peak, int split) {
+// dry: a workspace-size query -- all of the arena bookkeeping, none of the launches; the arena's peak goes to *peak
+int run_forward(const nope_unet* net, const FwdReq& q, void* ws, size_t ws_bytes, hipStream_t s, bool dry = false, size_t* peak = nullptr) {
     const nope_unet_config& cfg = net->cfg;
-    const int L = cfg.n_levels;
+    const int L = cfg.n_levels, n_src = q.n_src, n_hyp = q.n_hyp, H = q.H, W = q.W;
     Fwd f;
     f.begin(net, n_hyp, ws, ws_bytes, s, dry);
-    f.split = split;
+    f.split = q.split;
     const int HW = H * W;
     const int* dims = net->dims;
 
@@ -460,9 +444,9 @@ int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, cons
 
     // ---- input + pose embedding ----------------------------------------------------------------
     if (f.live()) {
-        f.chk(launch_nchw_to_nhwc(net->sdt, x, x_in, n_src, cin_k, HW, s, cfg.channels));
-        if (cfg.pose_mlp_layers == 0) f.chk(launch_pos_emb(pose, c0, n_hyp, cfg.pose_dim, net->classes, s));   // u_net.py:73-76
-        else f.chk(launch_linear_naive(pose, net->pose_w0, net->pose_b0, c0, n_hyp, net->classes, cfg.pose_dim, 0, net->classes, s));
+        f.chk(launch_nchw_to_nhwc(net->sdt, q.x, x_in, n_src, cin_k, HW, s, cfg.channels));
+        if (cfg.pose_mlp_layers == 0) f.chk(launch_pos_emb(q.pose, c0, n_hyp, cfg.pose_dim, net->classes, s));   // u_net.py:73-76
+        else f.chk(launch_linear_naive(q.pose, net->pose_w0, net->pose_b0, c0, n_hyp, net->classes, cfg.pose_dim, 0, net->classes, s));
         const float* c = c0;
         if (cfg.pose_mlp_layers == 2) {
             f.chk(launch_linear_naive(c0, net->pose_w2, net->pose_b2, c1, n_hyp, net->classes, net->classes, 2, net->classes, s));
@@ -475,34 +459,28 @@ int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, cons
         ea.Cout = net->emb_total; ea.nhyp = n_hyp;
         f.chk(launch_conv(NOPE_F32, ea, s));
     }
-    Act xin{x_in, cin_k, H, W, 1};
-    {
-        Fwd g = f;   // init_conv runs over the n_src reference samples only
-        g.nhyp = n_src;
-        g.conv(net->init_conv, xin, nullptr, x0, H, W, n_src, 1, 1);
-        f.chk(g.err);
-        f.x2 = g.x2;
-    }
-    Act r0{x0, dims[0], H, W, x_rep};
+    f.over(n_src, [&] { f.conv(net->init_conv, Act{x_in, cin_k, H, W}, nullptr, x0, H, W); });      // once per reference sample
+    Act r0{x0, dims[0], H, W, q.x_rep};
+    ConvOpts tracked; tracked.track_out = true;      // the resampling convs: their outputs go straight into f16x2 convs
     Act cur = r0;
     int slot = 0;
 
     // ---- down path ---------------------------------------------------------------------------------
     for (int l = 0; l < L; ++l) {
         const Level& D = net->downs[l];
-        Act h1{hbuf[2 * l], dims[l], cur.H, cur.W, 1};
-        Act h2{hbuf[2 * l + 1], dims[l], cur.H, cur.W, 1};
+        Act h1{hbuf[2 * l], dims[l], cur.H, cur.W};
+        Act h2{hbuf[2 * l + 1], dims[l], cur.H, cur.W};
         f.resnet(D.r0, cur, nullptr, true, h1.p);
         {
             const size_t mark = f.ar.off;
-            Act t{f.alloc_act((size_t)n_hyp * cur.H * cur.W * dims[l]), dims[l], cur.H, cur.W, 1};
+            Act t{f.alloc_act((size_t)n_hyp * cur.H * cur.W * dims[l]), dims[l], cur.H, cur.W};
             f.resnet(D.r1, h1, nullptr, true, t.p, /*next_is_attention=*/true);
             f.linattn(D.attn, t, h2.p);
             f.ar.off = mark;
         }
-        Act nxt{curbuf[slot], dims[l + 1], cur.H, cur.W, 1};
+        Act nxt{curbuf[slot], dims[l + 1], cur.H, cur.W};
         if (l < L - 1) { nxt.H = cur.H / 2; nxt.W = cur.W / 2; }
-        f.conv(D.resample, h2, nullptr, nxt.p, nxt.H, nxt.W, n_hyp, 1, 1, nullptr, 0, NOPE_F32, nullptr, nullptr, nullptr, /*track_out=*/true);
+        f.conv(D.resample, h2, nullptr, nxt.p, nxt.H, nxt.W, tracked);
         cur = nxt;
         slot ^= 1;
     }
@@ -510,11 +488,11 @@ int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, cons
     for (int it = 0; it < 2; ++it) {
         const size_t mark = f.ar.off;
         const size_t e = (size_t)n_hyp * cur.H * cur.W * cur.C;
-        Act a{f.alloc_act(e), cur.C, cur.H, cur.W, 1};
-        Act b{f.alloc_act(e), cur.C, cur.H, cur.W, 1};
+        Act a{f.alloc_act(e), cur.C, cur.H, cur.W};
+        Act b{f.alloc_act(e), cur.C, cur.H, cur.W};
         f.resnet(net->mid1, cur, nullptr, true, a.p, /*next_is_attention=*/true);
         f.attn(net->mid_attn, a, b.p);
-        Act c{curbuf[slot], cur.C, cur.H, cur.W, 1};
+        Act c{curbuf[slot], cur.C, cur.H, cur.W};
         f.resnet(net->mid2, b, nullptr, true, c.p);
         f.ar.off = mark;
         cur = c;
@@ -524,18 +502,18 @@ int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, cons
     for (int l = 0; l < L; ++l) {
         const Level& U = net->ups[l];
         const int r = L - 1 - l;
-        Act h2{hbuf[2 * r + 1], dims[r], cur.H, cur.W, 1};
-        Act h1{hbuf[2 * r], dims[r], cur.H, cur.W, 1};
+        Act h2{hbuf[2 * r + 1], dims[r], cur.H, cur.W};
+        Act h1{hbuf[2 * r], dims[r], cur.H, cur.W};
         const size_t mark = f.ar.off;
         const size_t e = (size_t)n_hyp * cur.H * cur.W * dims[r + 1];
-        Act a{f.alloc_act(e), dims[r + 1], cur.H, cur.W, 1};
-        Act b{f.alloc_act(e), dims[r + 1], cur.H, cur.W, 1};
+        Act a{f.alloc_act(e), dims[r + 1], cur.H, cur.W};
+        Act b{f.alloc_act(e), dims[r + 1], cur.H, cur.W};
         f.resnet(U.r0, cur, &h2, true, a.p);
         f.resnet(U.r1, a, &h1, true, b.p, /*next_is_attention=*/true);
         f.linattn(U.attn, b, a.p);
-        Act nxt{curbuf[slot], dims[r], cur.H, cur.W, 1};
+        Act nxt{curbuf[slot], dims[r], cur.H, cur.W};
         if (l < L - 1) { nxt.H = cur.H * 2; nxt.W = cur.W * 2; }
-        f.conv(U.resample, a, nullptr, nxt.p, nxt.H, nxt.W, n_hyp, 1, 1, nullptr, 0, NOPE_F32, nullptr, nullptr, nullptr, /*track_out=*/true);
+        f.conv(U.resample, a, nullptr, nxt.p, nxt.H, nxt.W, tracked);
         f.ar.off = mark;
         cur = nxt;
         slot ^= 1;
@@ -544,17 +522,19 @@ int run_forward(const nope_unet* net, const float* x, int n_src, int x_rep, cons
     {
         const size_t mark = f.ar.off;
         const size_t e = (size_t)n_hyp * HW * cfg.u_net_dim;
-        Act a{f.alloc_act(e), cfg.u_net_dim, H, W, 1};
-        Act b{f.alloc_act(e), cfg.u_net_dim, H, W, 1};
+        Act a{f.alloc_act(e), cfg.u_net_dim, H, W};
+        Act b{f.alloc_act(e), cfg.u_net_dim, H, W};
         f.resnet(net->final_res, cur, &r0, true, a.p);
         // final_conv = ResnetBlock -> Conv2d(dim, out_dim, 1) (u_net.py:154-157,197): the 1x1 conv rides in the block's last GroupNorm pass in the
         // split-precision modes (NOPE_FINAL_FUSED=0: its own launch, as in the other modes)
-        if (!f.resnet(net->final_conv0, a, nullptr, false, b.p, false, &net->final_conv1, out, out_dtype))
-            f.conv(net->final_conv1, b, nullptr, out, H, W, n_hyp, 1, 1, nullptr, /*out_nchw=*/1, out_dtype);
+        if (!f.resnet(net->final_conv0, a, nullptr, false, b.p, false, ProjTail{&net->final_conv1, q.out, q.out_dtype})) {
+            ConvOpts o; o.out_nchw = 1; o.out_dt = q.out_dtype;
+            f.conv(net->final_conv1, b, nullptr, q.out, H, W, o);
+        }
         f.ar.off = mark;
     }
     if (f.tracking())      // the forward's verdict and, if a layer left its window, NaNs over its output -- device side, no synchronisation (x2_range.h)
-        f.chk(f.x2.finish(out, (size_t)n_hyp * cfg.out_dim * HW * (size_t)(out_dtype == NOPE_F32 ? 4 : 2), out_dtype));
+        f.chk(f.x2.finish(q.out, (size_t)n_hyp * cfg.out_dim * HW * (size_t)(q.out_dtype == NOPE_F32 ? 4 : 2), q.out_dtype));
     if (peak) *peak = f.ar.peak;
     return f.err;
 }
@@ -756,10 +736,11 @@ static size_t unet_stage_bytes(const nope_unet* net, int n_hyp, int n_src, int H
 size_t nope_unet_workspace_bytes(const nope_unet* net, int n_hyp, int n_src, int H, int W) {
     if (!net || n_src <= 0 || n_hyp % n_src) return 0;
     if (check_shape(net, n_hyp, n_src, n_hyp / n_src, H, W) != NOPE_OK) return 0;
+    FwdReq q; q.n_src = n_src; q.x_rep = n_hyp / n_src; q.n_hyp = n_hyp; q.H = H; q.W = W;
     size_t peak = 0;
-    for (int split = 0; split <= 3; split += 3) {      // NOPE_SHARED_SPLIT is read per forward: the workspace holds either schedule
+    for (q.split = 0; q.split <= 3; q.split += 3) {      // NOPE_SHARED_SPLIT is read per forward: the workspace holds either schedule
         size_t pk = 0;
-        run_forward(net, nullptr, n_src, n_hyp / n_src, nullptr, n_hyp, H, W, nullptr, NOPE_F32, nullptr, 0, nullptr, true, &pk, split);
+        run_forward(net, q, nullptr, 0, nullptr, true, &pk);
         if (pk > peak) peak = pk;
     }
     size_t xb, pb, ob;
@@ -785,8 +766,9 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
                             !(net->x2 && net->x2r.active());
     rt::x2_poll_before_forward(net, stream);
     const int split = NOPE_ENV("NOPE_SHARED_SPLIT", 3) & 3;
-    if (!want_graph)
-        return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr, split);
+    FwdReq q; q.x = x; q.pose = pose; q.out = out; q.out_dtype = out_dtype;
+    q.n_src = n_src; q.x_rep = x_rep; q.n_hyp = n_hyp; q.H = H; q.W = W; q.split = split;
+    if (!want_graph) return run_forward(net, q, base, avail, s);
     std::lock_guard<std::mutex> lock(net->graph_mu);
     if (net->graph_split != split) {           // the launch plan changes: cached graphs are stale (as in nope_unet_x2_enable)
         for (const UGraph& g : net->graphs) hipGraphExecDestroy(g.exec);
@@ -805,16 +787,18 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
     if (!hit) {
         {   // dry pass: fail on a too-small arena BEFORE a capture is open
             size_t peak = 0;
-            e = run_forward(net, nullptr, n_src, x_rep, nullptr, n_hyp, H, W, nullptr, out_dtype, nullptr, 0, nullptr, true, &peak, split);
+            e = run_forward(net, q, nullptr, 0, nullptr, true, &peak);
             if (e) return e;
             if (align_up(peak, 256) > arena_bytes) return NOPE_ERR_WORKSPACE;
         }
         if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
             (void)hipGetLastError();
             net->graphs_ok = false;
-            return run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr, split);
+            return run_forward(net, q, base, avail, s);
         }
-        e = run_forward(net, x_s, n_src, x_rep, pose_s, n_hyp, H, W, out_s, out_dtype, arena, arena_bytes, s, false, nullptr, split);
+        FwdReq staged = q;      // the graph reads and writes the staging buffers: the caller's pointers stay out of it
+        staged.x = x_s; staged.pose = pose_s; staged.out = out_s;
+        e = run_forward(net, staged, arena, arena_bytes, s);
         hipGraph_t graph = nullptr;
         const hipError_t ce = hipStreamEndCapture(s, &graph);
         hipGraphExec_t exec = nullptr;
@@ -822,7 +806,7 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
             if (graph) hipGraphDestroy(graph);
             (void)hipGetLastError();
             net->graphs_ok = false;
-            return e != NOPE_OK ? e : run_forward(net, x, n_src, x_rep, pose, n_hyp, H, W, out, out_dtype, base, avail, s, false, nullptr, split);
+            return e != NOPE_OK ? e : run_forward(net, q, base, avail, s);
         }
         hipGraphDestroy(graph);
         if (net->graphs.size() >= 16) { hipGraphExecDestroy(net->graphs.front().exec); net->graphs.erase(net->graphs.begin()); }

@@ -141,10 +141,10 @@ struct Loader : LoaderCore {
 
 struct Fwd : FwdCore<nope_vae> {
     Act act(int C, int H, int W) { return Act{alloc_act((size_t)nhyp * H * W * C), C, H, W}; }
-    // conv of `a` into `out` (NHWC of the storage type, or NCHW f32 with out_nchw); output size from the geometry
-    void conv(const PackedConv& c, const Act& a, void* out, const void* resid = nullptr, int out_nchw = 0) {
+    // conv of `a` into `out` (NHWC of the storage type, or NCHW f32 with to_nchw); output size from the geometry
+    void conv(const PackedConv& c, const Act& a, void* out, const ConvOpts& o = ConvOpts()) {
         const int up = c.mode == NOPE_CONV_UP2P, down = c.mode == NOPE_CONV_STRIDE2_PAD01;
-        FwdCore::conv(c, a, out, up ? 2 * a.H : down ? a.H / 2 : a.H, up ? 2 * a.W : down ? a.W / 2 : a.W, resid, out_nchw);
+        FwdCore::conv(c, a, out, up ? 2 * a.H : down ? a.H / 2 : a.H, up ? 2 * a.W : down ? a.W / 2 : a.W, o);
     }
     // y = [silu](GroupNorm(norm_num_groups, eps)(x))
     void gn(const NormW& nm, const Act& x, void* y, int act) { FwdCore::gn(nm, net->cfg.norm_num_groups, x.p, y, x.H * x.W, act, net->eps); }
@@ -161,7 +161,7 @@ struct Fwd : FwdCore<nope_vae> {
             conv(R.sc, x, sk.p);
             resid = sk.p;
         }
-        conv(R.c2, t2, out, resid);
+        conv(R.c2, t2, out, with_resid(resid));
         ar.off = mark;
     }
     // AttnBlock: out = x + proj_attn(softmax(q k^T / sqrt(C)) v), q | k | v = Linear(GroupNorm(x))
@@ -172,7 +172,7 @@ struct Fwd : FwdCore<nope_vae> {
         gn(A.norm, x, t.p, 0);
         conv(A.qkv, t, qkv.p);
         if (live()) chk(C <= 128 ? launch_token_attention(net->dt, qkv.p, o.p, nhyp, HW, C, C, s) : launch_wide_attention(net->dt, qkv.p, o.p, nhyp, HW, C, s));
-        conv(A.proj, o, out, x.p);
+        conv(A.proj, o, out, with_resid(x.p));
         ar.off = mark;
     }
     // the network's activations alternate between two slots sized for the largest one (block temporaries sit above them): out = other(in)
@@ -234,7 +234,7 @@ int run_encode(const nope_vae* net, const float* image, int n, int H, int W, flo
     f.gn(net->e_norm_out, h, t.p, 1);
     Act m = f.act(net->mp, h.H, h.W);
     f.conv(net->e_conv_out, t, m.p);
-    f.conv(net->quant, m, latent, nullptr, 1);          // first latent_channels moments x 0.18215, NCHW f32
+    f.conv(net->quant, m, latent, to_nchw(NOPE_F32));          // first latent_channels moments x 0.18215, NCHW f32
     return f.finish(peak);
 }
 
@@ -261,7 +261,7 @@ int run_decode(const nope_vae* net, const float* latent, int n, int h, int w, fl
     }
     Act t = f.act(x.C, x.H, x.W);
     f.gn(net->d_norm_out, x, t.p, 1);
-    f.conv(unnorm ? net->d_conv_out_un : net->d_conv_out, t, image, nullptr, 1);
+    f.conv(unnorm ? net->d_conv_out_un : net->d_conv_out, t, image, to_nchw(NOPE_F32));
     return f.finish(peak);
 }
 
