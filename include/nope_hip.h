@@ -86,9 +86,10 @@ typedef void* nope_stream_t;
  * 12: nope_vis_column, nope_op_vis_grid, nope_op_vis_sheet, NOPE_VIS_*;
  * 13: nope_op_crop_frames;
  * 14: nope_op_group_norm_shared, nope_op_conv_class_weights;
- * 15: nope_op_refine_init / _normal_eq / _normal_eq_workspace_bytes / _step / _select, NOPE_REFINE_*).  Callers compare nope_abi_version() against the header they were
+ * 15: nope_op_refine_init / _normal_eq / _normal_eq_workspace_bytes / _step / _select, NOPE_REFINE_*;
+ * 16: nope_op_conv_gn_tail, nope_op_conv_tail_stat_blocks).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 15
+#define NOPE_ABI_VERSION 16
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -568,6 +569,19 @@ int nope_op_group_norm_shared(int dtype, const void* x, void* y, float* partial,
                               const void* resid, int resid_rep, float* out_stats, float eps, int fast_silu, uint32_t* amax_slot, float* amax_out,
                               nope_stream_t s);
 int nope_op_conv_class_weights(const float* w, float* out, int Cout, int Cin, nope_stream_t s);
+/* (ABI 16) nope_op_conv_gn_tail: the end of a ResnetBlock with a res_conv as the U-Net runtime launches it in the split-precision modes,
+ *     out[m, n] = conv1x1(src1 [cat src2])[m, n] + bias[n] + SiLU(GroupNorm(G)(resid)[m, n] gamma[n] + beta[n]),
+ *   in two launches: (mean, rstd) [n_hyp][G][2] of resid from its producer's column statistics colstats [n_hyp][stat_blocks][Cout][2] (rows of 64;
+ *   nope_op_conv_ex) into `ms`, then the conv, whose epilogue normalises and activates each residual vector on its way in.  Same arithmetic as
+ *   nope_op_group_norm_ex (fast_silu = 1, that colstats, act_silu = 1) with the conv's output as ITS residual: bit-identical.  resid may be
+ *   `out` (in place).  tail_stats [n_hyp][nope_op_conv_tail_stat_blocks()][2] or NULL: (sum, sum of squares) of the values written per 64-row x
+ *   96-column tile, for nope_op_gn_finalize.  NOPE_BF16X3 / NOPE_F16X2 only, and only a launch the policy in force puts on the per-tap ping-pong
+ *   kernel with the lean epilogue, H W a multiple of 64, (Cout / G) a multiple of 4, at most 64 tail_stats entries per hypothesis:
+ *   NOPE_ERR_UNSUPPORTED otherwise -- never a launch without the tail. */
+int nope_op_conv_tail_stat_blocks(int HW, int Cout);
+int nope_op_conv_gn_tail(int dtype, const void* src1, int C1, const void* src2, int C2, int Hs, int Ws, const void* w_packed, const float* bias,
+                         const void* resid, void* out, int Cout, int n_hyp, const float* colstats, int stat_blocks, const float* gamma,
+                         const float* beta, int G, float eps, float* ms, float* tail_stats, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
 /* max |x[i]| over n f32 values (NaNs ignored; 0 for n = 0 or all zeros): what the runtimes run over conv-produced tensors in NOPE_F16X2. */
 int nope_op_absmax_f32(const float* x, size_t n, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
 /* LinearAttention core (model_utils.py:403-416) and Attention core (:376-389) on a fused

@@ -288,6 +288,25 @@ int nope_op_group_norm_shared(int dtype, const void* x, void* y, float* partial,
     return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
 }
 
+// ---- (ABI 16) the GroupNorm tail of the per-tap ping-pong kernel's lean epilogue, as Fwd::res_tail (unet_runtime.hip) launches it
+int nope_op_conv_tail_stat_blocks(int HW, int Cout) { return conv_tail_stat_blocks(HW, Cout); }
+
+int nope_op_conv_gn_tail(int dtype, const void* src1, int C1, const void* src2, int C2, int Hs, int Ws, const void* w_packed, const float* bias,
+                         const void* resid, void* out, int Cout, int n_hyp, const float* colstats, int stat_blocks, const float* gamma,
+                         const float* beta, int G, float eps, float* ms, float* tail_stats, uint32_t* amax_slot, float* amax_out, nope_stream_t s) {
+    if ((amax_slot != nullptr) != (amax_out != nullptr)) return NOPE_ERR_ARG;
+    ConvArgs a;
+    fill_conv_args(a, src1, C1, 1, src2, C2, 1, Hs, Ws, NOPE_CONV_PLAIN, 1, w_packed, bias, resid, out, Cout, n_hyp, 0, NOPE_F32, 0);
+    a.gn_ms = ms; a.gn_gamma = gamma; a.gn_beta = beta; a.gn_G = G; a.tail_stats = tail_stats;
+    a.out_amax = amax_slot;
+    const ConvLaunch L = conv_plan(dtype, a);
+    if (L.err != NOPE_OK) return L.err;      // (before the statistics launch: a refused combination launches nothing)
+    if (const int e = launch_gn_colstats_finalize(colstats, ms, n_hyp, stat_blocks, Cout, G, Hs * Ws, eps, (hipStream_t)s)) return e;
+    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
+    if (const int e = launch_conv(L, (hipStream_t)s)) return e;
+    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
+}
+
 int nope_op_conv_class_weights(const float* w, float* out, int Cout, int Cin, nope_stream_t s) {
     return launch_pack_conv_classes(w, out, Cout, Cin, (hipStream_t)s);
 }

@@ -350,6 +350,10 @@ struct NoStamp { __device__ __forceinline__ void operator()() const {} };
 // GG: GEGLU on column pairs (ConvArgs::geglu; packed 16-bit path only -- the launcher guarantees it is the one taken).
 // LEANM = 1 (f32 storage on the 32 x 32 tiles only; ConvParams::lean: the launcher vouches for EVERY wave tile of the launch): the lean row
 // walk below instead of the generic loop -- a kernel instantiation of its own, because both forms in one kernel spill.
+// LEANM = 2: the lean row walk with the GroupNorm tail on its residual (ConvParams::gn_*; the launcher also vouches for a residual, one sample per
+// wave tile and groups of whole 4-channel chunks): each residual vector r becomes SiLU(r a + b) on its way in -- gn_apply_kernel's coefficients and
+// its three lines of arithmetic, the same bits -- so a ResnetBlock's res_conv reads the raw output of block2's conv as its residual and stores the
+// block's output.  Its own instantiation again: the launches without a tail keep their code and their registers.
 template <class T, bool PN, bool DRAIN = false, class Stamp = NoStamp, bool GG = false, int LEANM = 0>
 __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typename Tile<T>::acc_t (&acc)[Tile<T>::MT][Tile<T>::NTL],
                                               int m0, int n0, int wm, int wn, int lane, unsigned char* lds_wave, Stamp stamp = Stamp(),
@@ -544,7 +548,9 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
         }
     }
     static_assert(LEANM == 0 || (sizeof(T) == 4 && TL::TM == 32 && !GG), "the lean epilogue: f32 storage, 32 x 32 tiles");
-    if constexpr (LEANM == 1) {
+    static_assert(LEANM != 2 || !PN, "the GroupNorm tail: no fused PreNorm next to it");
+    if constexpr (LEANM >= 1) {
+        constexpr bool TAIL = LEANM == 2;
         // f32 storage on the 32 x 32 tiles (NOPE_BF16X3 / NOPE_F16X2: the modes the benchmark runs in), whole wave tile inside the tensor, rows in
         // NHWC order, one sample per wave tile under a fused PreNorm: the same arithmetic as the loop below with everything that does not
         // depend on the row hoisted and the chunk loop unrolled.  With CH = 8 chunks per panel row a lane keeps ONE column chunk (lane & 7)
@@ -557,6 +563,12 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
             const int ch = lane & 7, r0 = lane >> 3;
             float pmean = 0.f, prstd = 1.f;
             if (PN) { const int b = mw / (p.Hm * p.Wm); pmean = p.pn_ms[2 * b]; prstd = p.pn_ms[2 * b + 1]; }
+            // GroupNorm tail: the wave tile's sample (one per tile: the launcher), hence one (mean, rstd) per group and pass; `tz` is gn_apply_kernel's
+            // absent embedding -- a zero the compiler cannot see, added where that kernel adds it (-0 + 0 = +0: leaving it out could flip a sign bit)
+            const unsigned tb = TAIL ? p.d_hw.div((unsigned)mw) : 0u;
+            const float* tms = TAIL ? p.gn_ms + (size_t)tb * (unsigned)p.gn_G * 2 : nullptr;
+            const float tz = TAIL && p.gn_G <= 0 ? 1.f : 0.f;
+            f32x2_t os2 = {0.f, 0.f}, oq2 = {0.f, 0.f};            // (TAIL) sum / sum of squares of what this lane stores: ConvParams::tail_stats
             // Buffer addressing: 32-bit byte offsets (one per-lane base + a uniform pass / row-group term: one v_add per access) -- no 64-bit
             // address arithmetic in a kernel that has no register to spare.  The uniform term goes into the VECTOR offset, not the
             // instruction's scalar offset, on purpose: with an SGPR offset hipcc (ROCm 7.2) assumes a dwordx4 store has read its data before
@@ -582,6 +594,17 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
                             pb[e] = p.bias ? p.bias[nn + e] : 0.f;      // (qkv has no bias: a uniform branch around four loads)
                             pc1[e] = p.pn_c1[nn + e];
                             pc0[e] = p.pn_c0[nn + e] + pb[e];            // v = rstd * (pan - bias - mean * c1) + c0 + bias: the panel holds acc + bias
+                        }
+                    }
+                    f32x2_t gsc[2], gsh[2];                       // (TAIL) y = SiLU(r gsc + gsh) of this lane's four channels: hoisted like pc0 / pc1
+                    if constexpr (TAIL) {
+                        const int nn = nw + pass * 32 + ch * 4;   // (Cout / G) % 4 == 0: the chunk lies in one group
+                        const float* ms = tms + 2 * p.d_cpg.div((unsigned)nn);
+                        const float gmean = ms[0], grstd = ms[1];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float a = gn_scale(grstd, p.gn_gamma[nn + e]);      // (gn_apply_kernel: coeff)
+                            gsc[e >> 1][e & 1] = a; gsh[e >> 1][e & 1] = gn_shift(gmean, a, p.gn_beta[nn + e]);
                         }
                     }
                     const float bv = bvj[pass];
@@ -616,12 +639,25 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
                             if (RESID) {
                                 float rf[4];
                                 Elt<T>::unpack(rv[c], rf);
+                                if constexpr (TAIL) {
+#pragma unroll
+                                    for (int q = 0; q < 2; ++q) {
+                                        f32x2_t t = muladd(f32x2_t{rf[2 * q], rf[2 * q + 1]}, gsc[q], gsh[q]);      // (gn_apply_kernel: apply_v)
+                                        t = silu2<true>(t);
+                                        t += tz;
+                                        rf[2 * q] = t.x; rf[2 * q + 1] = t.y;
+                                    }
+                                }
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) v[e] += rf[e];
                             }
                             if (p.act) {                          // (uniform branch: the encoder's convs)
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+                            }
+                            if constexpr (TAIL) {
+#pragma unroll
+                                for (int q = 0; q < 2; ++q) { const f32x2_t t = {v[2 * q], v[2 * q + 1]}; os2 += t; oq2 += t * t; }
                             }
                             if (track_out) out_max = amax4(out_max, v[0], v[1], v[2], v[3]);
                             __builtin_amdgcn_raw_buffer_store_b128(Elt<T>::pack(v), ro, vo + (unsigned)(pass * 128) + (unsigned)(grp * LG + c) * rstep, 0, 0);
@@ -631,7 +667,19 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
                     stamp();
                 }
             };
-            if (resid) run(BoolTag<true>()); else run(BoolTag<false>());
+            if constexpr (TAIL) {
+                run(BoolTag<true>());
+                // GroupNorm(1) partials of the output: one entry per wave tile, [sample][64-row block][96-column tile] -- one writer each, the lanes folded by
+                // wave_sum's fixed butterfly (launch_gn_finalize adds the entries of a sample in index order)
+                if (p.tail_stats && nw < p.Cout) {                // (wave-uniform)
+                    const float os = wave_sum(os2.x + os2.y), oq = wave_sum(oq2.x + oq2.y);
+                    if (lane == 0) {
+                        const unsigned hw = (unsigned)(p.Hm * p.Wm), rb = ((unsigned)mw - tb * hw) >> 6;
+                        float* e = p.tail_stats + ((size_t)tb * (hw >> 6) * (unsigned)p.tail_cols + rb * (unsigned)p.tail_cols + (unsigned)nw / 96u) * 2;
+                        e[0] = os; e[1] = oq;
+                    }
+                }
+            } else if (resid) run(BoolTag<true>()); else run(BoolTag<false>());
             if (track_out) {
 #pragma unroll
                 for (int o = 32; o >= 1; o >>= 1) out_max = __builtin_fmaxf(out_max, __shfl_xor(out_max, o, 64));

@@ -71,6 +71,12 @@ struct ConvParams {
     int lean;                          // 1: f32 storage, every wave tile of the launch whole and in NHWC row order (see epilogue_wide, LEANM): the kernels' LEAN instantiations
     unsigned* out_amax;                // f32-storage launches with a wide NHWC epilogue: optional range slot (amax_publish) for max |out| of what the launch writes
     int s2_off;                        // STRIDE2: 0 = centre tap at (2 oy, 2 ox) (pad 1), 1 = at (2 oy + 1, 2 ox + 1) (NOPE_CONV_STRIDE2_PAD01: pad (0, 1, 0, 1))
+    // GroupNorm tail (ConvArgs::gn_*; the per-tap ping-pong kernel's lean epilogue only: conv_gemm_pp_kernel with PP_GN_TAIL): out = conv + SiLU(GN(resid))
+    const float* gn_ms; const float* gn_gamma; const float* gn_beta;
+    int gn_G;
+    FastDiv d_cpg;                     // / (Cout / gn_G)
+    float* tail_stats;                 // optional [nhyp][(HW / 64) * tail_cols][2]: (sum, sum of squares) of what each wave tile wrote
+    int tail_cols;                     // 96-column wave tiles across Cout
 };
 
 }  // namespace

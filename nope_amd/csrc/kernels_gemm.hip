@@ -374,6 +374,7 @@ static int stat_rows(int dt, const ConvArgs& a, const ConvSizes& z) {
     return 0;
 }
 int conv_stat_rows(int dt, const ConvArgs& a) { return stat_rows(dt_base(dt), a, conv_sizes(dt_base(dt), a)); }
+int conv_tail_stat_blocks(int HW, int Cout) { return HW / 64 * cdiv(Cout, 96); }
 
 // workgroups of a streaming launch: one per CU (NOPE_STREAM_GRID: the tests walk small grids; a multiple of 8)
 static int stream_grid() { const int g = NOPE_ENV("NOPE_STREAM_GRID", 256); return g >= 8 && g % 8 == 0 ? g : 256; }
@@ -493,6 +494,10 @@ ConvLaunch conv_plan(int dt, const ConvArgs& a0) {
     if (a.pn_ms && (!a.pn_c0 || !a.pn_c1 || a.mode != NOPE_CONV_PLAIN || a.ntaps != 1 || a.colstats)) return fail(NOPE_ERR_ARG);
     if (a.colstats && (!wide_out || phased || a.resid || a.act || a.stat_rows != stat_rows(dt, a, z))) return fail(NOPE_ERR_ARG);      // (act: the epilogues take the
                                                                                                       // statistics before an activation, the split-K reduce after it -- nobody needs the pair)
+    // GroupNorm tail on the residual (ConvArgs::gn_*): complete arguments here; that the launch is one whose epilogue has the tail, at the end
+    // (gn_G >= 1 is also what makes epilogue_wide's `tz` -- conv_gemm_common.h: a zero formed from `gn_G <= 0` -- a zero)
+    if ((a.gn_ms || a.tail_stats) && (!a.gn_ms || !a.gn_gamma || !a.gn_beta || !a.resid || a.gn_G < 1 || a.Cout % a.gn_G || a.act || a.pn_ms || a.colstats ||
+                                      ((uintptr_t)a.gn_ms & 7))) return fail(NOPE_ERR_ARG);
     // ---- kernel, tile, precision
     const KernelChoice pick = choose_kernel(dt, a, z);
     const bool dma = pick.dma;
@@ -646,6 +651,18 @@ ConvLaunch conv_plan(int dt, const ConvArgs& a0) {
     p.lean = (dt == NOPE_BF16X3 && dma && pick.small < 0 && p.wide_out && !p.posmajor && !phased && p.splits == 1 && !a.geglu && M % bm == 0 && a.Cout % 32 == 0 &&
               (!a.pn_ms || ((long long)p.Hm * p.Wm) % 64 == 0) && (unsigned long long)M * a.Cout * 4ull < 0xffffffffull && NOPE_ENV("NOPE_EPILOGUE_LEAN", 1) != 0) ? 1 : 0;
     L.grid = dim3(gx, phased ? 4u : 1u, (unsigned)p.splits);
+    if (a.gn_ms) {
+        // the tail lives in ONE epilogue: the lean row walk of the per-tap ping-pong kernel (conv_gemm_pp_kernel with PP_GN_TAIL), a wave tile inside one sample (one
+        // (mean, rstd) per group and pass), a lane's 4-channel chunk inside one group.  Any other launch is refused, never run without the tail.
+        const long long HW = (long long)p.Hm * p.Wm;
+        const int cpg = a.Cout / a.gn_G;
+        if (!(pick.pp && !pick.halo && !stream && p.lean && a.mode == NOPE_CONV_PLAIN && HW % 64 == 0 && cpg % 4 == 0 && variant == 0 && !NOPE_ENV_SET("NOPE_PP_VARIANT")))
+            return fail(NOPE_ERR_UNSUPPORTED);
+        if (a.tail_stats && conv_tail_stat_blocks((int)HW, a.Cout) > 64) return fail(NOPE_ERR_UNSUPPORTED);      // (the runtimes' partial buffers hold 64 entries per hypothesis)
+        p.gn_ms = a.gn_ms; p.gn_gamma = a.gn_gamma; p.gn_beta = a.gn_beta; p.gn_G = a.gn_G;
+        p.d_cpg = make_fastdiv((unsigned)cpg);
+        p.tail_stats = a.tail_stats; p.tail_cols = cdiv(a.Cout, 96);
+    }
     L.kind = pick.small >= 0 ? NOPE_CONV_KERNEL_SMALL : stream ? NOPE_CONV_KERNEL_STREAM : pick.halo ? NOPE_CONV_KERNEL_HALO256 : pick.pp ? NOPE_CONV_KERNEL_PP256
              : dma ? NOPE_CONV_KERNEL_DMA128 : NOPE_CONV_KERNEL_GENERIC;
     if ((L.kind == NOPE_CONV_KERNEL_HALO256 || L.kind == NOPE_CONV_KERNEL_PP256) && NOPE_ENV_SET("NOPE_PP_VARIANT")) p.variant = NOPE_ENV("NOPE_PP_VARIANT", 0);      // tuning ablations of the ping-pong kernel
@@ -681,7 +698,7 @@ static void trace_conv(const ConvLaunch& L) {
                                                  p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z, p.xcd_map, p.xcd_gn);
     else fprintf(stderr, "conv %s mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u posmajor %d persist %d xcd %d/%d%s%s\n",
                  names[L.kind], p.mode, p.ntaps, Cin, p.Cout, (long long)p.M, p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z,
-                 p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, p.geglu ? " geglu" : L.x2 ? " x2" : "", p.lean ? " lean" : "");
+                 p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, p.geglu ? " geglu" : L.x2 ? " x2" : "", p.gn_ms ? " lean gn-tail" : p.lean ? " lean" : "");
 }
 
 #define LAUNCH_GENERIC(T) \

@@ -53,8 +53,14 @@ struct KPos { int tap, kc; };
 
 // TUNE: the instantiation that honours the NOPE_PP_VARIANT ablations (run-time tests inside the K loop); production launches (variant 0) take the
 // one without them.
-template <class T, int MODE, bool PN, bool TUNE = false, bool LEAN = false>
+// MODE_ = the conv mode, + PP_GN_TAIL: the lean epilogue with the GroupNorm tail on its residual (epilogue_wide, LEANM = 2; ConvParams::gn_*).  The flag
+// rides on the mode instead of being one more template parameter, or a kernel of its own around a shared body, on purpose: either of those renames or
+// re-allocates the existing instantiations (a shared __forceinline__ body cost every TUNE instantiation a register), this leaves them byte for byte.
+constexpr int PP_GN_TAIL = 256;
+template <class T, int MODE_, bool PN, bool TUNE = false, bool LEAN = false>
 __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv_gemm_pp_kernel(ConvParams p) {
+    constexpr int MODE = MODE_ & (PP_GN_TAIL - 1);
+    constexpr bool TAIL = (MODE_ & PP_GN_TAIL) != 0;
     typedef Tile<T> TL;
     constexpr int VEC = Elt<T>::VEC;
     constexpr unsigned ES = (unsigned)sizeof(T);
@@ -412,7 +418,7 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv_gemm_pp_kernel(ConvPara
         return;
     }
     if constexpr (X2 && NOPE_X2_KERNEL_AMAX) x2_publish_amax(p, x2_amax, lane);
-    epilogue_wide<T, PN, false, NoStamp, false, LEAN ? 1 : 0>(p, acc, m0, n0, wm, wn, lane, lds + wave * Ep<T>::WAVE_BYTES, NoStamp(), x2_out);
+    epilogue_wide<T, PN, false, NoStamp, false, TAIL ? 2 : LEAN ? 1 : 0>(p, acc, m0, n0, wm, wn, lane, lds + wave * Ep<T>::WAVE_BYTES, NoStamp(), x2_out);
 }
 
 // ---- 3x3 convolutions: the A operand stays in LDS across the 9 taps ------------------------------------------------
@@ -1143,6 +1149,7 @@ template <class T, bool TUNE>
 void launch_pp_tt(const ConvParams& p, dim3 grid, hipStream_t s) {
     const dim3 block(PP_WAVES * 64);
     if constexpr (sizeof(T) == 4 && Tile<T>::TM == 32 && !TUNE) {
+        if (p.gn_ms) { hipLaunchKernelGGL((conv_gemm_pp_kernel<T, NOPE_CONV_PLAIN + PP_GN_TAIL, false, false, true>), grid, block, 0, s, p); return; }      // (conv_plan: lean, plain, no PreNorm, variant 0)
         if (p.lean && !p.pn_ms && p.mode == NOPE_CONV_PLAIN) { hipLaunchKernelGGL((conv_gemm_pp_kernel<T, NOPE_CONV_PLAIN, false, false, true>), grid, block, 0, s, p); return; }
         if (p.lean && p.mode == NOPE_CONV_DOWN2) { hipLaunchKernelGGL((conv_gemm_pp_kernel<T, NOPE_CONV_DOWN2, false, false, true>), grid, block, 0, s, p); return; }
     }

@@ -144,17 +144,13 @@ __device__ __forceinline__ void group_sums(const float* ch_s, const float* ch_q,
     }
 }
 
-// Fold [HW/64 row blocks][C][2] column statistics (written by the conv epilogue) of one hypothesis into
-// [G][2] group sums.  Fixed summation order -> deterministic.
-__global__ __launch_bounds__(NT) void gn_fold_kernel(const float* __restrict__ colstats, float* __restrict__ partial, int nb, int C, int G) {
-    __shared__ float ch_s[2048];
-    __shared__ float ch_q[2048];
-    const int hyp = blockIdx.x, tid = threadIdx.x;
-    const float* base = colstats + (size_t)hyp * nb * C * 2;
+// Per-channel sums of [nb row blocks][C][2] column statistics (written by the conv epilogue) of one sample into LDS: 8 independent loads in
+// flight, then the adds in row-block order.  One copy for gn_fold_kernel, gn_colstats_finalize_kernel and gn_apply_kernel's FOLD: same order, same bits.
+__device__ __forceinline__ void fold_columns(const float* base, int nb, int C, int tid, float* ch_s, float* ch_q) {
     for (int c = tid; c < C; c += NT) {
         float s = 0.f, q = 0.f;
         int b = 0;
-        for (; b + 8 <= nb; b += 8) {          // 8 independent loads in flight, then the adds in row-block order
+        for (; b + 8 <= nb; b += 8) {
             f32x2 v[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x2*>(base + ((size_t)(b + u) * C + c) * 2);
@@ -167,6 +163,16 @@ __global__ __launch_bounds__(NT) void gn_fold_kernel(const float* __restrict__ c
         }
         ch_s[c] = s; ch_q[c] = q;
     }
+}
+
+// Fold [HW/64 row blocks][C][2] column statistics (written by the conv epilogue) of one hypothesis into
+// [G][2] group sums.  Fixed summation order -> deterministic.
+__global__ __launch_bounds__(NT) void gn_fold_kernel(const float* __restrict__ colstats, float* __restrict__ partial, int nb, int C, int G) {
+    __shared__ float ch_s[2048];
+    __shared__ float ch_q[2048];
+    const int hyp = blockIdx.x, tid = threadIdx.x;
+    const float* base = colstats + (size_t)hyp * nb * C * 2;
+    fold_columns(base, nb, C, tid, ch_s, ch_q);
     __syncthreads();
     group_sums(ch_s, ch_q, C / G, G, tid, [&](int g, float S, float Q) {
         partial[((size_t)hyp * G + g) * 2] = S;
@@ -174,20 +180,24 @@ __global__ __launch_bounds__(NT) void gn_fold_kernel(const float* __restrict__ c
     });
 }
 
-typedef f32x2_t f32x2;
-
-// SiLU of two values in the 16-bit storage modes: v_pk_mul, 2 x v_exp_f32, v_pk_add, 2 x v_rcp_f32, v_pk_mul (the transcendentals
-// are quarter rate: 8 of the ~14 issue slots an element costs).  The f32 mode keeps expf and a true division (parity bar 1e-6).
-template <bool FAST> __device__ __forceinline__ f32x2 silu2(f32x2 t) {
-    if (FAST) {
-        const f32x2 a = t * -1.4426950408889634f;
-        f32x2 e = {__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
-        e = e + 1.0f;
-        const f32x2 r = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-        return t * r;
-    }
-    return f32x2{silu_f<false>(t.x), silu_f<false>(t.y)};
+// ... into per-group (mean, rstd) [hypothesis][G][2] instead: for a consumer that cannot fold per workgroup as gn_apply_kernel's FOLD does -- the
+// GroupNorm tail of a conv epilogue (epilogue_wide, LEANM = 2).  gn_fold_kernel's order and gn_apply_kernel's mean / rstd lines: the same bits.
+__global__ __launch_bounds__(NT) void gn_colstats_finalize_kernel(const float* __restrict__ colstats, float* __restrict__ ms, int nb, int C, int G, int HW, float eps) {
+    __shared__ float ch_s[2048];
+    __shared__ float ch_q[2048];
+    const int hyp = blockIdx.x, tid = threadIdx.x;
+    const int cpg = C / G;
+    fold_columns(colstats + (size_t)hyp * nb * C * 2, nb, C, tid, ch_s, ch_q);
+    __syncthreads();
+    group_sums(ch_s, ch_q, cpg, G, tid, [&](int g, float S, float Q) {
+        float mean, rstd;
+        gn_mean_rstd(S, Q, (float)cpg * (float)HW, eps, mean, rstd);
+        ms[((size_t)hyp * G + g) * 2] = mean;
+        ms[((size_t)hyp * G + g) * 2 + 1] = rstd;
+    });
 }
+
+typedef f32x2_t f32x2;
 
 // ACT / RES are template parameters and the arithmetic is written on float pairs: the body is VALU-bound before it is HBM-bound
 // (per 16-bit element: unpack, fma, SiLU = 2 quarter-rate transcendentals + 3, adds, clamp, pack), so runtime `if (act)` /
@@ -224,31 +234,9 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
         __shared__ float ch_s[2048];
         __shared__ float ch_q[2048];
         const float* base = partial + (size_t)xs * nchunk * C * 2;
-        for (int c = tid; c < C; c += NT) {
-            float s = 0.f, q = 0.f;
-            int b = 0;
-            for (; b + 8 <= nchunk; b += 8) {
-                f32x2 v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x2*>(base + ((size_t)(b + u) * C + c) * 2);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { s += v[u][0]; q += v[u][1]; }
-            }
-            for (; b < nchunk; ++b) {
-                const f32x2 v = *reinterpret_cast<const f32x2*>(base + ((size_t)b * C + c) * 2);
-                s += v[0]; q += v[1];
-            }
-            ch_s[c] = s; ch_q[c] = q;
-        }
+        fold_columns(base, nchunk, C, tid, ch_s, ch_q);
         __syncthreads();
-        group_sums(ch_s, ch_q, cpg, G, tid, [&](int g, float S, float Q) {
-            const float cnt = (float)cpg * (float)HW;
-            const float mean = S / cnt;
-            float var = Q / cnt - mean * mean;
-            var = var > 0.f ? var : 0.f;
-            s_mean[g] = mean;
-            s_rstd[g] = 1.0f / sqrtf(var + eps);
-        });
+        group_sums(ch_s, ch_q, cpg, G, tid, [&](int g, float S, float Q) { gn_mean_rstd(S, Q, (float)cpg * (float)HW, eps, s_mean[g], s_rstd[g]); });
     } else
     for (int g = tid; g < G; g += NT) {
         float S = 0.f, Q = 0.f;
@@ -256,12 +244,7 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
             const float* pp = partial + ((size_t)xs * nchunk + k) * G * 2 + g * 2;
             S += pp[0]; Q += pp[1];
         }
-        const float cnt = (float)cpg * (float)HW;
-        const float mean = S / cnt;
-        float var = Q / cnt - mean * mean;
-        var = var > 0.f ? var : 0.f;
-        s_mean[g] = mean;
-        s_rstd[g] = 1.0f / sqrtf(var + eps);
+        gn_mean_rstd(S, Q, (float)cpg * (float)HW, eps, s_mean[g], s_rstd[g]);
     }
     __syncthreads();
     // Pure streaming body: a thread owns ONE 16-byte channel vector for its whole pixel walk, so
@@ -287,8 +270,8 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
         f32x2 sc[V2], sh[V2], ev[V2];
         auto coeff = [&](int e, int g) {
             const int c = cv * VEC + e;
-            float a = s_rstd[g] * gamma[c];
-            float b = beta[c] - s_mean[g] * a;
+            float a = gn_scale(s_rstd[g], gamma[c]);
+            float b = gn_shift(s_mean[g], a, beta[c]);
             if (FILM) {                                // norm(x) * (1 + scale) + shift: still one fma per element
                 const float f = 1.0f + fb[c];
                 a = a * f;
@@ -311,7 +294,7 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const T* __restrict__ x, T
             if (RES) Elt<T>::unpack(xr, r);
 #pragma unroll
             for (int q = 0; q < V2; ++q) {
-                f32x2 t = f32x2{v[2 * q], v[2 * q + 1]} * sc[q] + sh[q];
+                f32x2 t = muladd(f32x2{v[2 * q], v[2 * q + 1]}, sc[q], sh[q]);      // (the conv epilogue's GroupNorm tail repeats these three lines: same bits)
                 if (ACT) t = silu2<FAST>(t);
                 t += ev[q];
                 if (RES) t += f32x2{r[2 * q], r[2 * q + 1]};
@@ -455,6 +438,13 @@ int launch_gn_stats_shared(int dt, const GnApplyArgs& a, float* partial, int nch
     if (form == 1) { if (fast) NOPE_GN_STATS_SH(true, 1); else NOPE_GN_STATS_SH(false, 1); }
     else           { if (fast) NOPE_GN_STATS_SH(true, 2); else NOPE_GN_STATS_SH(false, 2); }
 #undef NOPE_GN_STATS_SH
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
+int launch_gn_colstats_finalize(const float* colstats, float* ms, int nhyp, int blocks, int C, int G, int HW, float eps, hipStream_t s) {
+    if (!colstats || !ms || nhyp <= 0 || blocks < 1 || HW < 1 || G < 1 || C % G || C > 2048 || G > 64) return NOPE_ERR_ARG;
+    hipLaunchKernelGGL(gn_colstats_finalize_kernel, dim3((unsigned)nhyp), dim3(NT), 0, s, colstats, ms, blocks, C, G, HW, eps);
     NOPE_CHECK_LAUNCH();
     return NOPE_OK;
 }

@@ -269,6 +269,40 @@ template <bool FAST> __device__ __forceinline__ float silu_f(float x) {
     return x / (1.0f + expf(-x));
 }
 
+// SiLU of two values in the 16-bit storage modes: v_pk_mul, 2 x v_exp_f32, v_pk_add, 2 x v_rcp_f32, v_pk_mul (the transcendentals
+// are quarter rate: 8 of the ~14 issue slots an element costs).  The f32 mode keeps expf and a true division (parity bar 1e-6).
+template <bool FAST> __device__ __forceinline__ f32x2_t silu2(f32x2_t t) {
+    if (FAST) {
+        const f32x2_t a = t * -1.4426950408889634f;
+        f32x2_t e = {__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)};
+        e = e + 1.0f;
+        const f32x2_t r = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
+        return t * r;
+    }
+    return f32x2_t{silu_f<false>(t.x), silu_f<false>(t.y)};
+}
+
+// a * b + c where two kernels must agree on the rounding (gn_apply_kernel and the GroupNorm tail of the conv epilogue, epilogue_wide LEANM = 2):
+// the device compiler contracts the expression to one fma wherever it meets it, and here that is written down instead of left to it.  The host build
+// of tests/hipemu has no fused multiply-add: it rounds twice, in every kernel alike, as it always did.
+#ifdef HIPEMU
+__device__ __forceinline__ float muladd(float a, float b, float c) { return a * b + c; }
+__device__ __forceinline__ f32x2_t muladd(f32x2_t a, f32x2_t b, f32x2_t c) { return a * b + c; }
+#else
+__device__ __forceinline__ float muladd(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ f32x2_t muladd(f32x2_t a, f32x2_t b, f32x2_t c) { return __builtin_elementwise_fma(a, b, c); }
+#endif
+// GroupNorm as one multiply-add per element, y = x a + b: a = rstd gamma, b = beta - mean a  (values, not references: out-parameters moved gn_apply_kernel's registers)
+__device__ __forceinline__ float gn_scale(float rstd, float gamma) { return rstd * gamma; }
+__device__ __forceinline__ float gn_shift(float mean, float a, float beta) { return muladd(-mean, a, beta); }
+// (mean, rstd) of `cnt` values from their sum and sum of squares
+__device__ __forceinline__ void gn_mean_rstd(float S, float Q, float cnt, float eps, float& mean, float& rstd) {
+    mean = S / cnt;
+    float var = Q / cnt - mean * mean;
+    var = var > 0.f ? var : 0.f;
+    rstd = 1.0f / sqrtf(var + eps);
+}
+
 // Keeps a value (and the loads that produced it) alive in a tuning build that skips its consumer -- without this the
 // compiler deletes the loads too and the ablation measures less than it claims (cdna_hip_programming.md rule 17).
 #ifndef NOPE_KEEP_VGPR
@@ -370,6 +404,17 @@ struct ConvArgs {
     // (conv_geglu_fusable); same operands (rounded to the storage type) and same formula as geglu_kernel: bit-identical to conv + geglu.
     int geglu = 0;
     int s2_off = 0;              // STRIDE2 3x3: centre tap at source pixel (2 oy + s2_off, 2 ox + s2_off) -- set by launch_conv for NOPE_CONV_STRIDE2_PAD01
+    // GroupNorm tail on the residual (the end of a ResnetBlock with a res_conv in one launch, unet_runtime.hip):
+    //   out[m,n] = conv[m,n] + SiLU(resid[m,n] * a + b),  a = rstd[s,g] gamma[n],  b = beta[n] - mean[s,g] a,  s = sample of row m, g = group of column n
+    // with gn_apply_kernel's arithmetic (fast SiLU): bit-identical to the conv followed by launch_gn_apply with the conv's output as its residual.  resid
+    // may be `out` itself (every element is read and written by the same lane).  Only a launch that conv_plan puts on the per-tap ping-pong kernel
+    // with the lean epilogue takes it, with whole 64-row blocks per sample and (Cout / gn_G) % 4 == 0; NOPE_ERR_UNSUPPORTED otherwise (conv_plan).
+    const float* gn_ms = nullptr;    // [nhyp][gn_G][2] (mean, rstd) of resid (launch_gn_colstats_finalize)
+    const float* gn_gamma = nullptr; // [Cout]
+    const float* gn_beta = nullptr;  // [Cout]
+    int gn_G = 0;
+    float* tail_stats = nullptr;     // optional, with gn_ms: [nhyp][conv_tail_stat_blocks()][2] (sum, sum of squares) of the values written, one writer per
+                                     // entry, fixed order: the GroupNorm(1) partials of the output (launch_gn_finalize), as GnApplyArgs::out_stats
 };
 int launch_conv(int dt, const ConvArgs& a, hipStream_t s);
 bool conv_geglu_fusable(int dt, const ConvArgs& a);   // would launch_conv take this conv with geglu = 1?
@@ -378,6 +423,7 @@ bool conv_is_posmajor(int dt, const ConvArgs& a);
 int conv_kernel_kind(int dt, const ConvArgs& a);      // NOPE_CONV_KERNEL_* launch_conv would pick
 bool conv_takes_x2(int dt, const ConvArgs& a);        // would launch_conv run this NOPE_BF16X3 launch on the f16 + MX-fp8 tile (a.w_x2 set)?
 int conv_stat_rows(int dt, const ConvArgs& a);        // rows per block of the fused column statistics this conv can emit (0: none)
+int conv_tail_stat_blocks(int HW, int Cout);          // entries per hypothesis of ConvArgs::tail_stats: one per 64-row x 96-column wave tile
 double conv_executed_flops(int dt, const ConvArgs& a);
 
 int launch_gn_stats(int dt, const void* x, float* partial, int nhyp, int HW, int C, int G, int nchunk, hipStream_t s);
@@ -431,6 +477,8 @@ int launch_gn_finalize(const float* partial, float* ms, int nhyp, int nchunk, fl
 int gn_stats_chunks(int HW, int C, int dt);
 // fold the conv epilogue's per-row-block column statistics [nhyp][blocks][C][2] into per-(hypothesis, group) partials (nchunk = 1)
 int launch_gn_fold(const float* colstats, float* partial, int nhyp, int blocks, int C, int G, hipStream_t s);
+// ... into per-(hypothesis, group) (mean, rstd) [nhyp][G][2] over HW * C / G values each: gn_fold's order, gn_apply's mean / rstd lines (ConvArgs::gn_ms)
+int launch_gn_colstats_finalize(const float* colstats, float* ms, int nhyp, int blocks, int C, int G, int HW, float eps, hipStream_t s);
 
 int launch_linattn(int dt, const void* qkv, void* out, int nhyp, int HW, int heads, int dim_head, hipStream_t s);
 int launch_attn(int dt, const void* qkv, void* out, int nhyp, int HW, int heads, int dim_head, hipStream_t s);

@@ -144,6 +144,9 @@ struct ConvOpts {
     int out_nchw = 0, out_dt = NOPE_F32;    // the network's output conv: NCHW of type out_dt
     bool track_out = false;                 // the output goes straight into f16x2 convs: its epilogue records max |out| when it is one that can
                                             // (the wide NHWC epilogue); otherwise a later f16x2 consumer of `out` takes an absmax pass over it
+    // GroupNorm tail on the residual (ConvArgs::gn_*): out = conv + SiLU(GN(resid)), the norm's affine, its groups, (mean, rstd) [nhyp][G][2] of resid
+    // and, optionally, where the GroupNorm(1) partials of the output go (ConvArgs::tail_stats)
+    const NormW* gn = nullptr; int gn_G = 0; const float* gn_ms = nullptr; float* tail_stats = nullptr;
 };
 inline ConvOpts with_resid(const void* resid) { ConvOpts o; o.resid = resid; return o; }
 inline ConvOpts to_nchw(int out_dt) { ConvOpts o; o.out_nchw = 1; o.out_dt = out_dt; return o; }
@@ -194,6 +197,7 @@ template <class N> struct FwdCore {
         ca.mode = c.mode; ca.ntaps = c.ntaps; ca.w = c.w; ca.bias = c.bias; ca.resid = o.resid;
         ca.out = out; ca.Cout = c.Cout; ca.nhyp = nhyp; ca.out_nchw = o.out_nchw; ca.out_dt = o.out_dt;
         if (c.w_x2 && c.x2_id >= 0 && !net->x2r.off) { ca.w_x2 = c.w_x2; ca.x2_t_zero = net->x2r.t_zero(c.x2_id) ? 1 : 0; }
+        if (o.gn) { ca.gn_ms = o.gn_ms; ca.gn_gamma = o.gn->gamma; ca.gn_beta = o.gn->beta; ca.gn_G = o.gn_G; ca.tail_stats = o.tail_stats; }
         return true;
     }
     // Second half: the plan of the filled ConvArgs (made once: the tracking, a profile and launch_conv read the same decisions), tracked -- a

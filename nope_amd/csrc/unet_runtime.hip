@@ -87,7 +87,7 @@ struct nope_unet : rt::Net {      // (dt / sdt / x2 / x2r / allocs: rt::Net, run
     mutable std::vector<UGraph> graphs;
     mutable bool graphs_ok = true;           // cleared when capture is unavailable: direct launches from then on
     mutable std::mutex graph_mu;
-    mutable int graph_split = -1;            // NOPE_SHARED_SPLIT the cached graphs were captured under
+    mutable int graph_split = -1;            // NOPE_SHARED_SPLIT | NOPE_RES_TAIL << 2 the cached graphs were captured under
     mutable int graph_replays = 0;           // forwards served by a graph replay since create (tests assert the path really ran)
     long long graph_max = 0;                 // largest n_hyp * H * W that replays a graph; 0 = off
 };
@@ -189,6 +189,7 @@ struct Fwd : rt::FwdCore<nope_unet> {
     float* pn_partial = nullptr;   // (sum, sum sq) partials of the tensor that feeds the next attention block
     float* pn_ms = nullptr;        // its per-hypothesis (mean, rstd)
     const float* emb_all = nullptr;
+    int pn_blocks = 0;             // entries per hypothesis of pn_partial as its last producer laid them out (gn_apply_blocks, or conv_tail_stat_blocks)
     int split = 0;                 // NOPE_SHARED_SPLIT of this forward: bit 0 = downs[0][0].block2, bit 1 = final_res_block.block1
 
     // run `fn` as a forward over n samples (the per-reference launches: profiled, traced and range-tracked like every other)
@@ -234,9 +235,9 @@ struct Fwd : rt::FwdCore<nope_unet> {
         nope_unet::Ev ev;
         hipEventCreate(&ev.a); hipEventCreate(&ev.b);
         ev.flops = L.flops;   // executed MACs (UP2P: 4 taps per output pixel; padding taps of small maps skipped)
-        // algorithmic HBM bytes: every input, weight and output element exactly once
+        // algorithmic HBM bytes: every input, weight and output element exactly once (+ the residual a GroupNorm tail normalises: a pass of its own before)
         ev.bytes = ((double)(nhyp / a.rep) * a.H * a.W * a.C + (b ? (double)(nhyp / b->rep) * a.H * a.W * b->C : 0.0) +
-                    (double)c.Cout * c.ntaps * c.Cin * (c.mode == NOPE_CONV_UP2P ? 4 : 1) + (double)nhyp * Ho * Wo * c.Cout) * (double)es;
+                    (double)c.Cout * c.ntaps * c.Cin * (c.mode == NOPE_CONV_UP2P ? 4 : 1) + (double)nhyp * Ho * Wo * c.Cout * (o.gn ? 2 : 1)) * (double)es;
         ev.info = nope_conv_launch_info{0.0, ev.flops, ev.bytes, L.kind, c.mode, c.ntaps, c.Cin, c.Cout, a.H, a.W, nhyp,
                                         net->dt != NOPE_BF16X3 ? 1 : L.x2 ? 2 : 3, L.posmajor ? 1 : 0};
         hipEventRecord(ev.a, s);
@@ -280,6 +281,30 @@ struct Fwd : rt::FwdCore<nope_unet> {
         return gn_apply(ga);
     }
 
+    // The end of a ResnetBlock with a res_conv in ONE pass: res_conv reads the raw output of block2's conv (`out`) as its residual, normalises and
+    // activates it on the way in (ConvArgs::gn_*: gn_apply's arithmetic, the same bits) and stores the block's output over it -- res_conv's own output
+    // is never written and the apply pass never runs: 4 of 6 activation tensors moved.  Taken where conv_plan puts res_conv on the per-tap ping-pong
+    // kernel with the lean epilogue (the only one that has the tail), f32 storage in a split-precision mode (the fast SiLU), whole 64-row blocks per
+    // sample, groups of whole 4-channel chunks.  NOPE_RES_TAIL: bit 0 = blocks not followed by attention (bit-identical to the three passes), bit 1 =
+    // blocks followed by attention (the GroupNorm(1) partials of the output come from the epilogue's wave tiles: another summation order, results
+    // move at rounding level); 0 = the three passes everywhere.  Default 1: bit 1 measures another 0.2 ms per 512-template step, but a forward would
+    // then depend on NOPE_EPILOGUE_LEAN in its last bits, which tests/test_conv_stream.py forbids.  False: not taken, nothing launched.
+    bool res_tail(const Res& R, const Act& a, const Act* b, void* out, const Stats& st, bool next_is_attention) {
+        const int HW = a.H * a.W, G = net->cfg.groups, C = R.res.Cout;
+        if (!(NOPE_ENV("NOPE_RES_TAIL", 1) & (next_is_attention ? 2 : 1))) return false;
+        if (net->sdt != NOPE_F32 || net->dt == NOPE_F32 || !st.cs || HW < 64 || HW % 64 || G < 1 || C % G || (C / G) % 4) return false;
+        ConvOpts o;
+        o.resid = out; o.track_out = true;
+        o.gn = &R.n2; o.gn_G = G; o.gn_ms = gn_partial;      // (gn_partial: free between block1's GroupNorm and the next one; [nhyp][G][2] fits its [nhyp][16][G][2])
+        if (next_is_attention) o.tail_stats = pn_partial;
+        ConvArgs ca;
+        if (err != NOPE_OK || !conv_args(ca, R.res, a, b, out, a.H, a.W, o) || conv_plan(net->dt, ca).err != NOPE_OK) return false;
+        if (live()) chk(launch_gn_colstats_finalize(st.cs, gn_partial, nhyp, st.blocks, C, G, HW, 1e-5f, s));
+        conv(R.res, a, b, out, a.H, a.W, o);
+        if (next_is_attention) pn_blocks = conv_tail_stat_blocks(HW, C);
+        return true;
+    }
+
     // ResnetBlock, model_utils.py:271-279.  `a` may be shared by a.rep hypotheses (rep > 1 only for the very first block, where b == nullptr).
     // `next_is_attention`: also emit the GroupNorm(1) partials of the block's output into pn_partial.
     // tail: fused into the block's last pass where gn() can; returns whether it was (then `out` holds the un-normalised conv output and
@@ -292,6 +317,7 @@ struct Fwd : rt::FwdCore<nope_unet> {
         const bool f32_acts = net->sdt == NOPE_F32 && a.H >= 2 && a.W >= 2;      // (S and E are f32; a 1-pixel-wide map has no nine border classes)
         GnOpts g2;                     // the block's last GroupNorm: + the block's input (or res_conv of it)
         g2.resid = a.p; g2.resid_rep = a.rep; g2.out_stats = next_is_attention ? pn_partial : nullptr;
+        if (next_is_attention) pn_blocks = gn_apply_blocks(HW, R.n2.C, net->sdt, nhyp);
         if (a.rep > 1 && !b && (split & 1) && !R.has_res && R.c2_cls && use_emb && f32_acts) {
             // downs[0][0] with NOPE_SHARED_SPLIT bit 0: block2 convolves u + e_n 1, u = SiLU(GN(block1(x0))) per reference and e_n this block's
             // embedding row, constant over the map.  By linearity conv2(u + e_n 1)[p] = S[p] + E[n][cls(p)]: S = conv2(u) + bias once per
@@ -349,7 +375,8 @@ struct Fwd : rt::FwdCore<nope_unet> {
         }
         conv(R.c2, Act{t1, R.c1.Cout, a.H, a.W}, nullptr, out, a.H, a.W, with_stats(g2.stats));
         if (R.has_res) {
-            void* t3 = alloc_act(M * R.res.Cout);
+            void* t3 = alloc_act(M * R.res.Cout);      // (allocated under the one-pass form too: the workspace of a shape does not depend on NOPE_RES_TAIL)
+            if (!tail.proj && res_tail(R, a, b, out, g2.stats, next_is_attention)) { ar.off = mark; return false; }
             conv(R.res, a, b, t3, a.H, a.W);
             g2.resid = t3; g2.resid_rep = 1;
         } else if (b) { chk(NOPE_ERR_ARG); }
@@ -364,7 +391,7 @@ struct Fwd : rt::FwdCore<nope_unet> {
     void qkv_prenorm(const PackedConv& qkvw, const float* c0, const float* c1, const Act& x, void* qkv) {
         if (!live()) return;
         const int HW = x.H * x.W;
-        chk(launch_gn_finalize(pn_partial, pn_ms, nhyp, gn_apply_blocks(HW, x.C, net->sdt, nhyp), (float)HW * (float)x.C, 1e-5f, s));
+        chk(launch_gn_finalize(pn_partial, pn_ms, nhyp, pn_blocks, (float)HW * (float)x.C, 1e-5f, s));
         ConvOpts o; o.c0 = c0; o.c1 = c1;
         conv(qkvw, x, nullptr, qkv, x.H, x.W, o);
     }
@@ -770,10 +797,11 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
     q.n_src = n_src; q.x_rep = x_rep; q.n_hyp = n_hyp; q.H = H; q.W = W; q.split = split;
     if (!want_graph) return run_forward(net, q, base, avail, s);
     std::lock_guard<std::mutex> lock(net->graph_mu);
-    if (net->graph_split != split) {           // the launch plan changes: cached graphs are stale (as in nope_unet_x2_enable)
+    const int plan_key = split | (NOPE_ENV("NOPE_RES_TAIL", 1) & 3) << 2;      // the switches read per forward that change the launch sequence
+    if (net->graph_split != plan_key) {        // the launch plan changes: cached graphs are stale (as in nope_unet_x2_enable)
         for (const UGraph& g : net->graphs) hipGraphExecDestroy(g.exec);
         net->graphs.clear();
-        net->graph_split = split;
+        net->graph_split = plan_key;
     }
 
     float* x_s = (float*)base;

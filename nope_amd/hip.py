@@ -15,7 +15,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 15                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 16                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -116,6 +116,8 @@ _PROTOS = {
     "nope_op_conv_ex": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp,
                              _vp, _vp, C.POINTER(_i), _vp]),
     "nope_op_gn_apply_blocks": (_i, [_i, _i, _i, _i]),
+    "nope_op_conv_tail_stat_blocks": (_i, [_i, _i]),
+    "nope_op_conv_gn_tail": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "nope_op_group_norm_ex": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, C.c_float, _i,
                                    _vp, _vp, _vp]),
     "nope_op_gn_finalize": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp]),
@@ -1219,6 +1221,41 @@ def op_conv_ex(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torc
     if want_amax:
         return s.out, float(amax.item()), bool(rec.value)
     return s.out
+
+
+def op_conv_gn_tail(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], resid: torch.Tensor, colstats: torch.Tensor,
+                    gamma: torch.Tensor, beta: torch.Tensor, groups: int, src2: Optional[torch.Tensor] = None, eps: float = 1e-5,
+                    in_place: bool = False, tail_stats: bool = False, want_amax: bool = False, x2_shift: int = 0):
+    """conv1x1(src1 [cat src2]) + bias + SiLU(GroupNorm(groups)(resid)) in the conv's epilogue (nope_op_conv_gn_tail, include/nope_hip.h);
+    colstats [n][blocks][Cout][2]: resid's column statistics over blocks of 64 rows.  in_place: resid (a copy of it) is also the output buffer,
+    as the U-Net runtime launches it.  Returns out, or (out, extras) with extras["tail_stats"] [n][op_conv_tail_stat_blocks][2] / extras["amax"]."""
+    s = _conv_setup(dt, src1, w, bias, src2, CONV_PLAIN, 1, None, False, F32, False)
+    assert s.ntaps == 1 and tuple(resid.shape) == tuple(s.out.shape) and resid.dtype == torch.float32 and resid.is_contiguous()
+    assert colstats.dtype == torch.float32 and colstats.is_contiguous() and tuple(colstats.shape[::3]) == (s.n_hyp, 2) and colstats.shape[2] == s.cout
+    if x2_shift:
+        assert dt == F16X2
+        s.pw.view(torch.int32)[-1] = int(x2_shift)
+    if in_place:
+        s.out.copy_(resid)
+        resid = s.out
+    l = lib()
+    g, b = _f32c(gamma), _f32c(beta)
+    ms = torch.empty((s.n_hyp, groups, 2), dtype=torch.float32, device=src1.device)
+    ts = None
+    if tail_stats:
+        ts = torch.zeros((s.n_hyp, int(l.dll.nope_op_conv_tail_stat_blocks(s.hs * s.ws, s.cout)), 2), dtype=torch.float32, device=src1.device)
+    slot, amax = _amax_scratch(src1.device) if want_amax else (None, None)
+    l.check(l.dll.nope_op_conv_gn_tail(dt, _ptr(src1), s.c1, _ptr(src2), s.c2, s.hs, s.ws, _ptr(s.pw), _ptr(s.b), _ptr(resid), _ptr(s.out), s.cout,
+                                       s.n_hyp, _ptr(colstats), colstats.shape[1], _ptr(g), _ptr(b), groups, float(eps), _ptr(ms), _ptr(ts),
+                                       _ptr(slot), _ptr(amax), _stream(src1)), "nope_op_conv_gn_tail")
+    if not (tail_stats or want_amax):
+        return s.out
+    extras = {"ms": ms}
+    if tail_stats:
+        extras["tail_stats"] = ts
+    if want_amax:
+        extras["amax"] = float(amax.item())
+    return s.out, extras
 
 
 def op_gn_apply_blocks(dt: int, hw: int, c: int, n_hyp: int) -> int:
