@@ -87,9 +87,12 @@ typedef void* nope_stream_t;
  * 13: nope_op_crop_frames;
  * 14: nope_op_group_norm_shared, nope_op_conv_class_weights;
  * 15: nope_op_refine_init / _normal_eq / _normal_eq_workspace_bytes / _step / _select, NOPE_REFINE_*;
- * 16: nope_op_conv_gn_tail, nope_op_conv_tail_stat_blocks).  Callers compare nope_abi_version() against the header they were
+ * 16: nope_op_conv_gn_tail, nope_op_conv_tail_stat_blocks;
+ * 17: nope_conv_op / nope_op_conv / nope_op_conv_query and nope_gn_op / nope_op_group_norm take their arguments by name and replace
+ *     nope_op_conv_ws, nope_op_conv_ex, nope_op_conv_gn_tail, nope_op_conv_splitk_bytes, nope_op_conv_stat_rows, nope_op_conv_tail_stat_blocks,
+ *     nope_op_group_norm_ex and nope_op_group_norm_shared).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 16
+#define NOPE_ABI_VERSION 17
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -494,94 +497,113 @@ int nope_op_nchw_to_nhwc(int dtype, const float* x_nchw, void* y_nhwc, int n, in
 int nope_op_nhwc_to_nchw(int dtype, const void* x_nhwc, float* y_nchw, int n, int C, int HW, nope_stream_t s);
 int nope_op_pack_conv_weight(int dtype, const float* w, void* packed, int Cout, int Cin, int ntaps, int mode,
                              nope_stream_t s);
+/* RANGE SLOTS (nope_conv_op, nope_gn_op, nope_op_absmax_f32).  `amax_slot` is a scratch of nope_op_amax_slot_words() 32-bit words (the
+ * entries clear it), `amax_out` one device float that receives max |.| of what the launch wrote, folded from the slot; both NULL = no
+ * request, one without the other is NOPE_ERR_ARG. */
+int nope_op_amax_slot_words(void);
 /* conv3x3(pad1) / conv1x1 / nearest-x2+conv3x3 (HardUpsample, model_utils.py:161-165) /
  * space-to-depth+conv1x1 (HardDownsample, :168-172) / stride-2 conv (encoder) over a virtual channel concat
- * (torch.cat((x, skip), dim=1), u_net.py:186,189,194) as one implicit GEMM. */
-int nope_op_conv(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws,
-                 int mode, int ntaps, const void* w_packed, const float* bias, const void* resid, void* out,
-                 int Cout, int n_hyp, int out_nchw, int out_dtype, int act_relu, nope_stream_t s);
-/* ... with a scratch for a deterministic split-K launch (f32 partials + fixed-order reduce) when the launcher wants one for the shape:
- * nope_op_conv_splitk_bytes returns the bytes it would use (0: this shape is never split); a smaller or NULL scratch = no split. */
-size_t nope_op_conv_splitk_bytes(int dtype, int C1, int C2, int rep1, int Hs, int Ws, int mode, int ntaps, int Cout, int n_hyp);
-int nope_op_conv_ws(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws,
-                    int mode, int ntaps, const void* w_packed, const float* bias, const void* resid, void* out,
-                    int Cout, int n_hyp, int out_nchw, int out_dtype, int act_relu, void* splitk_ws, size_t splitk_bytes, nope_stream_t s);
+ * (torch.cat((x, skip), dim=1), u_net.py:186,189,194) as one implicit GEMM, with the fusion plumbing the network runtimes launch around it
+ * (no reference counterpart: the reference runs Conv2d, GroupNorm and PreNorm as separate torch ops, model_utils.py:226-252).  The entry
+ * returns whatever the launcher returns: a combination the launcher refuses is refused here.
+ * Arguments by name: zero-initialise, set struct_size, fill in what the launch has.  A zero / NULL optional field means "absent". */
+typedef struct nope_conv_op {
+    uint32_t struct_size; int dtype;      /* struct_size: sizeof(nope_conv_op); anything else is NOPE_ERR_ARG before another field is read */
+    const void* src1; int C1; int rep1;      /* NHWC, C1 channels, shared by rep1 consecutive hypotheses (0 reads as 1) */
+    const void* src2; int C2; int rep2;      /* the second half of the virtual concat, or NULL with C2 = 0; rep2 as rep1 */
+    int Hs, Ws;                /* source map; NOPE_CONV_DOWN2 / _STRIDE2 / _STRIDE2_PAD01 need both even (NOPE_ERR_ARG) */
+    int mode, ntaps;           /* NOPE_CONV_* */
+    const void* w_packed;      /* nope_op_pack_conv_weight's */
+    const float* bias;         /* [Cout] or NULL */
+    const void* resid;         /* NHWC of the output's shape, added after the bias, or NULL */
+    void* out; int Cout, n_hyp;
+    int out_nchw, out_dtype;   /* 1: NCHW output of element type out_dtype; 0: NHWC of dtype's storage type */
+    int act_relu;              /* 1: ReLU after bias and residual */
+    void* splitk_ws; size_t splitk_bytes;      /* scratch for a deterministic split-K launch (f32 partials + fixed-order reduce) when the launcher wants one
+                                * for the shape: nope_op_conv_query says how many bytes it would use; a smaller or NULL scratch = no split */
+    float* colstats; int stat_rows;      /* [M / stat_rows][Cout][2] f32 (sum, sum of squares) of the f32 results (accumulator + bias) per block of stat_rows
+                                * output rows, or NULL; stat_rows must be nope_op_conv_query's answer (NOPE_ERR_ARG otherwise, and for a shape whose kernel
+                                * has no such form) */
+    const float* pn_ms; const float* pn_c0; const float* pn_c1;      /* pn_ms [n_hyp][2] (mean, rstd), pn_c0 / pn_c1 [Cout]: fused PreNorm of a 1x1
+                                * NOPE_CONV_PLAIN conv whose packed weights carry gamma, out[m, n] = rstd[b] (acc[m, n] - mean[b] c1[n]) + c0[n] + bias[n],
+                                * c0 = W beta, c1 = the row sums of the packed W gamma; or NULL */
+    /* The GroupNorm tail (gn_gamma set): the end of a ResnetBlock with a res_conv as the U-Net runtime launches it in the split-precision modes,
+     *     out[m, n] = conv1x1(src1 [cat src2])[m, n] + bias[n] + SiLU(GroupNorm(gn_G)(resid)[m, n] gn_gamma[n] + gn_beta[n]),
+     *   in two launches: (mean, rstd) [n_hyp][gn_G][2] of resid from its producer's column statistics tail_colstats
+     *   [n_hyp][tail_stat_blocks][Cout][2] (rows of 64; `colstats` of the launch that wrote resid) into gn_ms, then the conv, whose epilogue
+     *   normalises and activates each residual vector on its way in.  Same arithmetic as nope_op_group_norm (fast_silu = 1, that colstats,
+     *   act_silu = 1) with the conv's output as ITS residual: bit-identical.  resid may be `out` (in place).  NOPE_BF16X3 / NOPE_F16X2 only, and
+     *   only a launch the policy in force puts on the per-tap ping-pong kernel with the lean epilogue, H W a multiple of 64, (Cout / gn_G) a
+     *   multiple of 4, at most 64 tail_stats entries per hypothesis: NOPE_ERR_UNSUPPORTED otherwise -- never a launch without the tail, and
+     *   nothing is launched for a refused combination.  gn_ms or tail_colstats missing: NOPE_ERR_ARG. */
+    const float* tail_colstats; int tail_stat_blocks;
+    const float* gn_gamma; const float* gn_beta; int gn_G; float gn_eps; float* gn_ms;
+    float* tail_stats;         /* [n_hyp][nope_conv_op_info.tail_stat_blocks][2] or NULL: (sum, sum of squares) of the values written per 64-row x
+                                * 96-column tile, for nope_op_gn_finalize */
+    uint32_t* amax_slot; float* amax_out;      /* RANGE SLOTS above */
+} nope_conv_op;
+/* amax_recorded (host int, may be NULL): 1 when this launch's kernel records max |out| (f32 storage, the wide NHWC epilogue of the
+ * 128 x 192 / ping-pong / tap-resident kernels, no split-K), else 0: amax_out is then 0. */
+int nope_op_conv(const nope_conv_op* op, int* amax_recorded, nope_stream_t s);
+/* What nope_op_conv would do with `op`, without a launch: a pure host call; pointer fields count as NULL / non-NULL only and are never
+ * dereferenced.  Follows the launch policy in force (NOPE_* tuning variables), as the launch itself does. */
+typedef struct nope_conv_op_info {
+    size_t splitk_bytes;       /* bytes of splitk_ws the launcher would use (0: this shape is never split, or not a compute dtype) */
+    int stat_rows;             /* rows per block of the column statistics a conv of this shape can emit (64; 16 / 32 on 16- / 32-pixel maps from the kernels
+                                *   that have that form; 0 = none: residual, NCHW output, ReLU, NOPE_CONV_UP2P, Cout not in whole 16-byte vectors or > 2048,
+                                *   not a compute dtype) */
+    int tail_stat_blocks;      /* entries per hypothesis of tail_stats: one per 64-row x 96-column tile of the output map */
+    int records_out_amax;      /* nope_op_conv's amax_recorded, had amax_slot been given */
+    int err;                   /* NOPE_OK, or what nope_op_conv returns for `op` before anything launches */
+} nope_conv_op_info;
+int nope_op_conv_query(const nope_conv_op* op, nope_conv_op_info* info);
 /* conv1 of the encoder trunk: 7x7 / stride 2 / pad 3 on an NCHW f32 image, + per-channel scale (folded into the
  * weights) and shift + ReLU -> NHWC (n_img, H/2, W/2, 64).  w (64,3,7,7), scale/shift (64). */
 int nope_op_stem_conv(int dtype, const float* image, const float* w, const float* scale, const float* shift, float* w_scratch,
                       void* out, int n_img, int H, int W, nope_stream_t s);
-/* GroupNorm(G, C) [+ SiLU] [+ emb[hyp, c]] [+ resid]: Block.norm/act (model_utils.py:241-252),
- * the conditioning add (:274-276), PreNorm (:226-234) and Residual (:198-204).
- * `partial` scratch: n_hyp * nope_op_gn_chunks() * G * 2 floats. */
+/* GroupNorm(G, C) [+ SiLU] [+ emb[hyp, c]] [+ resid]: Block.norm/act (model_utils.py:241-252), the conditioning add (:274-276), PreNorm
+ * (:226-234) and Residual (:198-204), with the fusion plumbing the network runtimes launch around it:
+ *     y[j] = act(GN(x_eff[j / x_rep]) (1 + scale[j]) + shift[j]) + emb[j] + resid[j / resid_rep],   j in [0, n_hyp).
+ * Arguments by name, as nope_conv_op.  The statistics come from, in this order of precedence:
+ *   sh_s / sh_e     a pass over x_eff (the shared form below) into `partial`: n_hyp * nope_op_gn_chunks() * G * 2 floats;
+ *   colstats        [n_hyp / x_rep][stat_blocks][C][2], a conv's column statistics, folded by every workgroup itself (fold_launch = 0; C <= 2048,
+ *                   no FiLM) or by a fold launch into `partial` ((n_hyp / x_rep) * G * 2 floats) first (fold_launch = 1): same bits either way;
+ *   otherwise       a pass over x into `partial`: (n_hyp / x_rep) * nope_op_gn_chunks() * G * 2 floats.
+ * Refused with NOPE_ERR_ARG: n_hyp <= 0, H <= 0, W <= 0, x_rep < 0, an n_hyp that x_rep does not divide; in the shared form a missing `partial`. */
 int nope_op_gn_chunks(int dtype, int HW, int C);
-int nope_op_group_norm(int dtype, const void* x, void* y, float* partial, const float* gamma, const float* beta,
-                       int n_hyp, int HW, int C, int G, int act_silu, const float* emb, int emb_stride,
-                       const void* resid, nope_stream_t s);
-/* (ABI 11) The fusion plumbing around GroupNorm that the network runtimes use in place of the plain pair above, one launcher per entry
- * (no reference counterpart: the reference runs Conv2d, GroupNorm and PreNorm as separate torch ops, model_utils.py:226-252).  Every entry
- * returns whatever its launcher returns: a combination the launcher refuses is refused here.
- *   RANGE SLOTS.  `amax_slot` is a scratch of nope_op_amax_slot_words() 32-bit words (the entries clear it), `amax_out` one device float
- *   that receives max |.| of what the launch wrote, folded from the slot; both NULL = no request.
- * nope_op_conv_stat_rows: rows per block of the column statistics a conv of this shape can emit (64; 16 / 32 on 16- / 32-pixel maps from
- *   the kernels that have that form; 0 = none: residual, NCHW output, ReLU, NOPE_CONV_UP2P, Cout not in whole 16-byte vectors or > 2048).
- *   Follows the launch policy in force (NOPE_* tuning variables), as the launch itself does.
- * nope_op_conv_ex: nope_op_conv_ws plus
- *   colstats [M / stat_rows][Cout][2] f32 (sum, sum of squares) of the f32 results (accumulator + bias) per block of stat_rows output rows, or
- *            NULL; stat_rows must be nope_op_conv_stat_rows' answer (NOPE_ERR_ARG otherwise, and for a shape whose kernel has no such form);
- *   pn_ms [n_hyp][2] (mean, rstd), pn_c0 / pn_c1 [Cout]: fused PreNorm of a 1x1 NOPE_CONV_PLAIN conv whose packed weights carry gamma,
- *            out[m, n] = rstd[b] (acc[m, n] - mean[b] c1[n]) + c0[n] + bias[n], c0 = W beta, c1 = the row sums of the packed W gamma; or NULL;
- *   amax_recorded (host int, may be NULL): 1 when this launch's kernel records max |out| (f32 storage, the wide NHWC epilogue of the
- *            128 x 192 / ping-pong / tap-resident kernels, no split-K), else 0: amax_out is then 0. */
-int nope_op_amax_slot_words(void);
-int nope_op_conv_stat_rows(int dtype, int C1, int C2, int rep1, int Hs, int Ws, int mode, int ntaps, int Cout, int n_hyp, int has_resid,
-                           int out_nchw, int act_relu);
-int nope_op_conv_ex(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws, int mode,
-                    int ntaps, const void* w_packed, const float* bias, const void* resid, void* out, int Cout, int n_hyp,
-                    int out_nchw, int out_dtype, int act_relu, void* splitk_ws, size_t splitk_bytes, float* colstats, int stat_rows,
-                    const float* pn_ms, const float* pn_c0, const float* pn_c1, uint32_t* amax_slot, float* amax_out, int* amax_recorded,
-                    nope_stream_t s);
-/* nope_op_group_norm_ex: y[j] = act(GN(x[j / x_rep]) (1 + scale[j]) + shift[j]) + emb[j] + resid[j / resid_rep], j in [0, n_hyp).
- *   Statistics: colstats = NULL: a pass over x (as nope_op_group_norm; `partial`: (n_hyp / x_rep) * nope_op_gn_chunks() * G * 2 floats);
- *   else colstats [n_hyp / x_rep][stat_blocks][C][2], a conv's column statistics, folded by every workgroup itself (fold_launch = 0;
- *   C <= 2048, no FiLM) or by a fold launch into `partial` ((n_hyp / x_rep) * G * 2 floats) first (fold_launch = 1): same bits either way.
- *   film [scale (C) | shift (C)] rows, film_stride floats apart per hypothesis (0: one row for all), or NULL;
- *   out_stats [n_hyp][nope_op_gn_apply_blocks()][2]: (sum, sum of squares) of the values each workgroup wrote, or NULL (not with FiLM);
- *   fast_silu: f32 storage only, SiLU on the hardware exp / rcp (what the split-precision modes run; the 16-bit types always do) -- the
- *   only form that records a range maximum: with the libm SiLU or FiLM amax_out stays 0.
- * nope_op_gn_finalize: (mean, rstd) [n_hyp][2] of whole samples from nchunk (sum, sum of squares) pairs each (out_stats), count = HW * C. */
 int nope_op_gn_apply_blocks(int dtype, int HW, int C, int n_hyp);
-int nope_op_group_norm_ex(int dtype, const void* x, void* y, float* partial, const float* colstats, int stat_blocks, int fold_launch,
-                          const float* gamma, const float* beta, int n_hyp, int HW, int C, int G, int act_silu, const float* emb,
-                          int emb_stride, const float* film, int film_stride, const void* resid, int x_rep, int resid_rep, float* out_stats,
-                          float eps, int fast_silu, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
+typedef struct nope_gn_op {
+    uint32_t struct_size; int dtype;      /* struct_size: sizeof(nope_gn_op); anything else is NOPE_ERR_ARG before another field is read */
+    const void* x;             /* NHWC [n_hyp / x_rep][H W][C] */
+    void* y;                   /* NHWC [n_hyp][H W][C] */
+    float* partial; const float* colstats; int stat_blocks; int fold_launch;
+    const float* gamma; const float* beta;
+    int n_hyp, H, W;           /* H, W: the map; only H W counts outside the shared form */
+    int C, G, act_silu;
+    const float* emb; int emb_stride;        /* rows of C floats, emb_stride floats apart, or NULL */
+    const float* film; int film_stride;      /* [scale (C) | shift (C)] rows, film_stride floats apart per hypothesis (0: one row for all), or NULL */
+    const void* resid; int x_rep, resid_rep;      /* a rep of 0 reads as 1, as sh_rep */
+    float* out_stats;          /* [n_hyp][nope_op_gn_apply_blocks()][2]: (sum, sum of squares) of the values each workgroup wrote, or NULL (not with FiLM) */
+    float eps;                 /* no default: 0 is 0 */
+    int fast_silu;             /* f32 storage only, SiLU on the hardware exp / rcp (what the split-precision modes run; the 16-bit types always do) -- the
+                                * only form that records a range maximum: with the libm SiLU or FiLM amax_out stays 0 */
+    /* The shared addend (sh_s or sh_e set): the value that is normalised is
+     *     x_eff[j][p][c] = x[j][p][c] + sh_s[j / sh_rep][p][c] + sh_e[j][cls(p)][c],   j in [0, n_hyp), p = y W + x,
+     *   cls(p) = 3 (y == 0 ? 0 : y == H - 1 ? 2 : 1) + (x == 0 ? 0 : x == W - 1 ? 2 : 1), the border class of the pixel; sh_s f32 NHWC
+     *   [n_hyp / sh_rep][H W][C], sh_e f32 [n_hyp][9][C], both 16-byte aligned.  Two forms exist, the ones the U-Net's schedule launches under
+     *   NOPE_SHARED_SPLIT: sh_s + sh_e with x = NULL (H, W >= 2), and x + sh_s with sh_e = NULL; SiLU on (act_silu = 1), x_rep = 1, no colstats, no
+     *   FiLM; any other combination is refused (NOPE_ERR_ARG where the statistics pass refuses it, else NOPE_ERR_UNSUPPORTED).  x_eff is never
+     *   stored: the statistics pass forms it into `partial`, the apply pass forms it again and continues as without the addend (emb, resid /
+     *   resid_rep, out_stats, fast_silu, the range maximum). */
+    const float* sh_s; int sh_rep; const float* sh_e;
+    uint32_t* amax_slot; float* amax_out;      /* RANGE SLOTS above */
+} nope_gn_op;
+int nope_op_group_norm(const nope_gn_op* op, nope_stream_t s);
+/* (mean, rstd) [n_hyp][2] of whole samples from nchunk (sum, sum of squares) pairs each (out_stats, tail_stats), count = HW * C. */
 int nope_op_gn_finalize(const float* partial, float* ms, int n_hyp, int nchunk, float count, float eps, nope_stream_t s);
-/* nope_op_group_norm_shared: nope_op_group_norm_ex with a shared addend -- the value that is normalised is
- *     x_eff[j][p][c] = x[j][p][c] + sh_s[j / sh_rep][p][c] + sh_e[j][cls(p)][c],   j in [0, n_hyp), p = y W + x,
- *   cls(p) = 3 (y == 0 ? 0 : y == H - 1 ? 2 : 1) + (x == 0 ? 0 : x == W - 1 ? 2 : 1), the border class of the pixel; sh_s f32 NHWC
- *   [n_hyp / sh_rep][H W][C], sh_e f32 [n_hyp][9][C], both 16-byte aligned.  Two forms exist, the ones the U-Net's schedule launches under
- *   NOPE_SHARED_SPLIT: sh_s + sh_e with x = NULL (H, W >= 2), and x + sh_s with sh_e = NULL; SiLU on (act_silu = 1); any other combination is
- *   NOPE_ERR_UNSUPPORTED.  x_eff is never stored: a statistics pass forms it into `partial` (n_hyp * nope_op_gn_chunks() * G * 2 floats), the
- *   apply pass forms it again and continues as nope_op_group_norm_ex does (emb, resid / resid_rep, out_stats, fast_silu, the range maximum).
- * nope_op_conv_class_weights: w [Cout][Cin][3][3] f32 -> out [9][Cout][Cin] f32, out[cls][co][ci] = the sum of w[co][ci] over the taps a
- *   zero-padded 3x3 conv has inside the map at a pixel of border class cls: conv(u + e 1) = conv(u) + out[cls(p)] e for e constant over the map. */
-int nope_op_group_norm_shared(int dtype, const void* x, void* y, float* partial, const float* sh_s, int sh_rep, const float* sh_e, int H, int W,
-                              const float* gamma, const float* beta, int n_hyp, int C, int G, int act_silu, const float* emb, int emb_stride,
-                              const void* resid, int resid_rep, float* out_stats, float eps, int fast_silu, uint32_t* amax_slot, float* amax_out,
-                              nope_stream_t s);
+/* w [Cout][Cin][3][3] f32 -> out [9][Cout][Cin] f32, out[cls][co][ci] = the sum of w[co][ci] over the taps a zero-padded 3x3 conv has inside
+ * the map at a pixel of border class cls: conv(u + e 1) = conv(u) + out[cls(p)] e for e constant over the map. */
 int nope_op_conv_class_weights(const float* w, float* out, int Cout, int Cin, nope_stream_t s);
-/* (ABI 16) nope_op_conv_gn_tail: the end of a ResnetBlock with a res_conv as the U-Net runtime launches it in the split-precision modes,
- *     out[m, n] = conv1x1(src1 [cat src2])[m, n] + bias[n] + SiLU(GroupNorm(G)(resid)[m, n] gamma[n] + beta[n]),
- *   in two launches: (mean, rstd) [n_hyp][G][2] of resid from its producer's column statistics colstats [n_hyp][stat_blocks][Cout][2] (rows of 64;
- *   nope_op_conv_ex) into `ms`, then the conv, whose epilogue normalises and activates each residual vector on its way in.  Same arithmetic as
- *   nope_op_group_norm_ex (fast_silu = 1, that colstats, act_silu = 1) with the conv's output as ITS residual: bit-identical.  resid may be
- *   `out` (in place).  tail_stats [n_hyp][nope_op_conv_tail_stat_blocks()][2] or NULL: (sum, sum of squares) of the values written per 64-row x
- *   96-column tile, for nope_op_gn_finalize.  NOPE_BF16X3 / NOPE_F16X2 only, and only a launch the policy in force puts on the per-tap ping-pong
- *   kernel with the lean epilogue, H W a multiple of 64, (Cout / G) a multiple of 4, at most 64 tail_stats entries per hypothesis:
- *   NOPE_ERR_UNSUPPORTED otherwise -- never a launch without the tail. */
-int nope_op_conv_tail_stat_blocks(int HW, int Cout);
-int nope_op_conv_gn_tail(int dtype, const void* src1, int C1, const void* src2, int C2, int Hs, int Ws, const void* w_packed, const float* bias,
-                         const void* resid, void* out, int Cout, int n_hyp, const float* colstats, int stat_blocks, const float* gamma,
-                         const float* beta, int G, float eps, float* ms, float* tail_stats, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
 /* max |x[i]| over n f32 values (NaNs ignored; 0 for n = 0 or all zeros): what the runtimes run over conv-produced tensors in NOPE_F16X2. */
 int nope_op_absmax_f32(const float* x, size_t n, uint32_t* amax_slot, float* amax_out, nope_stream_t s);
 /* LinearAttention core (model_utils.py:403-416) and Attention core (:376-389) on a fused

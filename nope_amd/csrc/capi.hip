@@ -25,6 +25,58 @@ EnvVal env_lookup(EnvCache& c, const char* name) {
 }
 }  // namespace nope
 
+// ---- the operator entries that take their arguments by name (nope_conv_op, nope_gn_op): nothing below computes, refuses or repairs anything
+// ---- a launcher would not; each piece exists once
+template <class Op>
+static bool sized(const Op* op) { return op && op->struct_size == sizeof(Op); }      // a binding built against another layout is refused, not read past its end
+
+// the range slot of a launch -> one float: fold the slot's lines (launch_amax_reduce zeroes them again); the word IS the bit pattern of max |.|
+static int amax_decode(uint32_t* slot, float* amax_out, hipStream_t s) { return launch_amax_reduce(slot, 1, reinterpret_cast<unsigned*>(amax_out), s); }
+
+// the range-slot tail of an entry: clear the slot, launch, decode (no slot: just launch)
+template <class Launch>
+static int with_amax(uint32_t* slot, float* amax_out, hipStream_t s, Launch launch) {
+    if (slot && hipMemsetAsync(slot, 0, (size_t)kX2SlotWords * 4, s) != hipSuccess) return NOPE_ERR_LAUNCH;
+    if (const int e = launch()) return e;
+    return slot ? amax_decode(slot, amax_out, s) : NOPE_OK;
+}
+
+// nope_conv_op -> ConvArgs (always filled: the query answers for a launch the entry would refuse), and what the entry refuses before it plans
+static int conv_args(const nope_conv_op& op, ConvArgs& a) {
+    a.src1 = op.src1; a.C1 = op.C1; a.rep1 = op.rep1 > 0 ? op.rep1 : 1; a.src2 = op.src2; a.C2 = op.C2; a.rep2 = op.rep2 > 0 ? op.rep2 : 1;
+    a.Hs = op.Hs; a.Ws = op.Ws; a.mode = op.mode; a.ntaps = op.ntaps;
+    const bool up = op.mode == NOPE_CONV_UP2 || op.mode == NOPE_CONV_UP2P;
+    const bool half = op.mode == NOPE_CONV_DOWN2 || op.mode == NOPE_CONV_STRIDE2 || op.mode == NOPE_CONV_STRIDE2_PAD01;
+    a.Ho = up ? 2 * op.Hs : (half ? op.Hs / 2 : op.Hs);
+    a.Wo = up ? 2 * op.Ws : (half ? op.Ws / 2 : op.Ws);
+    a.act = op.act_relu ? 1 : 0;
+    a.w = op.w_packed; a.bias = op.bias; a.resid = op.resid; a.out = op.out; a.Cout = op.Cout; a.nhyp = op.n_hyp;
+    a.out_nchw = op.out_nchw; a.out_dt = op.out_dtype;
+    a.splitk_ws = op.splitk_ws; a.splitk_bytes = op.splitk_ws ? op.splitk_bytes : 0;
+    a.colstats = op.colstats;
+    if (op.colstats) a.stat_rows = op.stat_rows;
+    a.pn_ms = op.pn_ms; a.pn_c0 = op.pn_c0; a.pn_c1 = op.pn_c1;
+    a.gn_ms = op.gn_ms; a.gn_gamma = op.gn_gamma; a.gn_beta = op.gn_beta; a.gn_G = op.gn_G; a.tail_stats = op.tail_stats;
+    a.out_amax = op.amax_slot;
+    if (half && ((op.Hs | op.Ws) & 1)) return NOPE_ERR_ARG;
+    if ((op.amax_slot != nullptr) != (op.amax_out != nullptr)) return NOPE_ERR_ARG;
+    if (op.gn_gamma && (!op.gn_ms || !op.tail_colstats)) return NOPE_ERR_ARG;      // (conv_plan takes a launch without gn_ms for one without the tail)
+    return NOPE_OK;
+}
+
+// nope_gn_op -> GnApplyArgs but for the statistics source (nope_op_group_norm), and the entry's own argument checks
+static int gn_args(const nope_gn_op& op, GnApplyArgs& a) {
+    a.x = op.x; a.y = op.y; a.partial = op.partial; a.gamma = op.gamma; a.beta = op.beta;
+    a.nhyp = op.n_hyp; a.HW = op.H * op.W; a.C = op.C; a.G = op.G; a.act = op.act_silu; a.emb = op.emb; a.emb_stride = op.emb_stride;
+    a.film = op.film; a.film_stride = op.film_stride; a.resid = op.resid;
+    a.x_rep = op.x_rep ? op.x_rep : 1; a.resid_rep = op.resid_rep ? op.resid_rep : 1;
+    a.out_stats = op.out_stats; a.eps = op.eps; a.fast_silu = op.fast_silu; a.amax_out = op.amax_slot;
+    a.sh_s = op.sh_s; a.sh_rep = op.sh_rep ? op.sh_rep : 1; a.sh_e = op.sh_e; a.sh_H = op.H; a.sh_W = op.W;
+    if (op.n_hyp <= 0 || op.H <= 0 || op.W <= 0 || a.x_rep < 1 || op.n_hyp % a.x_rep) return NOPE_ERR_ARG;
+    if ((op.amax_slot != nullptr) != (op.amax_out != nullptr)) return NOPE_ERR_ARG;
+    return NOPE_OK;
+}
+
 extern "C" {
 
 int nope_abi_version(void) { return NOPE_ABI_VERSION; }
@@ -136,44 +188,35 @@ int nope_op_pack_conv_weight(int dtype, const float* w, void* packed, int Cout, 
     return launch_pack_conv_w(dtype, w, packed, Cout, Cin, ntaps, mode, (hipStream_t)s);
 }
 
-static void fill_conv_args(ConvArgs& a, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws, int mode, int ntaps,
-                           const void* w_packed, const float* bias, const void* resid, void* out, int Cout, int n_hyp, int out_nchw,
-                           int out_dtype, int act_relu) {
-    a.src1 = src1; a.C1 = C1; a.rep1 = rep1; a.src2 = src2; a.C2 = C2; a.rep2 = rep2 > 0 ? rep2 : 1;
-    a.Hs = Hs; a.Ws = Ws; a.mode = mode; a.ntaps = ntaps;
-    const bool up = mode == NOPE_CONV_UP2 || mode == NOPE_CONV_UP2P;
-    const bool half = mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2 || mode == NOPE_CONV_STRIDE2_PAD01;
-    a.Ho = up ? 2 * Hs : (half ? Hs / 2 : Hs);
-    a.Wo = up ? 2 * Ws : (half ? Ws / 2 : Ws);
-    a.act = act_relu ? 1 : 0;
-    a.w = w_packed; a.bias = bias; a.resid = resid; a.out = out; a.Cout = Cout; a.nhyp = n_hyp;
-    a.out_nchw = out_nchw; a.out_dt = out_dtype;
-}
-
-int nope_op_conv_ws(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws, int mode,
-                    int ntaps, const void* w_packed, const float* bias, const void* resid, void* out, int Cout, int n_hyp,
-                    int out_nchw, int out_dtype, int act_relu, void* splitk_ws, size_t splitk_bytes, nope_stream_t s) {
+int nope_op_conv(const nope_conv_op* op, int* amax_recorded, nope_stream_t stream) {
+    if (!sized(op)) return NOPE_ERR_ARG;
     ConvArgs a;
-    fill_conv_args(a, src1, C1, rep1, src2, C2, rep2, Hs, Ws, mode, ntaps, w_packed, bias, resid, out, Cout, n_hyp, out_nchw, out_dtype, act_relu);
-    if ((mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2 || mode == NOPE_CONV_STRIDE2_PAD01) && ((Hs | Ws) & 1)) return NOPE_ERR_ARG;
-    a.splitk_ws = splitk_ws; a.splitk_bytes = splitk_ws ? splitk_bytes : 0;
-    return launch_conv(dtype, a, (hipStream_t)s);
+    if (const int e = conv_args(*op, a)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    const ConvLaunch L = conv_plan(op->dtype, a);
+    if (amax_recorded) *amax_recorded = L.p.out_amax ? 1 : 0;      // (of the launch that runs: a slot was given and its epilogue fills it)
+    if (op->gn_gamma) {      // the GroupNorm tail of the per-tap ping-pong kernel's lean epilogue, as Fwd::res_tail (unet_runtime.hip) launches it
+        if (L.err != NOPE_OK) return L.err;      // (before the statistics launch: a refused combination launches nothing)
+        if (const int e = launch_gn_colstats_finalize(op->tail_colstats, op->gn_ms, a.nhyp, op->tail_stat_blocks, a.Cout, a.gn_G, a.Hs * a.Ws,
+                                                      op->gn_eps, s)) return e;
+    }
+    return with_amax(op->amax_slot, op->amax_out, s, [&] { return launch_conv(L, s); });
 }
 
-int nope_op_conv(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws, int mode,
-                 int ntaps, const void* w_packed, const float* bias, const void* resid, void* out, int Cout, int n_hyp,
-                 int out_nchw, int out_dtype, int act_relu, nope_stream_t s) {
-    return nope_op_conv_ws(dtype, src1, C1, rep1, src2, C2, rep2, Hs, Ws, mode, ntaps, w_packed, bias, resid, out, Cout, n_hyp, out_nchw,
-                           out_dtype, act_relu, nullptr, 0, s);
-}
-
-size_t nope_op_conv_splitk_bytes(int dtype, int C1, int C2, int rep1, int Hs, int Ws, int mode, int ntaps, int Cout, int n_hyp) {
+int nope_op_conv_query(const nope_conv_op* op, nope_conv_op_info* info) {
+    if (!sized(op) || !info) return NOPE_ERR_ARG;
     ConvArgs a;
-    static const int dummy = 0;
-    fill_conv_args(a, &dummy, C1, rep1, C2 ? &dummy : nullptr, C2, 1, Hs, Ws, mode, ntaps, &dummy, nullptr, nullptr, (void*)&dummy, Cout, n_hyp, 0, NOPE_F32, 0);
-    if (!dt_is_compute(dtype)) return 0;
-    const int S = conv_splitk_factor(dtype, a);
-    return S > 1 ? (size_t)S * (size_t)n_hyp * a.Ho * a.Wo * Cout * 4 : 0;
+    const int e = conv_args(*op, a);
+    // (the pre-queries validate nothing: keep them from dividing by an empty tile count)
+    const bool ask = dt_is_compute(op->dtype) && a.C1 > 0 && a.C2 >= 0 && a.Cout > 0 && a.nhyp > 0 && a.Hs > 0 && a.Ws > 0 && a.Ho > 0 && a.Wo > 0;
+    const int S = ask ? conv_splitk_factor(op->dtype, a) : 1;
+    info->splitk_bytes = S > 1 ? (size_t)S * (size_t)a.nhyp * a.Ho * a.Wo * a.Cout * 4 : 0;
+    info->stat_rows = ask && !a.act ? conv_stat_rows(op->dtype, a) : 0;      // (launch_conv refuses statistics behind an activation)
+    info->tail_stat_blocks = ask ? conv_tail_stat_blocks(a.Ho * a.Wo, a.Cout) : 0;
+    const ConvLaunch L = conv_plan(op->dtype, a);
+    info->records_out_amax = L.err == NOPE_OK && L.records_out_amax ? 1 : 0;
+    info->err = e ? e : L.err;
+    return NOPE_OK;
 }
 
 int nope_op_stem_conv(int dtype, const float* image, const float* w, const float* scale, const float* shift, float* w_scratch,
@@ -185,126 +228,39 @@ int nope_op_stem_conv(int dtype, const float* image, const float* w, const float
 
 int nope_op_gn_chunks(int dtype, int HW, int C) { return gn_stats_chunks(HW, C, dtype); }
 
-int nope_op_group_norm(int dtype, const void* x, void* y, float* partial, const float* gamma, const float* beta, int n_hyp, int HW,
-                       int C, int G, int act_silu, const float* emb, int emb_stride, const void* resid, nope_stream_t s) {
-    const int nch = gn_stats_chunks(HW, C, dtype);
-    int e = launch_gn_stats(dtype, x, partial, n_hyp, HW, C, G, nch, (hipStream_t)s);
-    if (e) return e;
-    GnApplyArgs a;
-    a.x = x; a.y = y; a.partial = partial; a.nchunk = nch; a.gamma = gamma; a.beta = beta;
-    a.nhyp = n_hyp; a.HW = HW; a.C = C; a.G = G; a.act = act_silu; a.emb = emb; a.emb_stride = emb_stride; a.resid = resid;
-    return launch_gn_apply(dtype, a, (hipStream_t)s);
-}
-
-// ---- (ABI 11) the fused GroupNorm statistics plumbing, one launcher each: nothing below computes, refuses or repairs anything itself ----
-int nope_op_amax_slot_words(void) { return kX2SlotWords; }
-
-// the range slot of a launch -> one float: fold the slot's lines (launch_amax_reduce zeroes them again); the word IS the bit pattern of max |.|
-static int amax_decode(uint32_t* slot, float* amax_out, hipStream_t s) { return launch_amax_reduce(slot, 1, reinterpret_cast<unsigned*>(amax_out), s); }
-
-int nope_op_absmax_f32(const float* x, size_t n, uint32_t* amax_slot, float* amax_out, nope_stream_t s) {
-    if (!amax_slot || !amax_out) return NOPE_ERR_ARG;
-    if (hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
-    if (const int e = launch_absmax_f32(x, n, amax_slot, (hipStream_t)s)) return e;
-    return amax_decode(amax_slot, amax_out, (hipStream_t)s);
-}
-
-int nope_op_conv_stat_rows(int dtype, int C1, int C2, int rep1, int Hs, int Ws, int mode, int ntaps, int Cout, int n_hyp, int has_resid,
-                           int out_nchw, int act_relu) {
-    ConvArgs a;
-    static const int dummy = 0;
-    fill_conv_args(a, &dummy, C1, rep1, C2 ? &dummy : nullptr, C2, 1, Hs, Ws, mode, ntaps, &dummy, nullptr, has_resid ? &dummy : nullptr, (void*)&dummy,
-                   Cout, n_hyp, out_nchw, NOPE_F32, act_relu);
-    if (!dt_is_compute(dtype) || act_relu) return 0;      // (launch_conv refuses statistics behind an activation)
-    return conv_stat_rows(dtype, a);
-}
-
-int nope_op_conv_ex(int dtype, const void* src1, int C1, int rep1, const void* src2, int C2, int rep2, int Hs, int Ws, int mode,
-                    int ntaps, const void* w_packed, const float* bias, const void* resid, void* out, int Cout, int n_hyp,
-                    int out_nchw, int out_dtype, int act_relu, void* splitk_ws, size_t splitk_bytes, float* colstats, int stat_rows,
-                    const float* pn_ms, const float* pn_c0, const float* pn_c1, uint32_t* amax_slot, float* amax_out, int* amax_recorded,
-                    nope_stream_t s) {
-    ConvArgs a;
-    fill_conv_args(a, src1, C1, rep1, src2, C2, rep2, Hs, Ws, mode, ntaps, w_packed, bias, resid, out, Cout, n_hyp, out_nchw, out_dtype, act_relu);
-    if ((mode == NOPE_CONV_DOWN2 || mode == NOPE_CONV_STRIDE2 || mode == NOPE_CONV_STRIDE2_PAD01) && ((Hs | Ws) & 1)) return NOPE_ERR_ARG;
-    if ((amax_slot != nullptr) != (amax_out != nullptr)) return NOPE_ERR_ARG;
-    a.splitk_ws = splitk_ws; a.splitk_bytes = splitk_ws ? splitk_bytes : 0;
-    a.colstats = colstats;
-    if (colstats) a.stat_rows = stat_rows;
-    a.pn_ms = pn_ms; a.pn_c0 = pn_c0; a.pn_c1 = pn_c1;
-    a.out_amax = amax_slot;
-    const ConvLaunch L = conv_plan(dtype, a);
-    if (amax_recorded) *amax_recorded = L.p.out_amax ? 1 : 0;      // (of the launch that runs: a slot was given and its epilogue fills it)
-    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
-    if (const int e = launch_conv(L, (hipStream_t)s)) return e;
-    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
-}
-
 int nope_op_gn_apply_blocks(int dtype, int HW, int C, int n_hyp) { return gn_apply_blocks(HW, C, dtype, n_hyp); }
+
+int nope_op_group_norm(const nope_gn_op* op, nope_stream_t stream) {
+    if (!sized(op)) return NOPE_ERR_ARG;
+    GnApplyArgs a;
+    if (const int e = gn_args(*op, a)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    const int dt = op->dtype, nx = a.nhyp / a.x_rep;
+    if (op->sh_s || op->sh_e) {              // the shared addend: a statistics pass forms x_eff, the apply pass forms it again
+        if (!op->partial) return NOPE_ERR_ARG;
+        if (op->colstats) return NOPE_ERR_UNSUPPORTED;
+        a.nchunk = gn_stats_chunks(a.HW, a.C, dt);
+        if (const int e = launch_gn_stats_shared(dt, a, op->partial, a.nchunk, s)) return e;
+    } else if (op->colstats && op->fold_launch) {      // the separate fold launch + the partial path (what the runtimes do under NOPE_GN_FOLD_INLINE)
+        if (const int e = launch_gn_fold(op->colstats, op->partial, nx, op->stat_blocks, a.C, a.G, s)) return e;
+    } else if (op->colstats) {               // every gn_apply workgroup folds its sample's column statistics itself
+        a.colstats = op->colstats; a.stat_blocks = op->stat_blocks;
+    } else {
+        a.nchunk = gn_stats_chunks(a.HW, a.C, dt);
+        if (const int e = launch_gn_stats(dt, op->x, op->partial, nx, a.HW, a.C, a.G, a.nchunk, s)) return e;
+    }
+    return with_amax(op->amax_slot, op->amax_out, s, [&] { return launch_gn_apply(dt, a, s); });
+}
 
 int nope_op_gn_finalize(const float* partial, float* ms, int n_hyp, int nchunk, float count, float eps, nope_stream_t s) {
     return launch_gn_finalize(partial, ms, n_hyp, nchunk, count, eps, (hipStream_t)s);
 }
 
-int nope_op_group_norm_ex(int dtype, const void* x, void* y, float* partial, const float* colstats, int stat_blocks, int fold_launch,
-                          const float* gamma, const float* beta, int n_hyp, int HW, int C, int G, int act_silu, const float* emb,
-                          int emb_stride, const float* film, int film_stride, const void* resid, int x_rep, int resid_rep, float* out_stats,
-                          float eps, int fast_silu, uint32_t* amax_slot, float* amax_out, nope_stream_t s) {
-    if (x_rep < 1 || n_hyp <= 0 || n_hyp % x_rep || (amax_slot != nullptr) != (amax_out != nullptr)) return NOPE_ERR_ARG;
-    GnApplyArgs a;
-    a.partial = partial;
-    if (colstats && fold_launch) {           // the separate fold launch + the partial path (what the runtimes do under NOPE_GN_FOLD_INLINE)
-        if (const int e = launch_gn_fold(colstats, partial, n_hyp / x_rep, stat_blocks, C, G, (hipStream_t)s)) return e;
-    } else if (colstats) {                   // every gn_apply workgroup folds its sample's column statistics itself
-        a.colstats = colstats; a.stat_blocks = stat_blocks;
-    } else {
-        a.nchunk = gn_stats_chunks(HW, C, dtype);
-        if (const int e = launch_gn_stats(dtype, x, partial, n_hyp / x_rep, HW, C, G, a.nchunk, (hipStream_t)s)) return e;
-    }
-    a.x = x; a.y = y; a.gamma = gamma; a.beta = beta;
-    a.nhyp = n_hyp; a.HW = HW; a.C = C; a.G = G; a.act = act_silu; a.emb = emb; a.emb_stride = emb_stride;
-    a.film = film; a.film_stride = film_stride; a.resid = resid; a.x_rep = x_rep; a.resid_rep = resid_rep;
-    a.out_stats = out_stats; a.eps = eps; a.fast_silu = fast_silu; a.amax_out = amax_slot;
-    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
-    if (const int e = launch_gn_apply(dtype, a, (hipStream_t)s)) return e;
-    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
-}
+int nope_op_amax_slot_words(void) { return kX2SlotWords; }
 
-int nope_op_group_norm_shared(int dtype, const void* x, void* y, float* partial, const float* sh_s, int sh_rep, const float* sh_e, int H, int W,
-                              const float* gamma, const float* beta, int n_hyp, int C, int G, int act_silu, const float* emb, int emb_stride,
-                              const void* resid, int resid_rep, float* out_stats, float eps, int fast_silu, uint32_t* amax_slot, float* amax_out,
-                              nope_stream_t s) {
-    if (n_hyp <= 0 || H <= 0 || W <= 0 || (amax_slot != nullptr) != (amax_out != nullptr) || !partial) return NOPE_ERR_ARG;
-    if (!sh_s && !sh_e) return NOPE_ERR_ARG;          // (nope_op_group_norm_ex is the entry without a shared addend)
-    GnApplyArgs a;
-    a.x = x; a.y = y; a.partial = partial; a.gamma = gamma; a.beta = beta;
-    a.nhyp = n_hyp; a.HW = H * W; a.C = C; a.G = G; a.act = act_silu; a.emb = emb; a.emb_stride = emb_stride;
-    a.resid = resid; a.resid_rep = resid_rep; a.out_stats = out_stats; a.eps = eps; a.fast_silu = fast_silu; a.amax_out = amax_slot;
-    a.sh_s = sh_s; a.sh_rep = sh_rep; a.sh_e = sh_e; a.sh_H = H; a.sh_W = W;
-    a.nchunk = gn_stats_chunks(a.HW, C, dtype);
-    if (const int e = launch_gn_stats_shared(dtype, a, partial, a.nchunk, (hipStream_t)s)) return e;
-    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
-    if (const int e = launch_gn_apply(dtype, a, (hipStream_t)s)) return e;
-    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
-}
-
-// ---- (ABI 16) the GroupNorm tail of the per-tap ping-pong kernel's lean epilogue, as Fwd::res_tail (unet_runtime.hip) launches it
-int nope_op_conv_tail_stat_blocks(int HW, int Cout) { return conv_tail_stat_blocks(HW, Cout); }
-
-int nope_op_conv_gn_tail(int dtype, const void* src1, int C1, const void* src2, int C2, int Hs, int Ws, const void* w_packed, const float* bias,
-                         const void* resid, void* out, int Cout, int n_hyp, const float* colstats, int stat_blocks, const float* gamma,
-                         const float* beta, int G, float eps, float* ms, float* tail_stats, uint32_t* amax_slot, float* amax_out, nope_stream_t s) {
-    if ((amax_slot != nullptr) != (amax_out != nullptr)) return NOPE_ERR_ARG;
-    ConvArgs a;
-    fill_conv_args(a, src1, C1, 1, src2, C2, 1, Hs, Ws, NOPE_CONV_PLAIN, 1, w_packed, bias, resid, out, Cout, n_hyp, 0, NOPE_F32, 0);
-    a.gn_ms = ms; a.gn_gamma = gamma; a.gn_beta = beta; a.gn_G = G; a.tail_stats = tail_stats;
-    a.out_amax = amax_slot;
-    const ConvLaunch L = conv_plan(dtype, a);
-    if (L.err != NOPE_OK) return L.err;      // (before the statistics launch: a refused combination launches nothing)
-    if (const int e = launch_gn_colstats_finalize(colstats, ms, n_hyp, stat_blocks, Cout, G, Hs * Ws, eps, (hipStream_t)s)) return e;
-    if (amax_slot && hipMemsetAsync(amax_slot, 0, (size_t)kX2SlotWords * 4, (hipStream_t)s) != hipSuccess) return NOPE_ERR_LAUNCH;
-    if (const int e = launch_conv(L, (hipStream_t)s)) return e;
-    return amax_slot ? amax_decode(amax_slot, amax_out, (hipStream_t)s) : NOPE_OK;
+int nope_op_absmax_f32(const float* x, size_t n, uint32_t* amax_slot, float* amax_out, nope_stream_t s) {
+    if (!amax_slot || !amax_out) return NOPE_ERR_ARG;
+    return with_amax(amax_slot, amax_out, (hipStream_t)s, [&] { return launch_absmax_f32(x, n, amax_slot, (hipStream_t)s); });
 }
 
 int nope_op_conv_class_weights(const float* w, float* out, int Cout, int Cin, nope_stream_t s) {

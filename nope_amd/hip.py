@@ -15,7 +15,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 16                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 17                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -75,6 +75,32 @@ class VisColumn(C.Structure):
 VIS_UNNORMALIZE, VIS_CLAMP, VIS_MAX_COLS = 1, 2, 8
 
 
+# The arguments of the conv / GroupNorm operator entries, by name.  tests/test_host_logic.py holds the field names to the header's, in order;
+# the entries refuse a struct_size that is not their sizeof.
+class ConvOp(C.Structure):
+    """nope_conv_op"""
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", _i), ("src1", _vp), ("C1", _i), ("rep1", _i), ("src2", _vp), ("C2", _i), ("rep2", _i),
+                ("Hs", _i), ("Ws", _i), ("mode", _i), ("ntaps", _i), ("w_packed", _vp), ("bias", _vp), ("resid", _vp), ("out", _vp),
+                ("Cout", _i), ("n_hyp", _i), ("out_nchw", _i), ("out_dtype", _i), ("act_relu", _i), ("splitk_ws", _vp), ("splitk_bytes", _sz),
+                ("colstats", _vp), ("stat_rows", _i), ("pn_ms", _vp), ("pn_c0", _vp), ("pn_c1", _vp),
+                ("tail_colstats", _vp), ("tail_stat_blocks", _i), ("gn_gamma", _vp), ("gn_beta", _vp), ("gn_G", _i), ("gn_eps", C.c_float),
+                ("gn_ms", _vp), ("tail_stats", _vp), ("amax_slot", _vp), ("amax_out", _vp)]
+
+
+class ConvOpInfo(C.Structure):
+    """nope_conv_op_info"""
+    _fields_ = [("splitk_bytes", _sz), ("stat_rows", _i), ("tail_stat_blocks", _i), ("records_out_amax", _i), ("err", _i)]
+
+
+class GnOp(C.Structure):
+    """nope_gn_op"""
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", _i), ("x", _vp), ("y", _vp), ("partial", _vp), ("colstats", _vp), ("stat_blocks", _i),
+                ("fold_launch", _i), ("gamma", _vp), ("beta", _vp), ("n_hyp", _i), ("H", _i), ("W", _i), ("C", _i), ("G", _i), ("act_silu", _i),
+                ("emb", _vp), ("emb_stride", _i), ("film", _vp), ("film_stride", _i), ("resid", _vp), ("x_rep", _i), ("resid_rep", _i),
+                ("out_stats", _vp), ("eps", C.c_float), ("fast_silu", _i), ("sh_s", _vp), ("sh_rep", _i), ("sh_e", _vp), ("amax_slot", _vp),
+                ("amax_out", _vp)]
+
+
 _PROTOS = {
     "nope_strerror": (C.c_char_p, [_i]),
     "nope_abi_version": (_i, []),
@@ -105,24 +131,14 @@ _PROTOS = {
     "nope_op_nhwc_to_nchw": (_i, [_i, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_pack_conv_weight": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nope_encoder_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "nope_op_conv": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "nope_op_conv_ws": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "nope_op_conv_splitk_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "nope_op_conv": (_i, [C.POINTER(ConvOp), C.POINTER(_i), _vp]),
+    "nope_op_conv_query": (_i, [C.POINTER(ConvOp), C.POINTER(ConvOpInfo)]),
     "nope_op_stem_conv": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_gn_chunks": (_i, [_i, _i, _i]),
-    "nope_op_group_norm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "nope_op_group_norm": (_i, [C.POINTER(GnOp), _vp]),
     "nope_op_amax_slot_words": (_i, []),
-    "nope_op_conv_stat_rows": (_i, [_i] * 13),
-    "nope_op_conv_ex": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp, _vp, _vp,
-                             _vp, _vp, C.POINTER(_i), _vp]),
     "nope_op_gn_apply_blocks": (_i, [_i, _i, _i, _i]),
-    "nope_op_conv_tail_stat_blocks": (_i, [_i, _i]),
-    "nope_op_conv_gn_tail": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, C.c_float, _vp, _vp, _vp, _vp, _vp]),
-    "nope_op_group_norm_ex": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, C.c_float, _i,
-                                   _vp, _vp, _vp]),
     "nope_op_gn_finalize": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp]),
-    "nope_op_group_norm_shared": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_float, _i,
-                                       _vp, _vp, _vp]),
     "nope_op_conv_class_weights": (_i, [_vp, _vp, _i, _i, _vp]),
     "nope_op_absmax_f32": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "nope_op_linear_attention": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -1105,10 +1121,35 @@ def pack_conv_weight(w: torch.Tensor, dt: int, mode: int = CONV_PLAIN) -> Tuple[
     return out, cin, ntaps
 
 
-def _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k):
-    """What op_conv and op_conv_ex set up alike: the packed weight, the shapes, the output tensor, the f32 bias and -- split_k -- the scratch the
-    launcher asks for (sk bytes), under the names of the entry points' arguments."""
+def _op_struct(cls, fields):
+    """A zeroed ConvOp / GnOp with struct_size and the named fields set; a tensor goes in as its data pointer, None as NULL."""
+    op = cls(struct_size=C.sizeof(cls))
+    for k, v in fields.items():
+        setattr(op, k, _ptr(v) if isinstance(v, torch.Tensor) else v)
+    return op
+
+
+def _conv_call(stream: int, **fields) -> bool:
+    """nope_op_conv on these fields of nope_conv_op; whether the launch recorded its range maximum."""
+    l, rec = lib(), _i(0)
+    l.check(l.dll.nope_op_conv(C.byref(_op_struct(ConvOp, fields)), C.byref(rec), stream), "nope_op_conv")
+    return bool(rec.value)
+
+
+def _conv_query(**fields) -> ConvOpInfo:
+    """nope_op_conv_query: a pure host call, pointers count as NULL / non-NULL only."""
+    l, info = lib(), ConvOpInfo()
+    l.check(l.dll.nope_op_conv_query(C.byref(_op_struct(ConvOp, fields)), C.byref(info)), "nope_op_conv_query")
+    return info
+
+
+def _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k, x2_shift=0):
+    """What the conv wrappers set up alike: the packed weight (x2_shift poked into it), the shapes, the output tensor, the f32 bias and -- split_k
+    -- the scratch the launcher asks for; `op` holds them under the names of nope_conv_op's fields."""
     pw, cin, ntaps = pack_conv_weight(w, dt, mode)
+    if x2_shift:
+        assert dt == F16X2
+        pw.view(torch.int32)[-1] = int(x2_shift)
     n1, hs, ws, c1 = src1.shape
     c2 = 0 if src2 is None else src2.shape[3]
     assert c1 + c2 == cin
@@ -1119,13 +1160,20 @@ def _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype,
         out = torch.empty((n_hyp, cout, ho, wo), dtype=torch_dtype(out_dtype), device=src1.device)
     else:
         out = torch.empty((n_hyp, ho, wo, cout), dtype=torch_dtype(dt), device=src1.device)
-    b = None if bias is None else _f32c(bias)
+    op = dict(dtype=dt, src1=src1, C1=c1, rep1=rep1, src2=src2, C2=c2, Hs=hs, Ws=ws, mode=mode, ntaps=ntaps, w_packed=pw, out=out, Cout=cout,
+              n_hyp=n_hyp)
     scratch, sk = None, 0
-    if split_k:
-        sk = int(lib().dll.nope_op_conv_splitk_bytes(dt, c1, c2, rep1, hs, ws, mode, ntaps, cout, n_hyp))
+    if split_k:      # (asked of the shape alone; a scratch the launch with all its arguments finds too small means no split)
+        sk = int(_conv_query(**op).splitk_bytes)
         if sk:
             scratch = torch.empty(sk, dtype=torch.uint8, device=src1.device)
-    return SimpleNamespace(pw=pw, ntaps=ntaps, c1=c1, c2=c2, hs=hs, ws=ws, ho=ho, wo=wo, cout=cout, n_hyp=n_hyp, out=out, b=b, scratch=scratch, sk=sk)
+    op.update(bias=None if bias is None else _f32c(bias), out_nchw=int(out_nchw), out_dtype=out_dtype, splitk_ws=scratch, splitk_bytes=sk)
+    return SimpleNamespace(op=op, ntaps=ntaps, hs=hs, ws=ws, ho=ho, wo=wo, cout=cout, n_hyp=n_hyp, out=out)
+
+
+def _amax_scratch(dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(range slot, one float) for an entry that reports max |.| of what it wrote (include/nope_hip.h: RANGE SLOTS; the entry clears the slot)."""
+    return (torch.empty(lib().dll.nope_op_amax_slot_words(), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
 
 
 def op_conv(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -1135,42 +1183,21 @@ def op_conv(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.T
     """src* NHWC tensors of dtype dt; w torch Conv2d weight (f32).  Returns NHWC (or NCHW).  split_k: hand the launcher the scratch it
     asks for (as the U-Net / encoder runtimes do), so shapes it would split along K (few tiles, long K) are.  x2_shift (F16X2 only): the
     activation range shift t of the packed layer (word 3 of the pack's tail; include/nope_hip.h: full accuracy for 2^(t-4) <= |a| <= 1792 2^t)."""
-    s = _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k)
-    if x2_shift:
-        assert dt == F16X2
-        s.pw.view(torch.int32)[-1] = int(x2_shift)
-    l = lib()
-    l.check(l.dll.nope_op_conv_ws(dt, _ptr(src1), s.c1, rep1, _ptr(src2), s.c2, rep2, s.hs, s.ws, mode, s.ntaps, _ptr(s.pw), _ptr(s.b),
-                                  _ptr(resid), _ptr(s.out), s.cout, s.n_hyp, int(out_nchw), out_dtype, int(act_relu), _ptr(s.scratch), s.sk,
-                                  _stream(src1)), "nope_op_conv")
+    s = _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k, x2_shift)
+    _conv_call(_stream(src1), rep2=rep2, resid=resid, act_relu=int(act_relu), **s.op)
     return s.out
 
 
-def op_group_norm(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, act_silu: bool = False,
-                  emb: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
-    n, h, w, c = x.shape
-    l = lib()
-    dt = storage_code(dt)
-    nch = l.dll.nope_op_gn_chunks(dt, h * w, c)
-    partial = torch.empty((n, nch, groups, 2), dtype=torch.float32, device=x.device)
-    y = torch.empty_like(x)
-    g, b = _f32c(gamma), _f32c(beta)
-    e = None if emb is None else _f32c(emb)
-    l.check(l.dll.nope_op_group_norm(dt, _ptr(x), _ptr(y), _ptr(partial), _ptr(g), _ptr(b), n, h * w, c, groups,
-                                     int(act_silu), _ptr(e), 0 if e is None else e.shape[1], _ptr(resid), _stream(x)),
-            "nope_op_group_norm")
-    return y
-
-
-def _amax_scratch(dev) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(range slot, one float) for an entry that reports max |.| of what it wrote (include/nope_hip.h: RANGE SLOTS; the entry clears the slot)."""
-    return (torch.empty(lib().dll.nope_op_amax_slot_words(), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+_ANY = C.c_int(0)      # a query's stand-in for a tensor that exists: its address, never read
 
 
 def op_conv_stat_rows(dt: int, c1: int, c2: int, rep1: int, hs: int, ws: int, mode: int, ntaps: int, cout: int, n_hyp: int,
                       resid: bool = False, out_nchw: bool = False, act_relu: bool = False) -> int:
     """Rows per block of the fused column statistics a conv of this shape emits under the launch policy in force (0: none)."""
-    return int(lib().dll.nope_op_conv_stat_rows(dt, c1, c2, rep1, hs, ws, mode, ntaps, cout, n_hyp, int(resid), int(out_nchw), int(act_relu)))
+    some = C.addressof(_ANY)
+    return int(_conv_query(dtype=dt, src1=some, C1=c1, rep1=rep1, src2=some if c2 else None, C2=c2, Hs=hs, Ws=ws, mode=mode, ntaps=ntaps,
+                           w_packed=some, resid=some if resid else None, out=some, Cout=cout, n_hyp=n_hyp, out_nchw=int(out_nchw),
+                           act_relu=int(act_relu)).stat_rows)
 
 
 def prenorm_fold(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, dt: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1197,57 +1224,47 @@ def op_conv_ex(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torc
                resid: Optional[torch.Tensor] = None, n_hyp: Optional[int] = None, out_nchw: bool = False,
                out_dtype: int = F32, act_relu: bool = False, split_k: bool = False, colstats: Optional[torch.Tensor] = None,
                stat_rows: int = 0, prenorm: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, want_amax: bool = False):
-    """op_conv through nope_op_conv_ex: `colstats` (an f32 tensor of at least [M / stat_rows][Cout][2] values, written in place) with
+    """op_conv with the fusion plumbing of nope_conv_op: `colstats` (an f32 tensor of at least [M / stat_rows][Cout][2] values, written in place) with
     `stat_rows` as op_conv_stat_rows answered; prenorm = (ms [n_hyp][2], gamma, beta): the conv reads the UN-normalised tensor and applies
     GroupNorm(1) in its epilogue (prenorm_fold); want_amax: returns (out, max |out| as the launch recorded it, whether it did record).
     A combination the launcher refuses raises NopeError."""
-    pn = None
+    pn = (None, None, None)
     if prenorm is not None:
         ms, gamma, beta = prenorm
         w, c0, c1 = prenorm_fold(w.cpu(), gamma.cpu(), beta.cpu(), dt)
         pn = (_f32c(ms), c0.to(src1.device), c1.to(src1.device))
         w = w.to(src1.device)
     s = _conv_setup(dt, src1, w, bias, src2, mode, rep1, n_hyp, out_nchw, out_dtype, split_k)
-    l = lib()
     if colstats is not None:
         assert colstats.dtype == torch.float32 and colstats.is_contiguous()
         assert stat_rows <= 0 or colstats.numel() >= (s.n_hyp * s.ho * s.wo // stat_rows) * s.cout * 2
     slot, amax = _amax_scratch(src1.device) if want_amax else (None, None)
-    rec = _i(0)
-    l.check(l.dll.nope_op_conv_ex(dt, _ptr(src1), s.c1, rep1, _ptr(src2), s.c2, rep2, s.hs, s.ws, mode, s.ntaps, _ptr(s.pw), _ptr(s.b),
-                                  _ptr(resid), _ptr(s.out), s.cout, s.n_hyp, int(out_nchw), out_dtype, int(act_relu), _ptr(s.scratch), s.sk,
-                                  _ptr(colstats), int(stat_rows), _ptr(pn[0]) if pn else None, _ptr(pn[1]) if pn else None,
-                                  _ptr(pn[2]) if pn else None, _ptr(slot), _ptr(amax), C.byref(rec), _stream(src1)), "nope_op_conv_ex")
+    rec = _conv_call(_stream(src1), rep2=rep2, resid=resid, act_relu=int(act_relu), colstats=colstats, stat_rows=int(stat_rows),
+                     pn_ms=pn[0], pn_c0=pn[1], pn_c1=pn[2], amax_slot=slot, amax_out=amax, **s.op)
     if want_amax:
-        return s.out, float(amax.item()), bool(rec.value)
+        return s.out, float(amax.item()), rec
     return s.out
 
 
 def op_conv_gn_tail(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], resid: torch.Tensor, colstats: torch.Tensor,
                     gamma: torch.Tensor, beta: torch.Tensor, groups: int, src2: Optional[torch.Tensor] = None, eps: float = 1e-5,
                     in_place: bool = False, tail_stats: bool = False, want_amax: bool = False, x2_shift: int = 0):
-    """conv1x1(src1 [cat src2]) + bias + SiLU(GroupNorm(groups)(resid)) in the conv's epilogue (nope_op_conv_gn_tail, include/nope_hip.h);
+    """conv1x1(src1 [cat src2]) + bias + SiLU(GroupNorm(groups)(resid)) in the conv's epilogue (nope_conv_op's GroupNorm tail, include/nope_hip.h);
     colstats [n][blocks][Cout][2]: resid's column statistics over blocks of 64 rows.  in_place: resid (a copy of it) is also the output buffer,
     as the U-Net runtime launches it.  Returns out, or (out, extras) with extras["tail_stats"] [n][op_conv_tail_stat_blocks][2] / extras["amax"]."""
-    s = _conv_setup(dt, src1, w, bias, src2, CONV_PLAIN, 1, None, False, F32, False)
+    s = _conv_setup(dt, src1, w, bias, src2, CONV_PLAIN, 1, None, False, F32, False, x2_shift)
     assert s.ntaps == 1 and tuple(resid.shape) == tuple(s.out.shape) and resid.dtype == torch.float32 and resid.is_contiguous()
     assert colstats.dtype == torch.float32 and colstats.is_contiguous() and tuple(colstats.shape[::3]) == (s.n_hyp, 2) and colstats.shape[2] == s.cout
-    if x2_shift:
-        assert dt == F16X2
-        s.pw.view(torch.int32)[-1] = int(x2_shift)
     if in_place:
         s.out.copy_(resid)
         resid = s.out
-    l = lib()
-    g, b = _f32c(gamma), _f32c(beta)
     ms = torch.empty((s.n_hyp, groups, 2), dtype=torch.float32, device=src1.device)
     ts = None
     if tail_stats:
-        ts = torch.zeros((s.n_hyp, int(l.dll.nope_op_conv_tail_stat_blocks(s.hs * s.ws, s.cout)), 2), dtype=torch.float32, device=src1.device)
+        ts = torch.zeros((s.n_hyp, int(_conv_query(**s.op).tail_stat_blocks), 2), dtype=torch.float32, device=src1.device)
     slot, amax = _amax_scratch(src1.device) if want_amax else (None, None)
-    l.check(l.dll.nope_op_conv_gn_tail(dt, _ptr(src1), s.c1, _ptr(src2), s.c2, s.hs, s.ws, _ptr(s.pw), _ptr(s.b), _ptr(resid), _ptr(s.out), s.cout,
-                                       s.n_hyp, _ptr(colstats), colstats.shape[1], _ptr(g), _ptr(b), groups, float(eps), _ptr(ms), _ptr(ts),
-                                       _ptr(slot), _ptr(amax), _stream(src1)), "nope_op_conv_gn_tail")
+    _conv_call(_stream(src1), resid=resid, tail_colstats=colstats, tail_stat_blocks=colstats.shape[1], gn_gamma=_f32c(gamma), gn_beta=_f32c(beta),
+               gn_G=groups, gn_eps=float(eps), gn_ms=ms, tail_stats=ts, amax_slot=slot, amax_out=amax, **s.op)
     if not (tail_stats or want_amax):
         return s.out
     extras = {"ms": ms}
@@ -1263,36 +1280,19 @@ def op_gn_apply_blocks(dt: int, hw: int, c: int, n_hyp: int) -> int:
     return int(lib().dll.nope_op_gn_apply_blocks(storage_code(dt), hw, c, n_hyp))
 
 
-def op_group_norm_ex(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, act_silu: bool = False,
-                     emb: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, film: Optional[torch.Tensor] = None,
-                     colstats: Optional[torch.Tensor] = None, fold_launch: bool = False, x_rep: int = 1, resid_rep: int = 1,
-                     out_stats: bool = False, eps: float = 1e-5, fast_silu: bool = False, want_amax: bool = False):
-    """op_group_norm through nope_op_group_norm_ex (include/nope_hip.h).  x NHWC [n_x][h][w][C], n_hyp = n_x * x_rep; emb (n_hyp, C);
-    resid NHWC of n_hyp / resid_rep samples; film (n_hyp, 2 C) = one [scale | shift] row per hypothesis, or (2 C,) = one row for all;
-    colstats [n_x][blocks][C][2] f32 column statistics instead of a statistics pass (fold_launch: folded by its own launch).
-    Returns y, or (y, extras) with extras["out_stats"] [n_hyp][op_gn_apply_blocks][2] / extras["amax"] when asked for."""
-    nx, h, w, c = x.shape
-    n = nx * x_rep
-    l = lib()
-    dt = storage_code(dt)
+def _gn_run(dt, y, partial_rows, groups, gamma, beta, act_silu, emb, out_stats, want_amax, **fields):
+    """What the GroupNorm wrappers do alike around nope_op_group_norm, into y NHWC [n_hyp][h][w][C]: the `partial` scratch (partial_rows x groups
+    (sum, sum of squares) pairs; 0: none), out_stats and the range slot when asked for, the call, and the return value: y, or (y, extras)."""
+    n, h, w, c = y.shape
     g, b = _f32c(gamma), _f32c(beta)
     e = None if emb is None else _f32c(emb)
-    f = None if film is None else _f32c(film)
-    fstride = 0 if f is None or f.dim() == 1 else f.shape[1]
-    if colstats is not None:
-        assert colstats.dtype == torch.float32 and colstats.is_contiguous() and tuple(colstats.shape[::3]) == (nx, 2) and colstats.shape[2] == c
-        partial = torch.empty((nx, groups, 2), dtype=torch.float32, device=x.device) if fold_launch else None
-        blocks = colstats.shape[1]
-    else:
-        partial = torch.empty((nx, l.dll.nope_op_gn_chunks(dt, h * w, c), groups, 2), dtype=torch.float32, device=x.device)
-        blocks = 0
-    y = torch.empty((n, h, w, c), dtype=x.dtype, device=x.device)
-    os_ = torch.empty((n, op_gn_apply_blocks(dt, h * w, c, n), 2), dtype=torch.float32, device=x.device) if out_stats else None
-    slot, amax = _amax_scratch(x.device) if want_amax else (None, None)
-    l.check(l.dll.nope_op_group_norm_ex(dt, _ptr(x), _ptr(y), _ptr(partial), _ptr(colstats), blocks, int(fold_launch), _ptr(g), _ptr(b),
-                                        n, h * w, c, groups, int(act_silu), _ptr(e), 0 if e is None else e.shape[1], _ptr(f), fstride,
-                                        _ptr(resid), x_rep, resid_rep, _ptr(os_), float(eps), int(fast_silu), _ptr(slot), _ptr(amax),
-                                        _stream(x)), "nope_op_group_norm_ex")
+    partial = torch.empty((partial_rows, groups, 2), dtype=torch.float32, device=y.device) if partial_rows else None
+    os_ = torch.empty((n, op_gn_apply_blocks(dt, h * w, c, n), 2), dtype=torch.float32, device=y.device) if out_stats else None
+    slot, amax = _amax_scratch(y.device) if want_amax else (None, None)
+    op = _op_struct(GnOp, dict(fields, dtype=dt, y=y, partial=partial, gamma=g, beta=b, n_hyp=n, H=h, W=w, C=c, G=groups, act_silu=int(act_silu), emb=e,
+                               emb_stride=0 if e is None else e.shape[1], out_stats=os_, amax_slot=slot, amax_out=amax))
+    l = lib()
+    l.check(l.dll.nope_op_group_norm(C.byref(op), _stream(y)), "nope_op_group_norm")
     if not (out_stats or want_amax):
         return y
     extras = {}
@@ -1301,39 +1301,54 @@ def op_group_norm_ex(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.
     if want_amax:
         extras["amax"] = float(amax.item())
     return y, extras
+
+
+def op_group_norm(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, act_silu: bool = False,
+                  emb: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    n, h, w, c = x.shape
+    dt = storage_code(dt)
+    return _gn_run(dt, torch.empty_like(x), n * lib().dll.nope_op_gn_chunks(dt, h * w, c), groups, gamma, beta, act_silu, emb, False, False,
+                   x=x, resid=resid, eps=1e-5)
+
+
+def op_group_norm_ex(dt: int, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, act_silu: bool = False,
+                     emb: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, film: Optional[torch.Tensor] = None,
+                     colstats: Optional[torch.Tensor] = None, fold_launch: bool = False, x_rep: int = 1, resid_rep: int = 1,
+                     out_stats: bool = False, eps: float = 1e-5, fast_silu: bool = False, want_amax: bool = False):
+    """op_group_norm with the fusion plumbing of nope_gn_op (include/nope_hip.h).  x NHWC [n_x][h][w][C], n_hyp = n_x * x_rep; emb (n_hyp, C);
+    resid NHWC of n_hyp / resid_rep samples; film (n_hyp, 2 C) = one [scale | shift] row per hypothesis, or (2 C,) = one row for all;
+    colstats [n_x][blocks][C][2] f32 column statistics instead of a statistics pass (fold_launch: folded by its own launch).
+    Returns y, or (y, extras) with extras["out_stats"] [n_hyp][op_gn_apply_blocks][2] / extras["amax"] when asked for."""
+    nx, h, w, c = x.shape
+    dt = storage_code(dt)
+    f = None if film is None else _f32c(film)
+    if colstats is not None:
+        assert colstats.dtype == torch.float32 and colstats.is_contiguous() and tuple(colstats.shape[::3]) == (nx, 2) and colstats.shape[2] == c
+        rows = nx if fold_launch else 0      # (`partial`: the fold launch's output; none when every workgroup folds for itself)
+    else:
+        rows = nx * lib().dll.nope_op_gn_chunks(dt, h * w, c)
+    y = torch.empty((nx * x_rep, h, w, c), dtype=x.dtype, device=x.device)
+    return _gn_run(dt, y, rows, groups, gamma, beta, act_silu, emb, out_stats, want_amax, x=x, colstats=colstats,
+                   stat_blocks=0 if colstats is None else colstats.shape[1], fold_launch=int(fold_launch), film=f,
+                   film_stride=0 if f is None or f.dim() == 1 else f.shape[1], resid=resid, x_rep=x_rep, resid_rep=resid_rep, eps=float(eps),
+                   fast_silu=int(fast_silu))
 
 
 def op_group_norm_shared(dt: int, x: Optional[torch.Tensor], sh_s: torch.Tensor, sh_e: Optional[torch.Tensor], gamma: torch.Tensor,
                          beta: torch.Tensor, groups: int, n_hyp: int, act_silu: bool = True, emb: Optional[torch.Tensor] = None,
                          resid: Optional[torch.Tensor] = None, resid_rep: int = 1, out_stats: bool = False, eps: float = 1e-5,
                          fast_silu: bool = False, want_amax: bool = False):
-    """GroupNorm of x_eff = x + sh_s[j / sh_rep] + sh_e[j][border class of the pixel] through nope_op_group_norm_shared (include/nope_hip.h).
+    """GroupNorm of x_eff = x + sh_s[j / sh_rep] + sh_e[j][border class of the pixel]: nope_gn_op's shared addend (include/nope_hip.h).
     sh_s f32 NHWC [n_s][h][w][C] shared by n_hyp / n_s consecutive hypotheses; sh_e f32 (n_hyp, 9, C) or None; x NHWC [n_hyp][h][w][C] of
     the storage type, or None.  Returns y (storage type), or (y, extras) as op_group_norm_ex."""
     ns, h, w, c = sh_s.shape
     assert sh_s.dtype == torch.float32 and sh_s.is_contiguous() and n_hyp % ns == 0
     assert sh_e is None or (sh_e.dtype == torch.float32 and sh_e.is_contiguous() and tuple(sh_e.shape) == (n_hyp, 9, c))
     assert x is None or (tuple(x.shape) == (n_hyp, h, w, c) and x.is_contiguous())
-    l = lib()
     dt = storage_code(dt)
-    g, b = _f32c(gamma), _f32c(beta)
-    e = None if emb is None else _f32c(emb)
-    partial = torch.empty((n_hyp, l.dll.nope_op_gn_chunks(dt, h * w, c), groups, 2), dtype=torch.float32, device=sh_s.device)
     y = torch.empty((n_hyp, h, w, c), dtype=torch_dtype(dt), device=sh_s.device)
-    os_ = torch.empty((n_hyp, op_gn_apply_blocks(dt, h * w, c, n_hyp), 2), dtype=torch.float32, device=sh_s.device) if out_stats else None
-    slot, amax = _amax_scratch(sh_s.device) if want_amax else (None, None)
-    l.check(l.dll.nope_op_group_norm_shared(dt, _ptr(x), _ptr(y), _ptr(partial), _ptr(sh_s), n_hyp // ns, _ptr(sh_e), h, w, _ptr(g), _ptr(b),
-                                            n_hyp, c, groups, int(act_silu), _ptr(e), 0 if e is None else e.shape[1], _ptr(resid), resid_rep,
-                                            _ptr(os_), float(eps), int(fast_silu), _ptr(slot), _ptr(amax), _stream(sh_s)),
-            "nope_op_group_norm_shared")
-    if not (out_stats or want_amax):
-        return y
-    extras = {}
-    if out_stats:
-        extras["out_stats"] = os_
-    if want_amax:
-        extras["amax"] = float(amax.item())
-    return y, extras
+    return _gn_run(dt, y, n_hyp * lib().dll.nope_op_gn_chunks(dt, h * w, c), groups, gamma, beta, act_silu, emb, out_stats, want_amax, x=x,
+                   sh_s=sh_s, sh_rep=n_hyp // ns, sh_e=sh_e, resid=resid, resid_rep=resid_rep, eps=float(eps), fast_silu=int(fast_silu))
 
 
 def op_conv_class_weights(w: torch.Tensor) -> torch.Tensor:

@@ -1,4 +1,4 @@
-"""Operator-level parity of the fused GroupNorm statistics plumbing (include/nope_hip.h, ABI 11: nope_op_conv_ex, nope_op_group_norm_ex,
+"""Operator-level parity of the fused GroupNorm statistics plumbing (include/nope_hip.h: nope_conv_op, nope_gn_op,
 nope_op_gn_finalize, nope_op_absmax_f32), each piece against float64 torch on operands rounded to the mode's storage type:
 
   (a) the four emitters of ConvArgs::colstats -- the wide epilogue's 64-row and 16-row forms, the small-tile kernel's 16 / 32 / 64-row form,

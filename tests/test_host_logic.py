@@ -33,6 +33,54 @@ def test_capi_exports_every_declared_symbol():
     assert dll.nope_strerror(-3) == b"workspace too small"
 
 
+def _header_struct_fields(name):
+    """The field names of `typedef struct <name> { ... }` in include/nope_hip.h, in order."""
+    src = open(os.path.join(ROOT, "include", "nope_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, flags=re.S).group(1)
+    return [re.search(r"(\w+)\s*(\[\w*\])?\s*$", d).group(1) for decl in body.split(";") if decl.strip() for d in decl.split(",")]
+
+
+def test_operator_structs_mirror_the_header():
+    """The ctypes mirrors of the operator entries' argument structs name the header's fields, in the header's order: a field inserted, dropped or
+    moved in one of the two is seen here; a field of another width moves sizeof, which the entries check (struct_size, below)."""
+    from nope_amd import hip
+    for name, mirror in (("nope_conv_op", hip.ConvOp), ("nope_conv_op_info", hip.ConvOpInfo), ("nope_gn_op", hip.GnOp)):
+        fields = _header_struct_fields(name)
+        assert len(fields) > 4 and fields == [f[0] for f in mirror._fields_], (name, fields)
+    assert _header_struct_fields("nope_conv_op")[:2] == _header_struct_fields("nope_gn_op")[:2] == ["struct_size", "dtype"]
+
+
+def test_operator_entries_refuse_another_struct_size(emu):
+    """A nope_conv_op / nope_gn_op whose struct_size is off by 4 -- a binding built against another layout -- is NOPE_ERR_ARG from all three
+    entries before anything else happens: the output buffers keep their sentinel.  The same structs with the right size run."""
+    hip = emu
+    dll = hip.lib().dll
+    g = torch.Generator().manual_seed(5)
+    x, w = hip.to_nhwc(torch.randn(1, 32, 4, 4, generator=g), 0), torch.randn(8, 32, 3, 3, generator=g) / 17
+    pw = hip.pack_conv_weight(w, 0)[0]
+    out, y, partial = torch.full((1, 4, 4, 8), -77.0), torch.full((1, 4, 4, 32), -77.0), torch.full((64, 8, 2), -77.0)
+    ga, be = torch.ones(32), torch.zeros(32)
+    conv = hip.ConvOp(struct_size=ctypes.sizeof(hip.ConvOp), dtype=0, src1=x.data_ptr(), C1=32, Hs=4, Ws=4, mode=hip.CONV_PLAIN, ntaps=9,
+                      w_packed=pw.data_ptr(), out=out.data_ptr(), Cout=8, n_hyp=1)
+    gn = hip.GnOp(struct_size=ctypes.sizeof(hip.GnOp), dtype=0, x=x.data_ptr(), y=y.data_ptr(), partial=partial.data_ptr(), gamma=ga.data_ptr(),
+                  beta=be.data_ptr(), n_hyp=1, H=4, W=4, C=32, G=8, eps=1e-5)
+    info = hip.ConvOpInfo(splitk_bytes=77, stat_rows=-77, tail_stat_blocks=-77, records_out_amax=-77, err=-77)
+    rec = ctypes.c_int(-77)
+    for off in (4, -4):
+        conv.struct_size, gn.struct_size = ctypes.sizeof(hip.ConvOp) + off, ctypes.sizeof(hip.GnOp) + off
+        assert dll.nope_op_conv(ctypes.byref(conv), ctypes.byref(rec), None) == -1
+        assert dll.nope_op_conv_query(ctypes.byref(conv), ctypes.byref(info)) == -1
+        assert dll.nope_op_group_norm(ctypes.byref(gn), None) == -1
+        assert bool((out == -77.0).all()) and bool((y == -77.0).all()) and bool((partial == -77.0).all()) and rec.value == -77
+        assert (info.splitk_bytes, info.stat_rows, info.tail_stat_blocks, info.records_out_amax, info.err) == (77, -77, -77, -77, -77)
+    conv.struct_size, gn.struct_size = ctypes.sizeof(hip.ConvOp), ctypes.sizeof(hip.GnOp)
+    assert dll.nope_op_conv(ctypes.byref(conv), ctypes.byref(rec), None) == 0 and rec.value == 0
+    assert dll.nope_op_conv_query(ctypes.byref(conv), ctypes.byref(info)) == 0 and info.err == 0 and info.stat_rows == 16
+    assert dll.nope_op_group_norm(ctypes.byref(gn), None) == 0
+    assert torch.equal(out, hip.op_conv(0, x, w, None)) and torch.equal(y, hip.op_group_norm(0, x, ga, be, 8))
+
+
 def test_code_object_is_gfx950():
     from nope_amd.csrc import build
     lib = build.build()
@@ -501,13 +549,14 @@ def test_tuning_switches_are_cached_and_reloaded(emu, capfd):
         libc.setenv(b"NOPE_CONV_PP", b"29", 1)
         xs, pw = hip.to_nhwc(x, 0), hip.pack_conv_weight(w, 0)[0]
         out = torch.empty(1, 4, 4, 8)
-        call = lambda: hip.lib().dll.nope_op_conv(0, xs.data_ptr(), 32, 1, None, 0, 1, 4, 4, 0, 9, pw.data_ptr(), None, None, out.data_ptr(), 8, 1, 0, 0, 0, None)
+        op = hip.ConvOp(struct_size=ctypes.sizeof(hip.ConvOp), dtype=0, src1=xs.data_ptr(), C1=32, rep1=1, Hs=4, Ws=4, mode=0, ntaps=9,
+                        w_packed=pw.data_ptr(), out=out.data_ptr(), Cout=8, n_hyp=1)
         dll = hip.lib().dll              # (os.environ still says 13: the binding sees no change and does not reload)
         capfd.readouterr()
-        assert dll.nope_op_conv(0, xs.data_ptr(), 32, 1, None, 0, 1, 4, 4, 0, 9, pw.data_ptr(), None, None, out.data_ptr(), 8, 1, 0, 0, 0, None) == 0
+        assert dll.nope_op_conv(ctypes.byref(op), None, None) == 0
         assert "halo256" in capfd.readouterr().err
         dll.nope_tuning_reload()
-        assert dll.nope_op_conv(0, xs.data_ptr(), 32, 1, None, 0, 1, 4, 4, 0, 9, pw.data_ptr(), None, None, out.data_ptr(), 8, 1, 0, 0, 0, None) == 0
+        assert dll.nope_op_conv(ctypes.byref(op), None, None) == 0
         assert "halo256" not in capfd.readouterr().err
     finally:
         os.environ.pop("NOPE_CONV_TRACE", None)

@@ -2,7 +2,7 @@
 output of block2's conv as its residual, and the lean epilogue of the per-tap ping-pong kernel (epilogue_wide, LEANM = 2) turns each residual
 vector r into SiLU(GN(r)) on its way in -- gn_apply_kernel's arithmetic -- adds, and stores the block's output over it.
 
-(1) operator level: nope_op_conv_gn_tail against conv + GroupNorm apply as two launches on the same inputs, bit for bit, with the range maximum;
+(1) operator level: hip.op_conv_gn_tail against conv + GroupNorm apply as two launches on the same inputs, bit for bit, with the range maximum;
 (2) the GroupNorm(1) partials the epilogue emits, against float64 sums, and the (mean, rstd) they finalise to against the two-launch form's;
 (3) a 32-dim U-Net at 16 x 16: NOPE_RES_TAIL=1 against 0 bit-equal, 3 against 0 through the f32 mode of the library;
 (4) where the one-pass form must NOT be taken: launches, trace and bytes equal NOPE_RES_TAIL=0, and the operator refuses;
@@ -81,7 +81,7 @@ def _case(hip, dev, name, shape, mode, shift):
 @pytest.mark.parametrize("mode,shift", MODES)
 @pytest.mark.parametrize("shape", SHAPES)
 def test_op_bit_identical_to_two_launches(be, shape, mode, shift, monkeypatch, capfd):
-    """(1) conv + SiLU(GN(resid)) in one launch == the conv, then nope_op_group_norm_ex (colstats, hardware SiLU) with the conv's output as its
+    """(1) conv + SiLU(GN(resid)) in one launch == the conv, then hip.op_group_norm_ex (colstats, hardware SiLU) with the conv's output as its
     residual: every bit of the output, in place (resid == out, as the runtime launches it) and with a separate residual, and the range maximum
     both record for that tensor: the out_amax slot's content is compared through the one float the entry decodes it to (hip._amax_scratch), not
     word by word.  The launch is the per-tap ping-pong kernel's lean epilogue with the tail (trace line)."""
@@ -269,7 +269,7 @@ def test_fallbacks_small_maps_and_narrow_groups(dev_be, monkeypatch, capfd):
 
 
 def test_operator_refuses_what_has_no_tail(be, monkeypatch):
-    """(4) nope_op_conv_gn_tail never launches without the tail: a 4 x 4 map, 2 channels per group, the f32 mode and a launch the policy puts on
+    """(4) hip.op_conv_gn_tail never launches without the tail: a 4 x 4 map, 2 channels per group, the f32 mode and a launch the policy puts on
     another kernel are refused (NopeError): conv_plan rejects the launch before anything is enqueued."""
     hip, dev, name = be
     g = torch.Generator().manual_seed(7700)

@@ -5,7 +5,7 @@ image instead of once per pose hypothesis, and the GroupNorm behind each forms t
                                weights (nope_op_conv_class_weights), cls(p) = 3 cy + cx the border class of pixel p;
   bit 1, final_res_block.block1: conv(W, cat(cur, r)) = conv(W[:, :C], cur) + Sr, Sr = conv(W[:, C:], r) + bias per reference.
 
-(1) the algebra in float64, on the library's class weights; (2) the GroupNorm form at operator level (nope_op_group_norm_shared) against
+(1) the algebra in float64, on the library's class weights; (2) the GroupNorm form at operator level (hip.op_group_norm_shared) against
 float64; (3) the tiny U-Net with the switch at 3 against 0 and against the oracle; (4) the f16x2 mode on the device; (5) nothing is written
 outside nope_unet_workspace_bytes.  Every test runs on the interpreter (tests/hipemu) and on the device unless it says otherwise."""
 import pytest
@@ -67,7 +67,7 @@ def _q(x, dt, hip):
 
 @pytest.mark.parametrize("dt", [0, 1, 2])
 def test_group_norm_shared_form(be, dt):
-    """(2) nope_op_group_norm_shared against float64 group_norm + SiLU + emb + resid of x_eff, on operands rounded to the storage type (S and
+    """(2) hip.op_group_norm_shared against float64 group_norm + SiLU + emb + resid of x_eff, on operands rounded to the storage type (S and
     E are f32 in every mode).  C = 16, G = 8 (two channels per group: no 16-byte vector lies in one group), maps 4 x 4 and 2 x 5, six
     hypotheses on two shared samples (s_rep = 3: n / rep against n % rep).  Both forms -- S + E without x, x + S -- each plain, with the
     embedding, with a residual shared by three hypotheses, with out_stats; the libm and (f32) the hardware SiLU.  Bounds: OP_TOL of

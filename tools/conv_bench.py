@@ -57,10 +57,11 @@ def main():
         out = torch.empty(a.nhyp, ho, ho, cout, device="cuda", dtype=tdt)
         bias = torch.randn(cout, device="cuda")
         st = torch.cuda.current_stream().cuda_stream
+        op = C.byref(hip._op_struct(hip.ConvOp, dict(dtype=dt, src1=s1, C1=c1, src2=s2, C2=c2, Hs=hs, Ws=hs, mode=mode, ntaps=ntaps, w_packed=pw,
+                                                     bias=bias, out=out, Cout=cout, n_hyp=a.nhyp)))
 
         def run():
-            rc = l.dll.nope_op_conv(dt, s1.data_ptr(), c1, 1, None if s2 is None else s2.data_ptr(), c2, 1, hs, hs, mode, ntaps,
-                                    pw.data_ptr(), bias.data_ptr(), None, out.data_ptr(), cout, a.nhyp, 0, 0, 0, st)
+            rc = l.dll.nope_op_conv(op, None, st)
             assert rc == 0, rc
         fl = 2.0 * a.nhyp * ho * ho * cout * ntaps * cin
         times = {pp: [] for pp in pps}

@@ -2,6 +2,7 @@
 the launcher: time per launch with WARM weights (the same tensor every launch: it stays in the 256 MB Infinity Cache) and COLD ones
 (rotating through more weight tensors than the cache holds) -- tells a latency / DRAM-efficiency problem of the weight stream from a
 compute problem.   python tools/conv_split_bench.py"""
+import ctypes
 import os
 import sys
 
@@ -19,13 +20,14 @@ def bench(c1, cout, h, n, nw, reps=40, dt=hip.F16):
     l = hip.lib()
     packed = [hip.pack_conv_weight(w, dt)[0] for w in ws]
     out = torch.empty(n, h, h, cout, dtype=tdt, device="cuda")
-    sk = int(l.dll.nope_op_conv_splitk_bytes(dt, c1, 0, 1, h, h, 0, 9, cout, n))
+    shape = dict(dtype=dt, src1=x, C1=c1, Hs=h, Ws=h, mode=hip.CONV_PLAIN, ntaps=9, out=out, Cout=cout, n_hyp=n)
+    sk = int(hip._conv_query(w_packed=packed[0], **shape).splitk_bytes)
     scratch = torch.empty(max(sk, 16), dtype=torch.uint8, device="cuda")
+    ops = [ctypes.byref(hip._op_struct(hip.ConvOp, dict(shape, w_packed=pw, bias=b, splitk_ws=scratch if sk else None, splitk_bytes=sk))) for pw in packed]
+    st = torch.cuda.current_stream().cuda_stream
 
     def run(i):
-        pw = packed[i % nw]
-        l.check(l.dll.nope_op_conv_ws(dt, x.data_ptr(), c1, 1, None, 0, 1, h, h, 0, 9, pw.data_ptr(), b.data_ptr(), None, out.data_ptr(), cout, n, 0, 0, 0,
-                                      scratch.data_ptr() if sk else None, sk, torch.cuda.current_stream().cuda_stream), "conv")
+        l.check(l.dll.nope_op_conv(ops[i % nw], None, st), "conv")
     for i in range(nw + 3):
         run(i)
     torch.cuda.synchronize()

@@ -3,6 +3,7 @@ kernel's tuning ablations (NOPE_PP_VARIANT: 16 = no DMA stream, 32 = no MFMA, 64
 on the first tap of a channel chunk only, 1 = fragment reads before the DMA pieces -- wrong results, right instruction streams; sums combine), and
 two launches of the tap-resident kernel beside them.      python tools/pp_stream_probe.py [--nhyp 512]"""
 import argparse
+import ctypes
 import os
 import sys
 
@@ -37,9 +38,11 @@ def main():
             out = torch.empty(a.nhyp, ho, ho, cout, device="cuda", dtype=tdt)
             st = torch.cuda.current_stream().cuda_stream
 
+            op = ctypes.byref(hip._op_struct(hip.ConvOp, dict(dtype=dt, src1=s1, C1=c1, src2=s2, C2=c2, Hs=hs, Ws=hs, mode=mode, ntaps=ntaps,
+                                                              w_packed=pw, out=out, Cout=cout, n_hyp=a.nhyp)))
+
             def run(l):
-                rc = l.dll.nope_op_conv(dt, s1.data_ptr(), c1, 1, None if s2 is None else s2.data_ptr(), c2, 1, hs, hs, mode, ntaps,
-                                        pw.data_ptr(), None, None, out.data_ptr(), cout, a.nhyp, 0, 0, 0, st)
+                rc = l.dll.nope_op_conv(op, None, st)
                 assert rc == 0, rc
             line = f"{name:34s} {dtn:7s}"
             for var in ("0", "16", "32", "48", "112", "128") if ks == 3 else ("0", "16", "32", "1024", "512", "48", "49", "112"):

@@ -2,6 +2,7 @@
 it replaces, interleaved in ONE process (median of rounds).  Prints time, algorithmic bytes / time, and whether the outputs are equal bits.
     python tools/stream_bench.py [--dtype bf16x3] [--nhyp 512] [--settings "NOPE_CONV_STREAM=0;NOPE_CONV_STREAM=1;NOPE_CONV_STREAM=3"]"""
 import argparse
+import ctypes
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,10 +40,11 @@ def main():
         out = torch.empty(a.nhyp, h, h, cout, device="cuda", dtype=tdt)
         bias = torch.randn(cout, device="cuda")
         st = torch.cuda.current_stream().cuda_stream
+        op = ctypes.byref(hip._op_struct(hip.ConvOp, dict(dtype=dt, src1=s1, C1=c1, src2=s2, C2=c2, Hs=h, Ws=h, mode=hip.CONV_PLAIN, ntaps=1, w_packed=pw,
+                                                          bias=bias, out=out, Cout=cout, n_hyp=a.nhyp)))
 
         def run():
-            rc = l.dll.nope_op_conv(dt, s1.data_ptr(), c1, 1, None if s2 is None else s2.data_ptr(), c2, 1, h, h, hip.CONV_PLAIN, 1,
-                                    pw.data_ptr(), bias.data_ptr(), None, out.data_ptr(), cout, a.nhyp, 0, 0, 0, st)
+            rc = l.dll.nope_op_conv(op, None, st)
             assert rc == 0, rc
         byts = a.nhyp * h * h * (cin + cout) * es
         times = [[] for _ in settings]

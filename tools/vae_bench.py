@@ -7,6 +7,7 @@ peak.  One JSON line per measurement.
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -62,9 +63,11 @@ def main():
         out = torch.empty((8, 256, 256, 128), dtype=hip.torch_dtype(dt), device="cuda")
         l = hip.lib()
 
+        op = ctypes.byref(hip._op_struct(hip.ConvOp, dict(dtype=dt, src1=x, C1=128, Hs=256, Ws=256, mode=hip.CONV_PLAIN, ntaps=9, w_packed=pw, out=out,
+                                                          Cout=128, n_hyp=8)))
+
         def run():
-            l.check(l.dll.nope_op_conv(dt, x.data_ptr(), 128, 1, None, 0, 1, 256, 256, 0, 9, pw.data_ptr(), None, None, out.data_ptr(), 128, 8, 0, 0, 0,
-                                       hip._stream(x)), "conv")
+            l.check(l.dll.nope_op_conv(op, None, hip._stream(x)), "conv")
         ms = timed(run, 10)
         tflops = 2 * 8 * 256 * 256 * 128 * 128 * 9 / ms / 1e9
         print(json.dumps(dict(what="decoder_conv3x3_256x256_128ch", mode=name, batch=8, ms=ms, tflops=tflops)), flush=True)
