@@ -3,7 +3,7 @@
 // Host code only: built against tests/hipemu/include and linked to the interpreter library (tests/hipemu/build_emu.py); launches nothing.
 //
 //   conv_plan_dump table [K0 K1]    the thinned sweep that tests/conv_plan_table.txt records (tests/test_conv_plan.py)
-//   conv_plan_dump full E D         one shard of the full sweep: environment setting E (0..26), compute type D (0..5)
+//   conv_plan_dump full E D         one shard of the full sweep: environment setting E (0..39), compute type D (0..5); the sweep, then the GroupNorm-tail launches
 //
 // A deliberate change of the dispatch policy changes the table: regenerate it with
 //   python tests/test_conv_plan.py --regenerate
@@ -26,17 +26,29 @@ static const EnvSetting kEnvs[] = {
     {"NOPE_CONV_VARIANT=4"}, {"NOPE_HALO_SPLIT=0"}, {"NOPE_HALO_PERSIST=8"}, {"NOPE_XCD_MAP=1"}, {"NOPE_XCD_GN=2"}, {"NOPE_XCD_ANY=0"},
     {"NOPE_CONV_PERSIST=0"}, {"NOPE_EPILOGUE_LEAN=0"}, {"NOPE_STATS16=0"}, {"NOPE_UP2P_HALO=0"}, {"NOPE_UP2P_HALO=2"}, {"NOPE_X2_PP=0"},
     {"NOPE_X2_SMALL=1"}, {"NOPE_GEGLU_FUSED=2"},
+    // 27..: one setting per switch the settings above leave alone
+    {"NOPE_SMALL_MAX_TILES=64"}, {"NOPE_SMALL_1X1_MAXK=3"}, {"NOPE_SMALL_DEEP_MAX=512"}, {"NOPE_SMALL_KG2_MAX=0"},
+    {"NOPE_HALO_SPLIT_MIN_CHUNKS=4"}, {"NOPE_HALO_SPLIT_MAX_TILES=64"}, {"NOPE_HALO_MIN_TILES=256"},
+    {"NOPE_CONV_STREAM=1 NOPE_STREAM_GRID=8 NOPE_STREAM_MIN_ITERS=128"}, {"NOPE_GEGLU_FUSED_F32=0"}, {"NOPE_NCHW_STAGED=0"}, {"NOPE_PERSIST_GRID=256"},
+    {"NOPE_PP_VARIANT=1"}, {"NOPE_GEGLU_FUSED=0"},
 };
 constexpr int kNumEnvs = (int)(sizeof(kEnvs) / sizeof(kEnvs[0]));
-static const char* const kSwitches[] = {"NOPE_CONV_PP", "NOPE_CONV_SMALL", "NOPE_SMALL_TILE", "NOPE_CONV_STREAM", "NOPE_STREAM_GRID", "NOPE_CONV_VARIANT",
-    "NOPE_HALO_SPLIT", "NOPE_HALO_PERSIST", "NOPE_XCD_MAP", "NOPE_XCD_GN", "NOPE_XCD_ANY", "NOPE_CONV_PERSIST", "NOPE_EPILOGUE_LEAN", "NOPE_STATS16",
-    "NOPE_UP2P_HALO", "NOPE_X2_PP", "NOPE_X2_SMALL", "NOPE_GEGLU_FUSED", "NOPE_CONV_TRACE", "NOPE_PP_VARIANT", "NOPE_SMALL_MAX_TILES", "NOPE_SMALL_1X1_MAXK",
-    "NOPE_SMALL_DEEP_MAX", "NOPE_SMALL_KG2_MAX", "NOPE_HALO_SPLIT_MIN_CHUNKS", "NOPE_HALO_SPLIT_MAX_TILES", "NOPE_HALO_MIN_TILES", "NOPE_STREAM_MIN_ITERS",
-    "NOPE_GEGLU_FUSED_F32", "NOPE_NCHW_STAGED", "NOPE_PERSIST_GRID"};
+extern char** environ;
 
 static void set_env(int e) {
-    for (const char* n : kSwitches) unsetenv(n);
     char buf[128];
+    for (bool again = true; again;) {      // every NOPE_* variable, whatever switches the library has by now (unsetenv moves `environ`: start over)
+        again = false;
+        for (char** v = environ; *v; ++v)
+            if (!strncmp(*v, "NOPE_", 5) && strchr(*v, '=')) {
+                const size_t n = (size_t)(strchr(*v, '=') - *v);
+                if (n >= sizeof(buf)) continue;
+                memcpy(buf, *v, n); buf[n] = 0;
+                unsetenv(buf);
+                again = true;
+                break;
+            }
+    }
     strncpy(buf, kEnvs[e].text, sizeof(buf) - 1); buf[sizeof(buf) - 1] = 0;
     for (char* tok = strtok(buf, " "); tok; tok = strtok(nullptr, " ")) {
         char* eq = strchr(tok, '=');
@@ -59,7 +71,7 @@ static const int kSide[] = {4, 8, 16, 30, 32, 34};      // both sides of HALO_MA
 static const int kNhyp[] = {1, 26, 64, 128, 256, 341, 512};
 enum { F_RESID = 1, F_NCHW = 2, F_ACT = 4, F_STATS = 8, F_PRENORM = 16, F_GEGLU = 32 };
 
-static int g_dummy[4];      // every pointer of a case points here; nothing dereferences them
+alignas(16) static int g_dummy[4];      // every pointer of a case points here; nothing dereferences them
 
 static void print_plan(const ConvLaunch& L) {
     const ConvParams& p = L.p;
@@ -76,11 +88,14 @@ static void print_plan(const ConvLaunch& L) {
     for (const void* q : ptrs) putchar(q ? '1' : '0');
     printf(" scale_at %lld", p.x2_scale ? (long long)((const unsigned char*)p.x2_scale - p.w) : -1LL);
     printf(" launch %u,%u,%u kind %d small %d bm %d x2 %d reduce %d", L.grid.x, L.grid.y, L.grid.z, L.kind, L.small, L.bm, L.x2 ? 1 : 0, L.reduce);
+    // GroupNorm tail (ConvArgs::gn_*): groups, the divider by channels per group, wave-tile columns; gn_ms gn_gamma gn_beta tail_stats, set or not
+    if (p.gn_ms) printf(" gn_G %d d_cpg %u.%u tail_cols %d tail %d%d%d%d", p.gn_G, p.d_cpg.M, p.d_cpg.sh, p.tail_cols, p.gn_ms ? 1 : 0, p.gn_gamma ? 1 : 0, p.gn_beta ? 1 : 0, p.tail_stats ? 1 : 0);
 }
 
 // One case: the arguments as a runtime would fill them (statistics and split-K scratch asked for first), the plan, the queries.
 // accepted_only: print nothing for a launch conv_plan refuses.  Returns whether a line was printed.
-static bool plan_line(int e, const DtCase& d, const ModeCase& mc, const int* cin, int cout, int side, int nhyp, int rep1, int flags, int ws, bool accepted_only = false) {
+static bool plan_line(int e, const DtCase& d, const ModeCase& mc, const int* cin, int cout, int side, int nhyp, int rep1, int flags, int ws, bool accepted_only = false,
+                      int gn_G = 0, bool tail_stats = false) {      // gn_G > 0: with a GroupNorm tail on the residual
     ConvArgs a;
     a.src1 = g_dummy; a.C1 = cin[0]; a.rep1 = rep1;
     if (cin[1]) { a.src2 = g_dummy; a.C2 = cin[1]; }
@@ -95,6 +110,7 @@ static bool plan_line(int e, const DtCase& d, const ModeCase& mc, const int* cin
     if (flags & F_ACT) a.act = 1;
     if (flags & F_PRENORM) { a.pn_ms = a.pn_c0 = a.pn_c1 = (const float*)g_dummy; }
     if (flags & F_GEGLU) a.geglu = 1;
+    if (gn_G) { a.gn_ms = a.gn_gamma = a.gn_beta = (const float*)g_dummy; a.gn_G = gn_G; if (tail_stats) a.tail_stats = (float*)g_dummy; }
     const int stat_rows = conv_stat_rows(d.dt, a);
     if (flags & F_STATS) {
         if (stat_rows == 0) return false;      // (no statistics from this shape: the caller does not ask)
@@ -109,7 +125,9 @@ static bool plan_line(int e, const DtCase& d, const ModeCase& mc, const int* cin
     const ConvLaunch L = conv_plan(d.dt, a);
     const int err = L.err;
     if (err != NOPE_OK && accepted_only) return false;
-    printf("env %d %s mode %d taps %d Cin %d+%d Cout %d side %d nhyp %d rep1 %d flags %d ws %d | ", e, d.name, mc.mode, mc.ntaps, cin[0], cin[1], cout, side, nhyp, rep1, flags, ws);
+    printf("env %d %s mode %d taps %d Cin %d+%d Cout %d side %d nhyp %d rep1 %d flags %d ws %d", e, d.name, mc.mode, mc.ntaps, cin[0], cin[1], cout, side, nhyp, rep1, flags, ws);
+    if (gn_G) printf(" gn %d,%d", gn_G, tail_stats ? 1 : 0);
+    printf(" | ");
     if (err == NOPE_OK) print_plan(L);
     printf(" | err %d stat_rows %d splitk %d", err, stat_rows, S);
     if (err == NOPE_OK)      // (of a launch that is refused there is no plan to ask about)
@@ -154,6 +172,16 @@ static void sweep(int e, const DtCase& d, const int* nhyps, int n_nhyp, unsigned
         }
 }
 
+// The launches with a GroupNorm tail (ConvArgs::gn_*): 1x1 convs with a residual, refused ones included
+static void sweep_tail(int e, const DtCase& d) {
+    for (const auto& cin : kCin)
+        for (int cout : kCout)
+            for (int side : kSide)
+                for (int nhyp : kNhyp)
+                    for (int gn_G : {1, 32})
+                        for (int ts = 0; ts < 2; ++ts) plan_line(e, d, kModes[0], cin, cout, side, nhyp, 1, F_RESID, 0, false, gn_G, ts != 0);
+}
+
 int main(int argc, char** argv) {
     unsigned counter = 0;
     if (argc == 4 && !strcmp(argv[1], "full")) {
@@ -161,6 +189,7 @@ int main(int argc, char** argv) {
         if (e < 0 || e >= kNumEnvs || d < 0 || d >= 6) return 2;
         set_env(e);
         sweep(e, kDts[d], kNhyp, 7, 0, counter);
+        sweep_tail(e, kDts[d]);
         return 0;
     }
     if (argc >= 2 && !strcmp(argv[1], "table")) {
@@ -176,7 +205,7 @@ int main(int argc, char** argv) {
         }
         // one launch of every form the thinning above might miss (tests/test_conv_plan.py lists what a table must contain), and launches
         // conv_plan refuses (the sweep leaves out what is refused for its arguments alone)
-        struct Witness { int env, dt; ModeCase mc; int cin, cout, side, nhyp, flags, ws; };
+        struct Witness { int env, dt; ModeCase mc; int cin, cout, side, nhyp, flags, ws, gn_G, tail_stats; };
         static const Witness witnesses[] = {
             {0, 0, {NOPE_CONV_PLAIN, 9}, 1, 320, 8, 512, 0, 0},              // position-major rows (f32 keeps the 128 x 192 kernel)
             {0, 1, {NOPE_CONV_PLAIN, 1}, 1, 8, 16, 512, 0, 0},               // tile walk: 128 x 192 kernel
@@ -204,11 +233,15 @@ int main(int argc, char** argv) {
             {0, 1, {NOPE_CONV_PLAIN, 1}, 2, 192, 8, 64, 0, 0},               //          100 channels: no whole 16-byte vectors of 16-bit elements
             {0, 0, {NOPE_CONV_PLAIN, 1}, 0, 8, 4, 26, F_GEGLU, 0},           //          GEGLU off the LDS-DMA kernel
             {0, 5, {NOPE_CONV_UP2, 9}, 3, 192, 8, 64, 0, 0},                 //          the two-pass weights alone on a kernel that cannot read them
+            {0, 3, {NOPE_CONV_PLAIN, 1}, 5, 384, 16, 256, F_RESID, 0, 32, 1},       // GroupNorm tail: the per-tap ping-pong kernel's lean epilogue
+            {0, 3, {NOPE_CONV_PLAIN, 9}, 3, 384, 16, 256, F_RESID, 0, 32, 1},       //   refused: a 3x3 conv that goes tap-resident
+            {0, 3, {NOPE_CONV_PLAIN, 1}, 5, 384, 8, 26, F_RESID, 0, 32, 1},         //            a launch of the small-tile kernel
+            {38, 3, {NOPE_CONV_PLAIN, 1}, 5, 384, 16, 256, F_RESID, 0, 32, 1},      //            the accepted launch under NOPE_PP_VARIANT=1 (the ablations have no tail)
         };
         printf("# one launch of every form, and refused launches\n");
         for (const Witness& w : witnesses) {
             set_env(w.env);
-            plan_line(w.env, kDts[w.dt], w.mc, kCin[w.cin], w.cout, w.side, w.nhyp, 1, w.flags, w.ws);
+            plan_line(w.env, kDts[w.dt], w.mc, kCin[w.cin], w.cout, w.side, w.nhyp, 1, w.flags, w.ws, false, w.gn_G, w.tail_stats != 0);
         }
         return 0;
     }

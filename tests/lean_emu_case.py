@@ -12,8 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "hipemu"))
 import torch
 import torch.nn.functional as F
 
-from tests.stream_emu_case import _env, _restore
-from tests.util import rel
+from tests.util import rel, switches
 
 X2 = 4
 
@@ -29,12 +28,10 @@ def run(hip, dev, dts=(3, X2), light=False):
 
         def both(fn, what, ref, **env):
             nonlocal worst
-            old = _env(NOPE_EPILOGUE_LEAN=0, **env)
-            y0 = fn()
-            _restore(old)
-            old = _env(NOPE_EPILOGUE_LEAN=1, **env)
-            y1 = fn()
-            _restore(old)
+            with switches(NOPE_EPILOGUE_LEAN=0, **env):
+                y0 = fn()
+            with switches(NOPE_EPILOGUE_LEAN=1, **env):
+                y1 = fn()
             e = rel(hip.to_nchw(y1, 0).cpu(), ref)
             worst = max(worst, e / tol)
             assert e < tol, (what, dt, e)

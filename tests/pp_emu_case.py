@@ -13,11 +13,15 @@ import torch.nn.functional as F
 import build_emu
 from nope_amd import hip
 from oracle import nope_ref as R
-from tests.util import rel
+from tests.util import rel, switches
 
 
 def run(hip, dev, dts=(1, 0), light=False):
-    os.environ["NOPE_CONV_PP"] = "13"          # ping-pong kernel wherever it applies, position-major on it too
+    with switches(NOPE_CONV_PP=13):            # ping-pong kernel wherever it applies, position-major on it too
+        return _run(hip, dev, dts, light)
+
+
+def _run(hip, dev, dts, light):
     g = torch.Generator().manual_seed(77)
     rn = lambda *s: torch.randn(*s, generator=g)
     d = lambda x: x.to(dev)
@@ -58,9 +62,8 @@ def run(hip, dev, dts=(1, 0), light=False):
         ww = rn(16, 2 * C, 3, 3) / (3 * (2 * C) ** 0.5)
         y = hip.op_conv(dt, hip.to_nhwc(d(xw), dt), d(ww), None)
         chk(y, F.conv2d(q(xw), q(ww), padding=1), "halo W=32")
-        os.environ["NOPE_CONV_PP"] = "29"      # same shapes per tap on the ping-pong kernel: identical bits
-        y2 = hip.op_conv(dt, hip.to_nhwc(d(xw), dt), d(ww), None)
-        os.environ["NOPE_CONV_PP"] = "13"
+        with switches(NOPE_CONV_PP=29):        # same shapes per tap on the ping-pong kernel: identical bits
+            y2 = hip.op_conv(dt, hip.to_nhwc(d(xw), dt), d(ww), None)
         assert torch.equal(y, y2), "tap-resident kernel differs from the per-tap kernel"
         if dt != 0:
             # a workgroup walking several tiles (next tile's prologue in flight under the epilogue): 8 workgroups, 3 tiles each
@@ -70,16 +73,10 @@ def run(hip, dev, dts=(1, 0), light=False):
             # (and four panels over a 4 x 2 XCD grid: each XCD two panels of its run, 16 workgroups x 4 tiles)
             for (ns, cc, side, co, wgs, gn) in ((384, C, 4, 24, "8", "1"), (256, 2 * C, 4, 24, "8", "1"), (64, C, 8, 200, "16", "1"), (64, C, 8, 600, "16", "2")):
                 xq, wq, bq = rn(ns, cc, side, side), rn(co, cc, 3, 3) / (3 * cc ** 0.5), rn(co)
-                os.environ["NOPE_CONV_PP"] = "11"      # (4x4 maps in (sample, pixel) row order too)
-                os.environ["NOPE_HALO_PERSIST"] = wgs
-                os.environ["NOPE_XCD_GN"] = gn
-                y = hip.op_conv(dt, hip.to_nhwc(d(xq), dt), d(wq), d(bq))
-                os.environ["NOPE_HALO_PERSIST"] = "0"
-                os.environ["NOPE_XCD_MAP"] = "1"
-                y2 = hip.op_conv(dt, hip.to_nhwc(d(xq), dt), d(wq), d(bq))
-                for k in ("NOPE_HALO_PERSIST", "NOPE_XCD_MAP", "NOPE_XCD_GN"):
-                    os.environ.pop(k)
-                os.environ["NOPE_CONV_PP"] = "13"
+                with switches(NOPE_CONV_PP=11, NOPE_HALO_PERSIST=wgs, NOPE_XCD_GN=gn):      # (4x4 maps in (sample, pixel) row order too)
+                    y = hip.op_conv(dt, hip.to_nhwc(d(xq), dt), d(wq), d(bq))
+                    with switches(NOPE_HALO_PERSIST=0, NOPE_XCD_MAP=1):
+                        y2 = hip.op_conv(dt, hip.to_nhwc(d(xq), dt), d(wq), d(bq))
                 chk(y, F.conv2d(q(xq), q(wq), bq, padding=1), f"halo walk {ns}x{cc}")
                 assert torch.equal(y, y2), "walking workgroups differ from one tile per workgroup"
         # 1x1, one K step (nk = 1) and two (nk = 2), residual
@@ -107,7 +104,6 @@ def run(hip, dev, dts=(1, 0), light=False):
         xp, wp, bp, rp = rn(256, C, 2, 2), rn(24, C, 3, 3) / (3 * C ** 0.5), rn(24), rn(256, 24, 2, 2)
         y = hip.op_conv(dt, hip.to_nhwc(d(xp), dt), d(wp), d(bp), resid=hip.to_nhwc(d(rp), dt))
         chk(y, F.conv2d(q(xp), q(wp), bp, padding=1) + q(rp), "posmajor")
-    os.environ.pop("NOPE_CONV_PP")
     return worst
 
 
@@ -117,8 +113,7 @@ def run_unet(hip, dev, dim, cdt, n_hyp=2, hw=8):
     from nope_amd.u_net import UNet
     from nope_amd.weights import synth_init_
     from tests.util import StubEncoder
-    os.environ["NOPE_CONV_PP"] = "9"
-    try:
+    with switches(NOPE_CONV_PP=9):
         u = UNet(u_net_dim=dim, rot_representation_dim=6, encoder=StubEncoder(8), pose_mlp_name="single_layer", compute_dtype=cdt)
         synth_init_(u, 2022)
         sd = {k: v.clone() for k, v in u.own_state_dict().items()}
@@ -128,8 +123,6 @@ def run_unet(hip, dev, dim, cdt, n_hyp=2, hw=8):
         y = u.forward_hypotheses(x.to(dev), pose.to(dev)).cpu()[0]
         want = R.unet_forward(sd, x.expand(n_hyp, -1, -1, -1), pose[0])
         return rel(y, want)
-    finally:
-        os.environ.pop("NOPE_CONV_PP")
 
 
 if __name__ == "__main__":

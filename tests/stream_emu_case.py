@@ -13,25 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import nope_ref as R
-from tests.util import rel
-
-
-def _env(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    for k, v in kw.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    return old
-
-
-def _restore(old):
-    for k, v in old.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
+from tests.util import rel, switches
 
 
 def run(hip, dev, dts=(3, 1), light=False):
@@ -48,13 +30,11 @@ def run(hip, dev, dts=(3, 1), light=False):
 
         def both(fn, what, ref, grid, min_iters=1):
             nonlocal worst
-            old = _env(NOPE_CONV_STREAM=0, NOPE_CONV_PP=0, NOPE_CONV_SMALL=0)
-            y_old = fn()
-            _restore(old)
-            old = _env(NOPE_CONV_STREAM=1, NOPE_STREAM_GRID=grid, NOPE_STREAM_MIN_ITERS=min_iters, NOPE_CONV_PP=0, NOPE_CONV_SMALL=0, NOPE_CONV_TRACE=1)
-            y = fn()
-            y2 = fn()
-            _restore(old)
+            with switches(NOPE_CONV_STREAM=0, NOPE_CONV_PP=0, NOPE_CONV_SMALL=0):
+                y_old = fn()
+            with switches(NOPE_CONV_STREAM=1, NOPE_STREAM_GRID=grid, NOPE_STREAM_MIN_ITERS=min_iters, NOPE_CONV_PP=0, NOPE_CONV_SMALL=0, NOPE_CONV_TRACE=1):
+                y = fn()
+                y2 = fn()
             e = rel(hip.to_nchw(y, dt).cpu(), ref)
             worst = max(worst, e / tol)
             assert e < tol, (what, dt, e)
@@ -92,12 +72,10 @@ def run_unet(hip, dev, dim, cdt, n_hyp=4, hw=16):
     u = u.to(dev)
     g = torch.Generator().manual_seed(23)
     x, pose = torch.randn(1, 8, hw, hw, generator=g), torch.randn(1, n_hyp, 6, generator=g)
-    old = _env(NOPE_CONV_STREAM=0)
-    y0 = u.forward_hypotheses(x.to(dev), pose.to(dev)).cpu()[0]
-    _restore(old)
-    old = _env(NOPE_CONV_STREAM=3, NOPE_STREAM_GRID=8, NOPE_STREAM_MIN_ITERS=1)
-    y = u.forward_hypotheses(x.to(dev), pose.to(dev)).cpu()[0]
-    _restore(old)
+    with switches(NOPE_CONV_STREAM=0):
+        y0 = u.forward_hypotheses(x.to(dev), pose.to(dev)).cpu()[0]
+    with switches(NOPE_CONV_STREAM=3, NOPE_STREAM_GRID=8, NOPE_STREAM_MIN_ITERS=1):
+        y = u.forward_hypotheses(x.to(dev), pose.to(dev)).cpu()[0]
     want = R.unet_forward(sd, x.expand(n_hyp, -1, -1, -1), pose[0])
     return rel(y, want), bool(torch.equal(y, y0))
 

@@ -11,6 +11,8 @@ import os
 import pytest
 import torch
 
+from tests.util import switches
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -60,9 +62,8 @@ def test_f16x2_tile_gpu(gpu):
         e = float((ys[0] - y3).abs().max() / y3.abs().max())
         print(f"f16x2 vs bf16x3, {cin} -> {cout} @ {h}x{h} x {n}: {e:.2e}")
         assert e < 3e-5
-        os.environ["NOPE_HALO_PERSIST"] = "0"
-        y1 = hip.op_conv(hip.F16X2, s1, w, b, src2=s2)
-        os.environ.pop("NOPE_HALO_PERSIST")
+        with switches(NOPE_HALO_PERSIST=0):
+            y1 = hip.op_conv(hip.F16X2, s1, w, b, src2=s2)
         assert torch.equal(ys[0], y1), ("tile walk differs", c1, c2, cout, h)
 
 
@@ -79,13 +80,10 @@ def test_up2p_tap_resident_gpu(gpu):
             w = torch.randn(cout, cin, 3, 3, device="cuda", generator=g) / (cin * 9) ** 0.5
             x = torch.randn(512, h, h, cin, device="cuda", generator=g)
             b = torch.randn(cout, device="cuda", generator=g)
-            os.environ["NOPE_UP2P_HALO"] = "2"         # (2: bf16x3 layers too; the default takes the tap-resident form for f16x2 layers only)
-            try:
+            with switches(NOPE_UP2P_HALO=2):           # (2: bf16x3 layers too; the default takes the tap-resident form for f16x2 layers only)
                 ys = [hip.op_conv(dt, x, w, b, mode=hip.CONV_UP2P) for _ in range(3)]
-                os.environ["NOPE_UP2P_HALO"] = "0"
-                y_tap = hip.op_conv(dt, x, w, b, mode=hip.CONV_UP2P)
-            finally:
-                os.environ.pop("NOPE_UP2P_HALO")
+                with switches(NOPE_UP2P_HALO=0):
+                    y_tap = hip.op_conv(dt, x, w, b, mode=hip.CONV_UP2P)
             torch.cuda.synchronize()
             assert all(torch.equal(ys[0], y) for y in ys[1:]), ("not reproducible", dt, cin, cout, h)
             assert torch.equal(ys[0], y_tap), ("tap-resident phase convs != per-tap kernel", dt, cin, cout, h)
@@ -124,12 +122,11 @@ def test_pingpong_bit_identical_to_128_tile_kernel(gpu, dt):
         outs = {}
         # 0: 128 x 192 kernel; 3: ping-pong schedule everywhere (3x3 convs on the tap-resident kernel); 19: 3x3 convs per tap
         for pp in ("0", "3", "19"):
-            os.environ["NOPE_CONV_PP"] = pp
-            ys = [hip.op_conv(dt, s1, w, b, src2=s2, mode=mode) for _ in range(3)]
-            torch.cuda.synchronize()
-            assert all(torch.equal(ys[0], y) for y in ys[1:]), ("not reproducible", pp, c1, c2, cout, h, mode)
-            outs[pp] = ys[0]
-        os.environ.pop("NOPE_CONV_PP")
+            with switches(NOPE_CONV_PP=pp):
+                ys = [hip.op_conv(dt, s1, w, b, src2=s2, mode=mode) for _ in range(3)]
+                torch.cuda.synchronize()
+                assert all(torch.equal(ys[0], y) for y in ys[1:]), ("not reproducible", pp, c1, c2, cout, h, mode)
+                outs[pp] = ys[0]
         # (the 128-tile kernel runs the 4x4 shape position-major: the padding taps it skips only ever add exact zeros)
         assert torch.equal(outs["0"], outs["3"]), ("ping-pong / tap-resident != 128-tile kernel", c1, c2, cout, h, mode, ks)
         assert torch.equal(outs["0"], outs["19"]), ("per-tap ping-pong != 128-tile kernel", c1, c2, cout, h, mode, ks)
@@ -138,8 +135,7 @@ def test_pingpong_bit_identical_to_128_tile_kernel(gpu, dt):
             # the epilogue without a residual (bf16: packed two-rows-per-dword panel) against the one with (f32 panel), and
             # workgroups walking several tiles against one tile per workgroup
             y0 = hip.op_conv(dt, s1, w, b, src2=s2, mode=mode, resid=torch.zeros_like(outs["3"]))
-            os.environ["NOPE_HALO_PERSIST"] = "0"
-            y1 = hip.op_conv(dt, s1, w, b, src2=s2, mode=mode)
-            os.environ.pop("NOPE_HALO_PERSIST")
+            with switches(NOPE_HALO_PERSIST=0):
+                y1 = hip.op_conv(dt, s1, w, b, src2=s2, mode=mode)
             assert torch.equal(outs["3"], y0), ("epilogue panels differ", c1, c2, cout, h, ks)
             assert torch.equal(outs["3"], y1), ("tile walk differs", c1, c2, cout, h, ks)

@@ -58,15 +58,18 @@ def coverage_gaps(text):
         case, plan, ans = line.split(" | ")
         err, splitk = _field(ans, r"err (-?\d+) stat_rows \d+ splitk (\d+)")
         seen.add(f"err {err}")
+        tail = re.search(r" gn \d+,\d$", case) is not None      # a launch with a GroupNorm tail (ConvArgs::gn_*)
         if err:
+            if tail:
+                seen.add("tail refused")
             continue
         kind, = _field(plan, r" kind (\d) ")
         xcd, = _field(plan, r" xcd (\d)/")
         persist, = _field(plan, r" persist (\d+),")
         splits, = _field(plan, r" splits (\d+) ")
-        reduce_, = _field(plan, r" reduce (\d)$")
+        reduce_, = _field(plan, r" reduce (\d)(?: gn_G .*)?$")
         mode, = _field(plan, r" mode (\d) ")
-        ws, = _field(case, r" ws (\d)$")
+        ws, = _field(case, r" ws (\d)(?: gn \d+,\d)?$")
         seen.update({f"kind {kind}", f"xcd_map {xcd}", "lean %d" % _field(plan, r" lean (\d)")})
         if " posmajor 1 " in plan:
             seen.add("posmajor")
@@ -80,6 +83,8 @@ def coverage_gaps(text):
             seen.add("x2 phase convs tap-resident" if (kind, mode) == (3, 3) else f"x2 on kind {kind}")
         if " geglu 1 " in plan:
             seen.add("geglu")
+        if tail and " gn_G " in plan:
+            seen.add("tail")
         if ws == 2 and splitk > 1 and splits == 1:
             seen.add("downgraded: split-K scratch short")
     want = ([f"kind {k}" for k in range(6)] + [f"xcd_map {m}" for m in range(5)] + ["posmajor", "lean 0", "lean 1", "nchw_staged", "geglu"] +
@@ -88,6 +93,7 @@ def coverage_gaps(text):
             # (conv_splitk_factor never splits a launch that emits statistics unless the tap-resident split applies: plain reduce only)
             ["splits on kind 3 reduce 1", "splits on kind 3 reduce 2", "splits on kind 1 reduce 1"] +
             ["x2 on kind 3", "x2 on kind 2", "x2 phase convs tap-resident"] +      # two-pass tile: tap-resident, per tap, the phase convs of an up-sampling
+            ["tail", "tail refused"] +      # GroupNorm tail: one launch that carries it, one that is refused rather than run without it
             ["downgraded: split-K scratch short", "err 0", "err -1", "err -6"])     # (NOPE_ERR_ARG, NOPE_ERR_UNSUPPORTED: all conv_plan returns)
     return [w for w in want if w not in seen]
 

@@ -11,6 +11,8 @@ import os
 import pytest
 import torch
 
+from tests.util import switches
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -55,13 +57,11 @@ def test_small_tile_bit_identical_to_128_tile_kernel(gpu, dt):
         b = torch.randn(cout, device="cuda", generator=g)
         outs = {}
         for small, tile in (("0", "0"), ("2", "0"), ("2", "1"), ("2", "2")):
-            os.environ["NOPE_CONV_SMALL"], os.environ["NOPE_SMALL_TILE"], os.environ["NOPE_CONV_PP"] = small, tile, "0"
-            ys = [hip.op_conv(dt, s1, w, b, src2=s2, mode=mode) for _ in range(3)]
-            torch.cuda.synchronize()
-            assert all(torch.equal(ys[0], y) for y in ys[1:]), ("not reproducible", small, tile, c1, c2, cout, h, mode)
-            outs[(small, tile)] = ys[0]
-        for k in ("NOPE_CONV_SMALL", "NOPE_SMALL_TILE", "NOPE_CONV_PP"):
-            os.environ.pop(k)
+            with switches(NOPE_CONV_SMALL=small, NOPE_SMALL_TILE=tile, NOPE_CONV_PP=0):
+                ys = [hip.op_conv(dt, s1, w, b, src2=s2, mode=mode) for _ in range(3)]
+                torch.cuda.synchronize()
+                assert all(torch.equal(ys[0], y) for y in ys[1:]), ("not reproducible", small, tile, c1, c2, cout, h, mode)
+                outs[(small, tile)] = ys[0]
         for k, y in outs.items():
             assert torch.equal(outs[("0", "0")], y), ("small-tile kernel != 128-tile kernel", k, c1, c2, cout, h, mode, ks)
         assert bool(torch.isfinite(outs[("2", "0")].float()).all()) and float(outs[("2", "0")].float().abs().max()) > 0.1

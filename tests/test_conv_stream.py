@@ -46,7 +46,7 @@ def test_lean_epilogue_whole_step_bit_identical(gpu):
     import torch
     from nope_amd.u_net import UNet
     from nope_amd.weights import synth_init_
-    from tests.util import StubEncoder
+    from tests.util import StubEncoder, switches
     for cdt in ("bf16x3", "f16x2"):
         u = UNet(u_net_dim=192, rot_representation_dim=6, encoder=StubEncoder(8), pose_mlp_name="single_layer", compute_dtype=cdt)
         synth_init_(u, 2022)
@@ -55,7 +55,6 @@ def test_lean_epilogue_whole_step_bit_identical(gpu):
         x, pose = torch.randn(1, 8, 32, 32, generator=g).cuda(), torch.randn(1, 64, 6, generator=g).cuda()
         outs = []
         for lean in ("0", "1"):
-            os.environ["NOPE_EPILOGUE_LEAN"] = lean
-            outs.append(u.forward_hypotheses(x, pose).clone())
-        os.environ.pop("NOPE_EPILOGUE_LEAN")
+            with switches(NOPE_EPILOGUE_LEAN=lean):
+                outs.append(u.forward_hypotheses(x, pose).clone())
         assert bool(torch.isfinite(outs[0]).all()) and torch.equal(outs[0], outs[1]), cdt

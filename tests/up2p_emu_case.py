@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "hipemu"))
 import torch
 import torch.nn.functional as F
 
-from tests.util import rel
+from tests.util import rel, switches
 from tests.x2_emu_case import X2, up2p_conv, up2p_phase_weights, x2_reference
 
 BF16X3 = 3
@@ -24,22 +24,19 @@ def launch_trace(fn):
     import tempfile
     sys.stderr.flush()
     saved = os.dup(2)
-    os.environ["NOPE_CONV_TRACE"] = "1"
     with tempfile.TemporaryFile(mode="w+b") as f:
         os.dup2(f.fileno(), 2)
         try:
-            out = fn()
+            with switches(NOPE_CONV_TRACE=1):
+                out = fn()
         finally:
             os.dup2(saved, 2)
             os.close(saved)
-            os.environ.pop("NOPE_CONV_TRACE")
         f.seek(0)
         return out, f.read().decode(errors="replace")
 
 
 def run(hip, dev, light=False):
-    os.environ["NOPE_CONV_PP"] = "13"          # ping-pong kernels at any tile count
-    os.environ["NOPE_UP2P_HALO"] = "2"         # (the default, 1, takes the tap-resident form for f16x2 layers only: measured flat for bf16x3)
     g = torch.Generator().manual_seed(314)
     rn = lambda *s: torch.randn(*s, generator=g)
     d = lambda t: t.to(dev)
@@ -49,16 +46,16 @@ def run(hip, dev, light=False):
     shapes = [(3, C, 5, 6, 40), (3, 2 * C, 10, 9, 200), (40, 3 * C, 4, 4, 24), (1, 2 * C, 9, 30, 16)]
     if light:
         shapes = shapes[1:2]       # two chunks (both A stages, the last-chunk path), ragged M, two weight panels
-    try:
+    # ping-pong kernels at any tile count; NOPE_UP2P_HALO: the default, 1, takes the tap-resident form for f16x2 layers only (measured flat for bf16x3)
+    with switches(NOPE_CONV_PP=13, NOPE_UP2P_HALO=2):
         for n, c, h, w_, co in shapes:
             x, w, b = rn(n, c, h, w_), rn(co, c, 3, 3) / (3 * c ** 0.5), rn(co)
             want32 = F.conv2d(F.interpolate(x, scale_factor=2, mode="nearest"), w, b, padding=1)
             for dt in (BF16X3, X2):
                 y, tr = launch_trace(lambda: hip.op_conv(dt, hip.to_nhwc(d(x), 0), d(w), d(b), mode=hip.CONV_UP2P))
                 assert "conv halo256 mode 3" in tr, ("the plan did not pick the tap-resident kernel", tr)
-                os.environ["NOPE_UP2P_HALO"] = "0"
-                y_tap = hip.op_conv(dt, hip.to_nhwc(d(x), 0), d(w), d(b), mode=hip.CONV_UP2P)
-                os.environ["NOPE_UP2P_HALO"] = "2"
+                with switches(NOPE_UP2P_HALO=0):
+                    y_tap = hip.op_conv(dt, hip.to_nhwc(d(x), 0), d(w), d(b), mode=hip.CONV_UP2P)
                 assert torch.equal(y, y_tap), ("tap-resident phase convs differ from the per-tap kernel", dt, n, c, h, w_, co,
                                                float((y - y_tap).abs().max()))
                 yy = hip.to_nchw(y, 0).cpu()
@@ -74,9 +71,6 @@ def run(hip, dev, light=False):
         y0 = hip.op_conv(X2, hip.to_nhwc(d(xr), 0), d(wr), None, mode=hip.CONV_UP2P)
         y12 = hip.op_conv(X2, hip.to_nhwc(d(xr * 4096.0), 0), d(wr), None, mode=hip.CONV_UP2P, x2_shift=12)
         assert torch.equal(y12, y0 * 4096.0), "phase convs: range shift 12 is not an exact rescaling"
-    finally:
-        os.environ.pop("NOPE_CONV_PP", None)
-        os.environ.pop("NOPE_UP2P_HALO", None)
     return worst
 
 

@@ -1,3 +1,6 @@
+import contextlib
+import os
+
 import torch
 from torch import nn
 
@@ -7,6 +10,27 @@ from nope_amd.harness import StubEncoder  # noqa: F401  (re-exported: the tests'
 
 def rel(a, b):
     return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-30))
+
+
+@contextlib.contextmanager
+def switches(**kw):
+    """`with switches(NOPE_CONV_PP=13, NOPE_XCD_GN=None):` -- the named NOPE_* variables set (values through str(); None = unset) inside the
+    block, and on the way out, an exception included, exactly what was there before.  Nests.  (nope_amd.hip.lib() notices any change of
+    os.environ and has the library read its switches again, so nothing else is needed.)"""
+    assert all(k.startswith("NOPE_") for k in kw), kw
+    old = {k: os.environ.get(k) for k in kw}
+
+    def put(values):
+        for k, v in values.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+    put(kw)
+    try:
+        yield
+    finally:
+        put(old)
 
 
 # Regression bounds per compute mode, (embedding maps, similarity scores), relative to the tensor's largest magnitude: ~3x what an MI355X

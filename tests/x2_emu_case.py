@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "hipemu"))
 import torch
 import torch.nn.functional as F
 
-from tests.util import rel
+from tests.util import rel, switches
 
 X2 = 4                      # hip.F16X2
 A_LO_SHIFT, A_SHIFT, W_LO_EXTRA = 9, -2, 11      # nope_common.h: kX2ALoShift, kX2AShift, kX2WLoExtra
@@ -66,7 +66,6 @@ def up2p_conv(a, wp):
 
 
 def run(hip, dev, light=False):
-    os.environ["NOPE_CONV_PP"] = "13"          # ping-pong kernels at any tile count
     g = torch.Generator().manual_seed(91)
     rn = lambda *s: torch.randn(*s, generator=g)
     d = lambda t: t.to(dev)
@@ -84,7 +83,7 @@ def run(hip, dev, light=False):
         worst = max(worst, e_exact / 2e-6, e32 / 3e-5)
         assert e_exact < 2e-6, (what, "vs the restated arithmetic", e_exact)
         assert e32 < 3e-5, (what, "vs the f32 convolution", e32)
-    try:
+    with switches(NOPE_CONV_PP=13):            # ping-pong kernels at any tile count
         # concat of two sources, ragged M (270 rows = 2 tiles), two N tiles, bias: chunks from both sources
         x1, x2 = rn(3, C, 10, 9), rn(3, C, 10, 9)
         w, b = rn(200, 2 * C, 3, 3) / 30, rn(200)
@@ -128,15 +127,11 @@ def run(hip, dev, light=False):
             xq, wq, bq = rn(64, 4 * C, 8, 8), rn(200, 4 * C, 3, 3) / (3 * (4 * C) ** 0.5), rn(200)
             y0 = hip.op_conv(X2, hip.to_nhwc(d(xq), 0), d(wq), d(bq))
             chk(y0, xq, wq, bq, "halo 64 x 8x8, 4 chunks")
-            os.environ["NOPE_CONV_PP"] = "11"
-            os.environ["NOPE_HALO_PERSIST"] = "16"
-            y1 = hip.op_conv(X2, hip.to_nhwc(d(xq), 0), d(wq), d(bq))
-            os.environ.pop("NOPE_HALO_PERSIST")
-            os.environ["NOPE_CONV_PP"] = "13"
+            with switches(NOPE_CONV_PP=11, NOPE_HALO_PERSIST=16):
+                y1 = hip.op_conv(X2, hip.to_nhwc(d(xq), 0), d(wq), d(bq))
             assert torch.equal(y0, y1), "walking workgroups differ from one tile per workgroup"
-            os.environ["NOPE_HALO_SPLIT_MIN_CHUNKS"] = "2"
-            y2 = hip.op_conv(X2, hip.to_nhwc(d(xq[:8]), 0), d(wq), d(bq), split_k=True)
-            os.environ.pop("NOPE_HALO_SPLIT_MIN_CHUNKS")
+            with switches(NOPE_HALO_SPLIT_MIN_CHUNKS=2):
+                y2 = hip.op_conv(X2, hip.to_nhwc(d(xq[:8]), 0), d(wq), d(bq), split_k=True)
             chk(y2, xq[:8], wq, bq, "halo split-K")
         # ---- the per-tap kernel (operand split in registers): 1x1 over a concat of two sources (two K steps, one per source), ragged M and N
         w1, b1 = rn(200, 2 * C, 1, 1) / 8, rn(200)
@@ -159,14 +154,12 @@ def run(hip, dev, light=False):
             y = hip.op_conv(X2, hip.to_nhwc(d(xp), 0), d(wp_), d(bp))
             chk(y, xp, wp_, bp, "per-tap 3x3, position-major")
         # a launch no ping-pong kernel takes (here: too few tiles under the default plan): the element type refuses it
-        os.environ.pop("NOPE_CONV_PP")
-        try:
-            hip.op_conv(X2, hip.to_nhwc(d(x2), 0), d(rn(24, C, 1, 1)), None)
-            raise AssertionError("NOPE_F16X2 accepted a launch that runs on the small-tile kernel")
-        except hip.NopeError:
-            pass
-    finally:
-        os.environ.pop("NOPE_CONV_PP", None)
+        with switches(NOPE_CONV_PP=None):
+            try:
+                hip.op_conv(X2, hip.to_nhwc(d(x2), 0), d(rn(24, C, 1, 1)), None)
+                raise AssertionError("NOPE_F16X2 accepted a launch that runs on the small-tile kernel")
+            except hip.NopeError:
+                pass
     return worst
 
 
@@ -180,11 +173,8 @@ def run_unet_range(hip, dev, dim=64, n_hyp=5, hw=16, scales=(1.0, 1e2, 1e3, 1e4,
     from nope_amd.weights import synth_init_
     from oracle import nope_ref as R
     from tests.util import StubEncoder
-    os.environ["NOPE_CONV_PP"] = "9"
-    saved_mode = os.environ.get("NOPE_X2_RANGE_CHECK")
-    os.environ["NOPE_X2_RANGE_CHECK"] = "2"         # range_mode "repeat": synchronise, read the verdict, issue the forward again (hip.UNetHandle)
     out = []
-    try:
+    with switches(NOPE_CONV_PP=9, NOPE_X2_RANGE_CHECK=2):      # range_mode "repeat": synchronise, read the verdict, issue the forward again (hip.UNetHandle)
         u = UNet(u_net_dim=dim, rot_representation_dim=6, encoder=StubEncoder(8), pose_mlp_name="single_layer", compute_dtype="f16x2")
         synth_init_(u, 2022)
         sd = {k: v.clone() for k, v in u.own_state_dict().items()}
@@ -216,12 +206,6 @@ def run_unet_range(hip, dev, dim=64, n_hyp=5, hw=16, scales=(1.0, 1e2, 1e3, 1e4,
         assert any(ev["attempt"] == -1 for ev in h.range_events[n0:]), "the next forward reports the verdict"
         out.append((S, rel(y2, want), h.range_events[n0:], h.x2_enabled))
         return out
-    finally:
-        os.environ.pop("NOPE_CONV_PP")
-        if saved_mode is None:
-            os.environ.pop("NOPE_X2_RANGE_CHECK", None)
-        else:
-            os.environ["NOPE_X2_RANGE_CHECK"] = saved_mode
 
 
 def run_unet(hip, dev, dim=64, n_hyp=5, hw=16):
@@ -230,8 +214,7 @@ def run_unet(hip, dev, dim=64, n_hyp=5, hw=16):
     from nope_amd.weights import synth_init_
     from oracle import nope_ref as R
     from tests.util import StubEncoder
-    os.environ["NOPE_CONV_PP"] = "9"       # ping-pong kernels (tap-resident for the 3x3 convs) at any tile count
-    try:
+    with switches(NOPE_CONV_PP=9):         # ping-pong kernels (tap-resident for the 3x3 convs) at any tile count
         u = UNet(u_net_dim=dim, rot_representation_dim=6, encoder=StubEncoder(8), pose_mlp_name="single_layer", compute_dtype="f16x2")
         synth_init_(u, 2022)
         sd = {k: v.clone() for k, v in u.own_state_dict().items()}
@@ -241,8 +224,6 @@ def run_unet(hip, dev, dim=64, n_hyp=5, hw=16):
         y = u.forward_hypotheses(x.to(dev), pose.to(dev)).cpu()[0]
         want = R.unet_forward(sd, x.expand(n_hyp, -1, -1, -1), pose[0])
         return rel(y, want)
-    finally:
-        os.environ.pop("NOPE_CONV_PP")
 
 
 if __name__ == "__main__":
