@@ -90,9 +90,10 @@ typedef void* nope_stream_t;
  * 16: nope_op_conv_gn_tail, nope_op_conv_tail_stat_blocks;
  * 17: nope_conv_op / nope_op_conv / nope_op_conv_query and nope_gn_op / nope_op_group_norm take their arguments by name and replace
  *     nope_op_conv_ws, nope_op_conv_ex, nope_op_conv_gn_tail, nope_op_conv_splitk_bytes, nope_op_conv_stat_rows, nope_op_conv_tail_stat_blocks,
- *     nope_op_group_norm_ex and nope_op_group_norm_shared).  Callers compare nope_abi_version() against the header they were
+ *     nope_op_group_norm_ex and nope_op_group_norm_shared);
+ * 18: nope_op_pose_modes.  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 17
+#define NOPE_ABI_VERSION 18
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -149,6 +150,36 @@ int nope_topk_merge(const float* cand_vals, const int64_t* cand_idx, int64_t* id
  *             bit 1 = an index outside [0, N). */
 int nope_op_geodesic(const double* poses, int64_t pose_stride_b, int N, const int64_t* idx, const double* gt, const int* symmetry,
                      double* err_rad, int* status, int B, int k, nope_stream_t stream);
+
+/* (ABI 18) Pose distribution and distinct pose modes from the retrieval scores.  No reference counterpart: the
+ * reference stops at `similarity.topk(k=5)` (src/model/model.py:265), one grid vertex and four of its neighbours.  One workgroup per query,
+ * no workspace, nothing read by the host, no floating-point atomics: bit-identical from run to run.
+ *   similarity      (B, N) f32, row stride similarity_ld >= N; columns >= N are never read
+ *   template_poses  (B|1, N, 3, 3) f64, sample stride pose_stride_b elements (0 = one grid for every query, as nope_op_geodesic)
+ *   symmetry        (B) int32 in {0, 1, 2} or NULL (all 0)
+ * Distribution, per row: p[n] = exp((s[n] - max s) / temperature) / Z and entropy = -sum p ln p (nats, 0 ln 0 = 0); exponentials, sums and
+ * the entropy in f64, rounded once to f32.  -inf is an ordinary score (p = 0, ranks last).  A row whose maximum is NaN or +-inf is
+ * undefined: its prob row and entropy are NaN, n_modes = 0, every slot mode_idx = -1 / mode_score = NaN / mode_mass = 0 / mode_count = 0,
+ * and *status (one device int, zeroed by the call) gets bit 0; the other rows are not affected.
+ * Modes, greedy suppression: all N templates start alive; slot m = 0, 1, ...: the seed is the alive template with the highest score (ties ->
+ * the lowest index, nope_topk's rule), its members are the alive templates n with d(poses[n], poses[seed]) <= radius_rad (the seed always, a
+ * NaN distance never); mode_idx = seed, mode_score = s[seed], mode_mass = sum of p over the members (f64 sum), mode_count = their number;
+ * the members leave.  It stops when nothing is alive; n_modes[b] = the slots filled this way.  Left-over slots: fill = 0: mode_idx = -1,
+ * mode_score = -inf, mass 0, count 0; fill = 1 (needs max_modes <= N): the best-scoring templates not yet listed, in nope_topk order, with
+ * mass 0 and count 0 -- a caller that needs exactly max_modes valid candidates always gets them.  max_modes = 0: the distribution only.
+ * The distance d is this op's own, f64: theta(A, B) = acos(clamp((tr(A B^T) - 1) / 2, -1, 1)); symmetry 0: theta(A, B); 1: min(theta(A, B),
+ * theta(diag(-1, 1, -1) A, B)); 2: the clamped acos of the cosine between the viewing axes -inv(P)[2, :] (norms floored at 1e-8).  Unlike
+ * nope_op_geodesic it does not reproduce the reference's f32 round trips, pytorch3d's linear extrapolation of acos (a self-distance of
+ * 0.0071 rad) or the unclamped acos of the circular branch (NaN between viewpoints of equal elevation): right for a reported metric, wrong
+ * for a membership decision.  The two differ by <= 0.0071 rad, near 0 and pi only.
+ *   prob (B, N) f32, row stride prob_ld, or NULL;  entropy (B) f32;  mode_idx (B, max_modes) int64;  mode_score, mode_mass (B, max_modes)
+ *   f32;  mode_count (B, max_modes) int32;  n_modes (B) int32.
+ * NOPE_ERR_ARG, before anything is launched or written: temperature not finite or not > 0; radius_rad NaN or < 0; max_modes outside
+ * [0, 64]; N < 1; fill with max_modes > N; a missing pointer.  The alive flags live in LDS: N <= 262144, NOPE_ERR_UNSUPPORTED beyond. */
+int nope_op_pose_modes(const float* similarity, int64_t similarity_ld, const double* template_poses, int64_t pose_stride_b, int N,
+                       const int* symmetry, double temperature, double radius_rad, int max_modes, int fill, float* prob, int64_t prob_ld,
+                       float* entropy, int64_t* mode_idx, float* mode_score, float* mode_mass, int* mode_count, int* n_modes, int* status,
+                       int B, nope_stream_t stream);
 
 /* (ABI 15) Sub-grid pose refinement: Gauss-Newton on SO(3) through the U-Net.  No reference counterpart: the reference's prediction is
  * template_poses[nearest_idx] (src/model/model.py:352-354), a vertex of the template grid (26 templates: ~32 degrees apart).  The U-Net is a

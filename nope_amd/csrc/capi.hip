@@ -121,6 +121,15 @@ int nope_op_geodesic(const double* poses, int64_t pose_stride_b, int N, const in
     return launch_geodesic(poses, (long long)pose_stride_b, N, (const long long*)idx, gt, symmetry, err_rad, status, B, k, (hipStream_t)stream);
 }
 
+int nope_op_pose_modes(const float* similarity, int64_t similarity_ld, const double* template_poses, int64_t pose_stride_b, int N,
+                       const int* symmetry, double temperature, double radius_rad, int max_modes, int fill, float* prob, int64_t prob_ld,
+                       float* entropy, int64_t* mode_idx, float* mode_score, float* mode_mass, int* mode_count, int* n_modes, int* status,
+                       int B, nope_stream_t stream) {
+    return launch_pose_modes(similarity, (long long)similarity_ld, template_poses, (long long)pose_stride_b, N, symmetry, temperature, radius_rad,
+                             max_modes, fill, prob, (long long)prob_ld, entropy, (long long*)mode_idx, mode_score, mode_mass, mode_count, n_modes,
+                             status, B, (hipStream_t)stream);
+}
+
 int nope_op_refine_init(const float* all_relativeR, int64_t N, const int64_t* idx, double* dR, double* dR_init, float* poses, int* status,
                         int B, int k, double fd_step, nope_stream_t stream) {
     return launch_refine_init(all_relativeR, (long long)N, (const long long*)idx, dR, dR_init, poses, status, B, k, fd_step, (hipStream_t)stream);

@@ -529,6 +529,11 @@ int launch_topk(const float* scores, long long* idx, float* vals, int B, int N, 
 int launch_gather_topk(const float* gathered, int G, int B, int N, float* scores, long long* idx, float* vals, int k, hipStream_t s);
 int launch_geodesic(const double* poses, long long stride_b, int N, const long long* idx, const double* gt, const int* symmetry,
                     double* err, int* status, int B, int k, hipStream_t s);
+// pose distribution and distinct modes (kernels_modes.hip)
+int launch_pose_modes(const float* sim, long long sim_ld, const double* poses, long long stride_b, int N, const int* symmetry,
+                      double temperature, double radius_rad, int max_modes, int fill, float* prob, long long prob_ld, float* entropy,
+                      long long* mode_idx, float* mode_score, float* mode_mass, int* mode_count, int* n_modes, int* status, int B,
+                      hipStream_t s);
 // sub-grid pose refinement (kernels_refine.hip)
 int launch_refine_init(const float* all_rel, long long N, const long long* idx, double* dR, double* dR0, float* poses, int* status, int B, int k,
                        double h, hipStream_t s);

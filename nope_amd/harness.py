@@ -144,13 +144,17 @@ def geodesic_deg(predR: torch.Tensor, gtR: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False,
-                  errors_out: Optional[list] = None, refine_iters: int = 0):
+                  errors_out: Optional[list] = None, refine_iters: int = 0, distinct_deg: Optional[float] = None, temperature: float = 1.0):
     """The body of PoseConditional.eval_geodesic (model.py:268-376).  visualize (effective with a decoding encoder and model.save_dir only,
     model.py:269-274; needs batch["gt_templates"] (B, N, 3, S, S)): the three kinds of pictures and the video under save_dir/media
     (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions.  errors_out: a list that
     receives this batch's (B,) top-1 errors in degrees (run_split pools them over a split).  refine_iters > 0 (no reference counterpart): the
     retrieved candidates are refined below the grid spacing (PoseConditional.refine) and scored as well: the same metric keys under a
-    "refined/" prefix, and `refined_relR` (B, k, 3, 3) in the saved predictions; at 0 nothing changes."""
+    "refined/" prefix, and `refined_relR` (B, k, 3, 3) in the saved predictions; at 0 nothing changes.  distinct_deg (no reference counterpart
+    either; None: nothing changes): the distinct pose modes of the scores within that radius (hip.op_pose_modes at `temperature`, the batch's
+    symmetry classes) are scored as well -- the same metric keys under "modes/", computed on the mode seeds, plus the batch means
+    "modes/entropy" (nats) and "modes/n_modes"; with refine_iters > 0 the refinement starts from the mode seeds as well and reports under
+    "modes_refined/"; the saved predictions gain `mode_idx`, `mode_mass` and `entropy`."""
     visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
     if visualize and "gt_templates" not in batch:
         raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
@@ -187,6 +191,18 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
         res.update({f"refined/{k}": float(v) for k, v in refined.items()})
         if save_path:
             extra["refined_relR"] = ref.relR.cpu().numpy()
+    if distinct_deg is not None:
+        modes = hip.op_pose_modes(similarity, batch["template_poses"][:1], sym, temperature=temperature, radius_deg=distinct_deg,
+                                  max_modes=nearest_idx.shape[1], fill=True, want_prob=False)
+        _, m_metric = GeodesicError(list(thresholds)).from_indices(batch["template_poses"][:1], modes.idx, batch["query_pose"], sym)
+        res.update({f"modes/{k}": float(v) for k, v in m_metric.items()})
+        res["modes/entropy"], res["modes/n_modes"] = float(modes.entropy.mean()), float(modes.n_modes.float().mean())
+        if refine_iters > 0:
+            ref = model.refine(query, reference, batch["all_relativeR"], modes.idx, similarity, iters=refine_iters, template_poses=batch["template_poses"][:1])
+            _, refined = GeodesicError(list(thresholds))._topk_result(hip.op_geodesic(ref.pred_R, batch["query_pose"], sym))
+            res.update({f"modes_refined/{k}": float(v) for k, v in refined.items()})
+        if save_path:
+            extra.update(mode_idx=modes.idx.cpu().numpy(), mode_mass=modes.mass.cpu().numpy(), entropy=modes.entropy.cpu().numpy())
     if save_path:
         if visualize:       # model.py:334-339,367-375: the un-resized grid of the last picture
             extra["vis_imgs"] = hip.op_vis_grid(retrieved)[0].cpu().numpy()
@@ -259,10 +275,13 @@ def main(argv=None):
     ap.add_argument("--u-net-dim", type=int, default=None, help="with --data-root: U-Net width (default: template_base.yaml's 192)")
     ap.add_argument("--refine", type=int, default=0, metavar="ITERS",
                     help="refine the retrieved poses with ITERS Gauss-Newton iterations through the U-Net and print their scores as well (refined/...)")
+    ap.add_argument("--distinct-deg", type=float, default=None, metavar="D",
+                    help="also score the distinct pose modes of the similarity within D degrees (modes/...: their seeds, the entropy, the mode count)")
+    ap.add_argument("--temperature", type=float, default=1.0, metavar="T", help="with --distinct-deg: the softmax temperature, in score units")
     a = ap.parse_args(argv)
     if a.data_root:
-        if a.refine:
-            ap.error("--refine applies to the synthetic batch (a split's pooled scores are not refined)")
+        if a.refine or a.distinct_deg is not None:
+            ap.error("--refine / --distinct-deg apply to the synthetic batch (a split's pooled scores carry neither)")
         return main_dataset(a, ap)
     a.size = a.size or 128
     if a.visualize and (a.encoder != "vae" or not a.save_dir):
@@ -275,7 +294,8 @@ def main(argv=None):
     for name, batch in batches.items():                         # test_step, model.py:550-565
         t0 = time.time()
         save = os.path.join(a.save_dir, "predictions", f"pred_step0_rank{model.global_rank}") if a.save_dir else None
-        sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize, refine_iters=a.refine)
+        sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize, refine_iters=a.refine, distinct_deg=a.distinct_deg,
+                                      temperature=a.temperature)
         torch.cuda.synchronize()
         res.update(dataloader=name, seconds=time.time() - t0, nearest_idx=idx.tolist())
         print(json.dumps(res))

@@ -7,15 +7,16 @@ missing (not built) the import of anything that computes fails with a clear erro
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 17                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 18                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -110,6 +111,7 @@ _PROTOS = {
     "nope_gather_topk": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "nope_topk_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_geodesic": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "nope_op_pose_modes": (_i, [_vp, _i64, _vp, _i64, _i, _vp, C.c_double, C.c_double, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "nope_op_refine_init": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp]),
     "nope_op_refine_normal_eq_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nope_op_refine_normal_eq": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _sz, _vp]),
@@ -432,6 +434,61 @@ def op_geodesic(poses: torch.Tensor, gt: torch.Tensor, symmetry: Optional[torch.
         raise ValueError("A matrix has trace outside valid range [-1-eps,3+eps].")      # pytorch3d so3_rotation_angle's message
     return err
 
+
+class PoseModes(NamedTuple):
+    """op_pose_modes: prob (B, N) f32 or None, entropy (B,) f32 (nats), idx (B, max_modes) int64, score, mass (B, max_modes) f32,
+    count (B, max_modes) int32, n_modes (B,) int32.  An undefined row (NaN / +inf score, or all -inf) has n_modes 0 and a NaN entropy."""
+    prob: Optional[torch.Tensor]
+    entropy: torch.Tensor
+    idx: torch.Tensor
+    score: torch.Tensor
+    mass: torch.Tensor
+    count: torch.Tensor
+    n_modes: torch.Tensor
+
+
+def op_pose_modes(similarity: torch.Tensor, template_poses: torch.Tensor, symmetry: Optional[torch.Tensor] = None, *, temperature: float,
+                  radius_deg: float, max_modes: int = 5, fill: bool = False, want_prob: bool = True) -> PoseModes:
+    """The pose distribution of each score row -- softmax at `temperature` (score units) and its entropy -- and its distinct modes: greedy
+    suppression on the template grid within `radius_deg` under the sample's symmetry class (include/nope_hip.h: nope_op_pose_modes).
+    similarity (B, N) f32 (a view with inner stride 1 is read in place through its row stride), template_poses (B|1, N, 3, 3) of any float
+    dtype, symmetry (B,) / (B, 1) in {0, 1, 2}.  Everything follows the scores' device.  fill: left-over slots take the best templates not
+    yet listed (mass 0, count 0) instead of idx -1; needs max_modes <= N.  Nothing is read by the host."""
+    require_device(similarity)
+    if similarity.dim() != 2:
+        raise NopeError(f"similarity {tuple(similarity.shape)}: expected (B, N)")
+    if similarity.dtype != torch.float32 or (similarity.shape[1] > 1 and similarity.stride(1) != 1) or \
+            (similarity.shape[0] > 1 and similarity.stride(0) < similarity.shape[1]):
+        similarity = _f32c(similarity)
+    B, N = similarity.shape
+    ld = similarity.stride(0) if B > 1 else N
+    dev = similarity.device
+    poses = template_poses.to(device=dev, dtype=torch.float64).contiguous()
+    if poses.dim() != 4 or tuple(poses.shape[2:]) != (3, 3) or poses.shape[0] not in (1, B) or poses.shape[1] != N:
+        raise NopeError(f"template_poses {tuple(poses.shape)}: expected (B|1, N, 3, 3) for similarity {(B, N)}")
+    sym = None if symmetry is None else symmetry.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    if sym is not None and sym.numel() != B:
+        raise NopeError(f"symmetry has {sym.numel()} entries for {B} samples")
+    max_modes = int(max_modes)
+    prob = torch.empty((B, N), dtype=torch.float32, device=dev) if want_prob else None
+    out = PoseModes(prob, torch.empty(B, dtype=torch.float32, device=dev), torch.empty((B, max(max_modes, 0)), dtype=torch.int64, device=dev),
+                    torch.empty((B, max(max_modes, 0)), dtype=torch.float32, device=dev), torch.empty((B, max(max_modes, 0)), dtype=torch.float32, device=dev),
+                    torch.empty((B, max(max_modes, 0)), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    if B == 0:
+        return out
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    stride_b = 0 if (poses.shape[0] == 1 and B > 1) else N * 9
+    return _pose_modes_call(similarity, ld, poses, stride_b, N, sym, temperature, math.radians(radius_deg), max_modes, fill, out, status)
+
+
+def _pose_modes_call(similarity, ld, poses, stride_b, N, sym, temperature, radius_rad, max_modes, fill, out: PoseModes, status) -> PoseModes:
+    """The launch of op_pose_modes into given outputs (the argument tests pre-fill them)."""
+    l = lib()
+    l.check(l.dll.nope_op_pose_modes(_ptr(similarity), ld, _ptr(poses), stride_b, N, _ptr(sym), float(temperature), float(radius_rad),
+                                     int(max_modes), int(bool(fill)), _ptr(out.prob), N, _ptr(out.entropy), _ptr(out.idx), _ptr(out.score),
+                                     _ptr(out.mass), _ptr(out.count), _ptr(out.n_modes), _ptr(status), similarity.shape[0],
+                                     _stream(similarity)), "nope_op_pose_modes")
+    return out
 
 
 # --------------------------------------------------------------------------------------------

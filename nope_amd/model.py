@@ -368,13 +368,30 @@ class PoseConditional(nn.Module):
         return self.refine_from_feat(query_feat, reference_feat, all_relativeR, nearest_idx, similarity, **kw)
 
     @torch.no_grad()
-    def predict_pose(self, query, reference, all_relativeR, template_poses, refine_iters=0, **kw):
+    def pose_distribution(self, similarity, template_poses, symmetry=None, temperature=1.0, radius_deg=15.0, max_modes=5):
+        """The retrieval scores as a distribution over the template grid, and its distinct modes (hip.op_pose_modes, DESIGN.md section
+        4.10): a PoseModes with prob (B,N), entropy (B,) in nats, and per mode idx / score / mass / count (B,max_modes) and n_modes (B,).
+        A symmetric or otherwise ambiguous object shows as several modes of comparable mass and a high entropy.  similarity (B,N) as
+        `retrieval` returns it (under template_parallel: the full matrix every rank holds), template_poses (B|1,N,3,3), symmetry (B,) in
+        {0,1,2} (loss.py's classes).  `temperature` is in SCORE units, and a score is a sum over the h*w latent pixels (model.py:257-262),
+        so the useful scale grows with the latent size.  No default here is tuned -- neither the temperature nor radius_deg (choose it
+        from the grid: above its vertex spacing): there are no trained weights to tune them on."""
+        return hip.op_pose_modes(similarity, template_poses, symmetry, temperature=temperature, radius_deg=radius_deg, max_modes=max_modes)
+
+    @torch.no_grad()
+    def predict_pose(self, query, reference, all_relativeR, template_poses, refine_iters=0, distinct_deg=None, symmetry=None, temperature=1.0,
+                     **kw):
         """(pred_R (B,k,3,3) f64, score (B,k) f32): the k best poses of the query.  refine_iters = 0: template_poses[nearest_idx]
         (model.py:352-354) and the retrieval scores; above 0: those candidates refined below the grid spacing (refine_from_feat, whose
-        keyword arguments pass through), in ITS order.  template_poses (B|1,N,3,3).  None for a metric the reference does not implement."""
+        keyword arguments pass through), in ITS order.  template_poses (B|1,N,3,3).  None for a metric the reference does not implement.
+        distinct_deg (None: the plain top-k, every output as without the argument): the k = 5 candidates are the seeds of the distinct
+        modes within that radius under `symmetry` (op_pose_modes with fill: always k valid candidates), not a vertex and its neighbours."""
         if self.similarity_metric != "l2":
             return None
         similarity, nearest_idx, _, query_feat, reference_feat = self._encode_generate_retrieve(query, reference, all_relativeR)
+        if distinct_deg is not None:
+            nearest_idx = hip.op_pose_modes(similarity, template_poses, symmetry, temperature=temperature, radius_deg=distinct_deg,
+                                            max_modes=nearest_idx.shape[1], fill=True, want_prob=False).idx
         if refine_iters <= 0:
             tp = template_poses.to(device=nearest_idx.device, dtype=torch.float64)
             rows = torch.arange(nearest_idx.shape[0], device=nearest_idx.device)[:, None] if tp.shape[0] != 1 else 0
