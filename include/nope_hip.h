@@ -91,9 +91,10 @@ typedef void* nope_stream_t;
  * 17: nope_conv_op / nope_op_conv / nope_op_conv_query and nope_gn_op / nope_op_group_norm take their arguments by name and replace
  *     nope_op_conv_ws, nope_op_conv_ex, nope_op_conv_gn_tail, nope_op_conv_splitk_bytes, nope_op_conv_stat_rows, nope_op_conv_tail_stat_blocks,
  *     nope_op_group_norm_ex and nope_op_group_norm_shared);
- * 18: nope_op_pose_modes.  Callers compare nope_abi_version() against the header they were
+ * 18: nope_op_pose_modes;
+ * 19: nope_conv_op gains gn_emb, gn_emb_stride, gn_self, gn_resid_rep (the conv's own GroupNorm).  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 18
+#define NOPE_ABI_VERSION 19
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -572,6 +573,17 @@ typedef struct nope_conv_op {
     float* tail_stats;         /* [n_hyp][nope_conv_op_info.tail_stat_blocks][2] or NULL: (sum, sum of squares) of the values written per 64-row x
                                 * 96-column tile, for nope_op_gn_finalize */
     uint32_t* amax_slot; float* amax_out;      /* RANGE SLOTS above */
+    /* The conv's OWN GroupNorm (gn_self = 1, with gn_gamma / gn_beta / gn_G / gn_eps; gn_ms, tail_colstats, tail_stats, colstats, the PreNorm and
+     *   act_relu unset): a ResnetBlock's conv3x3 -> GroupNorm -> SiLU [-> + emb] [-> + x] in ONE launch,
+     *     out[m, n] = SiLU(GroupNorm(gn_G)(conv3x3(src1 [cat src2]) + bias)[m, n] gn_gamma[n] + gn_beta[n]) [+ gn_emb[sample of m][n]] [+ resid[m, n]],
+     *   the statistics formed inside the launch by the workgroup that owns the samples.  `resid` is added LAST here.  Same column sums, fold order
+     *   and arithmetic as the conv with `colstats` followed by nope_op_group_norm (fast_silu = 1, act_silu = 1, that colstats, emb, resid):
+     *   bit-identical to those two launches.  NOPE_BF16X3 / NOPE_F16X2 only, and only a launch the policy in force puts on the tap-resident 3x3
+     *   kernel with the lean epilogue and no split-K, H W in {16, 64, 256}, n_hyp H W a multiple of 256, (Cout / gn_G) a multiple of 4 that divides
+     *   192, gn_resid_rep 0 or 1: NOPE_ERR_UNSUPPORTED otherwise -- never a launch without the GroupNorm, nothing launched for a refused combination. */
+    const float* gn_emb; int gn_emb_stride;      /* [n_hyp][gn_emb_stride] (columns [0, Cout) of row s) or NULL */
+    int gn_self;
+    int gn_resid_rep;          /* hypotheses that share a sample of resid under gn_self (0 reads as 1) */
 } nope_conv_op;
 /* amax_recorded (host int, may be NULL): 1 when this launch's kernel records max |out| (f32 storage, the wide NHWC epilogue of the
  * 128 x 192 / ping-pong / tap-resident kernels, no split-K), else 0: amax_out is then 0. */

@@ -58,9 +58,13 @@ static int conv_args(const nope_conv_op& op, ConvArgs& a) {
     a.pn_ms = op.pn_ms; a.pn_c0 = op.pn_c0; a.pn_c1 = op.pn_c1;
     a.gn_ms = op.gn_ms; a.gn_gamma = op.gn_gamma; a.gn_beta = op.gn_beta; a.gn_G = op.gn_G; a.tail_stats = op.tail_stats;
     a.out_amax = op.amax_slot;
+    if (op.gn_self) {      // the conv's own GroupNorm: resid is added behind it
+        a.gn_self = 1; a.gn_eps = op.gn_eps; a.gn_emb = op.gn_emb; a.gn_emb_stride = op.gn_emb_stride; a.gn_resid = op.resid; a.resid = nullptr;
+    }
     if (half && ((op.Hs | op.Ws) & 1)) return NOPE_ERR_ARG;
     if ((op.amax_slot != nullptr) != (op.amax_out != nullptr)) return NOPE_ERR_ARG;
-    if (op.gn_gamma && (!op.gn_ms || !op.tail_colstats)) return NOPE_ERR_ARG;      // (conv_plan takes a launch without gn_ms for one without the tail)
+    if (op.gn_gamma && !op.gn_self && (!op.gn_ms || !op.tail_colstats)) return NOPE_ERR_ARG;      // (conv_plan takes a launch without gn_ms for one without the tail)
+    if (op.gn_self && op.gn_resid_rep > 1) return NOPE_ERR_UNSUPPORTED;      // (the launch reads one residual sample per output sample)
     return NOPE_OK;
 }
 
@@ -204,7 +208,7 @@ int nope_op_conv(const nope_conv_op* op, int* amax_recorded, nope_stream_t strea
     hipStream_t s = (hipStream_t)stream;
     const ConvLaunch L = conv_plan(op->dtype, a);
     if (amax_recorded) *amax_recorded = L.p.out_amax ? 1 : 0;      // (of the launch that runs: a slot was given and its epilogue fills it)
-    if (op->gn_gamma) {      // the GroupNorm tail of the per-tap ping-pong kernel's lean epilogue, as Fwd::res_tail (unet_runtime.hip) launches it
+    if (op->gn_gamma && !op->gn_self) {      // the GroupNorm tail of the per-tap ping-pong kernel's lean epilogue, as Fwd::res_tail (unet_runtime.hip) launches it
         if (L.err != NOPE_OK) return L.err;      // (before the statistics launch: a refused combination launches nothing)
         if (const int e = launch_gn_colstats_finalize(op->tail_colstats, op->gn_ms, a.nhyp, op->tail_stat_blocks, a.Cout, a.gn_G, a.Hs * a.Ws,
                                                       op->gn_eps, s)) return e;

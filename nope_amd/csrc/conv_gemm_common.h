@@ -354,10 +354,23 @@ struct NoStamp { __device__ __forceinline__ void operator()() const {} };
 // wave tile and groups of whole 4-channel chunks): each residual vector r becomes SiLU(r a + b) on its way in -- gn_apply_kernel's coefficients and
 // its three lines of arithmetic, the same bits -- so a ResnetBlock's res_conv reads the raw output of block2's conv as its residual and stores the
 // block's output.  Its own instantiation again: the launches without a tail keep their code and their registers.
+// LEANM = 3 (the tap-resident kernel only: 256-row tiles of four wave rows, all eight waves of the workgroup here together; ConvParams::gn_self): the
+// lean row walk with the launch's OWN GroupNorm.  The launcher vouches that a tile holds whole samples (maps of 256, 64 or 16 pixels) and whole groups.
+// The column sums below go to LDS (SelfLds: [row blocks of the tile][192] sums and sums of squares) instead of ConvParams::colstats; behind one
+// workgroup barrier wave w forms (mean, rstd) of the (sample, group) pairs w, w + 8, ... with the fold and the group sum of kernels_norm.hip
+// (gn_fold_column, gn_group_sum, gn_mean_rstd: the same bits) into SelfLds::ms; behind a second one the row walk turns every panel vector v into
+// SiLU(v a + b) + emb [+ residual] -- gn_apply_kernel's coefficients and its lines of arithmetic in its order.  max |y| (out_amax) is taken of what
+// is stored.  Its own instantiation again.
+struct SelfLds { float* cs_s; float* cs_q; float* ms; };
 template <class T, bool PN, bool DRAIN = false, class Stamp = NoStamp, bool GG = false, int LEANM = 0>
 __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typename Tile<T>::acc_t (&acc)[Tile<T>::MT][Tile<T>::NTL],
                                               int m0, int n0, int wm, int wn, int lane, unsigned char* lds_wave, Stamp stamp = Stamp(),
-                                              float acc_scale = 1.0f) {
+                                              float acc_scale = 1.0f, SelfLds self = SelfLds()) {
+    constexpr bool SELF = LEANM == 3;
+    // (SELF: what only this form computes from the lane index -- LDS and coefficient addresses -- is computed from an opaque copy, per tile: hoisted out
+    //  of the tap-resident kernel's tile walk, across its K loop, these values spilled)
+    int lane_s = lane;
+    if constexpr (SELF) NOPE_OPAQUE_VGPR(lane_s);
     typedef Tile<T> TL;
     constexpr int VEC = Elt<T>::VEC;
     // NOPE_F16X2: the accumulators hold 2^-t x the convolution (t = the layer's activation range shift, nope_common.h: kX2*); acc_scale = 2^t
@@ -382,7 +395,7 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
     bool inrange[TL::NTL];              // f16 storage: this lane's values of column tile j are known to lie inside the format's range
 #pragma unroll
     for (int j = 0; j < TL::NTL; ++j) inrange[j] = false;
-    if (p.colstats && p.stat_rows == 16) {
+    if ((SELF || p.colstats) && p.stat_rows == 16) {
         // ... per 16-row block: maps of 16 pixels (the 4 x 4 level: a wave's 64 rows are four samples).  A lane's accumulator registers
         // r < 8 / r >= 8 of a 32 x 32 tile are rows 0-15 / 16-31 of it (out_row), a 16 x 16 tile is one block: the sums split in the lane,
         // only the fold over the lanes that share a column stays.  Same order and single-writer rule as the 64-row form below.
@@ -408,13 +421,18 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
                     for (int o = TL::TM; o < 64; o <<= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
                     const int mrow = m0 + wm * 64 + i * TL::TM + h * 16;
                     if (lane < TL::TM && n < p.Cout && mrow < p.M) {
-                        float* cs = p.colstats + ((size_t)(mrow >> 4) * p.Cout + n) * 2;
-                        cs[0] = s; cs[1] = q;
+                        if constexpr (SELF) {
+                            const int e = ((mrow - m0) >> 4) * BN + wn * 96 + j * TL::TM + TL::out_col(lane_s);
+                            self.cs_s[e] = s; self.cs_q[e] = q;
+                        } else {
+                            float* cs = p.colstats + ((size_t)(mrow >> 4) * p.Cout + n) * 2;
+                            cs[0] = s; cs[1] = q;
+                        }
                     }
                 }
             if (Elt<T>::SATURATES) inrange[j] = qtot <= kF16Max * kF16Max;
         }
-    } else if (p.colstats) {
+    } else if (SELF || p.colstats) {
         // GroupNorm statistics of the conv output, fused: per column (sum, sum of squares) over this wave's 64
         // rows, straight from the accumulators (f32, before the rounding to T): a lane adds up the rows it
         // holds, the 64/TM lanes sharing a column are folded with cross-lane adds.  Fixed order and exactly one
@@ -440,8 +458,13 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
             for (int o = TL::TM; o < 64; o <<= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
             // (M % 128 == 64: the second wave row of the last tile lies beyond M -- it owns no row block)
             if (lane < TL::TM && n < p.Cout && m0 + wm * 64 < p.M) {
-                float* cs = p.colstats + ((size_t)((m0 + wm * 64) >> 6) * p.Cout + n) * 2;
-                cs[0] = s; cs[1] = q;
+                if constexpr (SELF) {
+                    const int e = wm * BN + wn * 96 + j * TL::TM + TL::out_col(lane_s);
+                    self.cs_s[e] = s; self.cs_q[e] = q;
+                } else {
+                    float* cs = p.colstats + ((size_t)((m0 + wm * 64) >> 6) * p.Cout + n) * 2;
+                    cs[0] = s; cs[1] = q;
+                }
             }
         }
     }
@@ -548,7 +571,26 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
         }
     }
     static_assert(LEANM == 0 || (sizeof(T) == 4 && TL::TM == 32 && !GG), "the lean epilogue: f32 storage, 32 x 32 tiles");
-    static_assert(LEANM != 2 || !PN, "the GroupNorm tail: no fused PreNorm next to it");
+    static_assert(LEANM < 2 || !PN, "the GroupNorm tail / the launch's own GroupNorm: no fused PreNorm next to it");
+    if constexpr (SELF) {
+        // (mean, rstd) of every (sample, group) pair of the tile from the column sums the eight waves have just left in LDS
+        __syncthreads();
+        const int hw = p.Hm * p.Wm, cpg = p.gn_cpg;
+        const int nb = p.stat_rows == 16 ? 1 : hw >> 6;            // row blocks per sample: 4, 1 (64-row blocks), 1 (16-row blocks)
+        const int ncols = p.Cout - n0 < BN ? p.Cout - n0 : BN;
+        const int ng = (int)p.d_cpg.div((unsigned)ncols), npairs = (int)p.d_hw.div(256u) * ng;
+        for (int pr = wm * 2 + wn; pr < npairs; pr += 8) {         // (wave-uniform: gn_group_sum is wave-collective)
+            const int t = pr / ng, g = pr - t * ng;
+            float S, Q;
+            gn_group_sum(cpg, lane_s, [&](int c) {
+                return gn_fold_column(nb, [&](int b) { const int e = (t * nb + b) * BN + g * cpg + c; return f32x2_t{self.cs_s[e], self.cs_q[e]}; });
+            }, S, Q);
+            float mean, rstd;
+            gn_mean_rstd(S, Q, (float)cpg * (float)hw, p.gn_eps, mean, rstd);
+            if (lane_s == 0) { self.ms[2 * pr] = mean; self.ms[2 * pr + 1] = rstd; }
+        }
+        __syncthreads();
+    }
     if constexpr (LEANM >= 1) {
         constexpr bool TAIL = LEANM == 2;
         // f32 storage on the 32 x 32 tiles (NOPE_BF16X3 / NOPE_F16X2: the modes the benchmark runs in), whole wave tile inside the tensor, rows in
@@ -567,7 +609,12 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
             // absent embedding -- a zero the compiler cannot see, added where that kernel adds it (-0 + 0 = +0: leaving it out could flip a sign bit)
             const unsigned tb = TAIL ? p.d_hw.div((unsigned)mw) : 0u;
             const float* tms = TAIL ? p.gn_ms + (size_t)tb * (unsigned)p.gn_G * 2 : nullptr;
-            const float tz = TAIL && p.gn_G <= 0 ? 1.f : 0.f;
+            const float tz = (TAIL || SELF) && p.gn_G <= 0 ? 1.f : 0.f;
+            // the launch's own GroupNorm: the samples of this wave tile are st0 ... of the tile (one, or four on 16-pixel maps: rows 16 k .. 16 k + 15), sn0 + ... of the launch
+            const bool s16 = SELF && p.stat_rows == 16;
+            const int sng = SELF ? (int)p.d_cpg.div((unsigned)(p.Cout - n0 < BN ? p.Cout - n0 : BN)) : 0;
+            const int st0 = SELF ? (s16 ? wm * 4 : (int)p.d_hw.div((unsigned)(wm * 64))) : 0;
+            const unsigned sn0 = SELF ? p.d_hw.div((unsigned)m0) : 0u;
             f32x2_t os2 = {0.f, 0.f}, oq2 = {0.f, 0.f};            // (TAIL) sum / sum of squares of what this lane stores: ConvParams::tail_stats
             // Buffer addressing: 32-bit byte offsets (one per-lane base + a uniform pass / row-group term: one v_add per access) -- no 64-bit
             // address arithmetic in a kernel that has no register to spare.  The uniform term goes into the VECTOR offset, not the
@@ -607,6 +654,24 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
                             gsc[e >> 1][e & 1] = a; gsh[e >> 1][e & 1] = gn_shift(gmean, a, p.gn_beta[nn + e]);
                         }
                     }
+                    // (SELF) the same coefficients from the (mean, rstd) in LDS, and the embedding row: per pass where the wave tile is one sample, per
+                    // 16-row group on 16-pixel maps (four samples per wave tile: four sets would not fit the registers; gamma / beta come out of the cache again)
+                    f32x2_t gev[2];
+                    auto self_coef = [&](int t) {
+                        const int nn = nw + pass * 32 + (lane_s & 7) * 4;
+                        const float* ms = self.ms + 2 * ((st0 + t) * sng + (int)p.d_cpg.div((unsigned)(nn - n0)));
+                        const float gmean = ms[0], grstd = ms[1];
+                        const float* eb = p.gn_emb ? p.gn_emb + (size_t)(sn0 + (unsigned)(st0 + t)) * (unsigned)p.gn_emb_stride + nn : nullptr;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float a = gn_scale(grstd, p.gn_gamma[nn + e]);      // (gn_apply_kernel: coeff)
+                            gsc[e >> 1][e & 1] = a; gsh[e >> 1][e & 1] = gn_shift(gmean, a, p.gn_beta[nn + e]);
+                            gev[e >> 1][e & 1] = eb ? eb[e] : tz;
+                        }
+                    };
+                    if constexpr (SELF) {
+                        if (!s16) self_coef(0);
+                    }
                     const float bv = bvj[pass];
 #pragma unroll
                     for (int i = 0; i < TL::MT; ++i)
@@ -635,6 +700,16 @@ __device__ __forceinline__ void epilogue_wide(const ConvParams& p, const typenam
                             if (PN) {
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) v[e] = pn_apply(v[e] - pb[e], pmean, prstd, pc1[e], pc0[e]);
+                            }
+                            if constexpr (SELF) {
+                                if (s16 && ((grp * LG + c) & 1) == 0) self_coef((grp * LG + c) >> 1);      // (rows 8 k .. 8 k + 7 of the wave tile: sample k / 2)
+#pragma unroll
+                                for (int q = 0; q < 2; ++q) {
+                                    f32x2_t t = muladd(f32x2_t{v[2 * q], v[2 * q + 1]}, gsc[q], gsh[q]);    // (gn_apply_kernel: apply_v)
+                                    t = silu2<true>(t);
+                                    t += gev[q];
+                                    v[2 * q] = t.x; v[2 * q + 1] = t.y;
+                                }
                             }
                             if (RESID) {
                                 float rf[4];

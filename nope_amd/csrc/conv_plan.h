@@ -77,6 +77,12 @@ struct ConvParams {
     FastDiv d_cpg;                     // / (Cout / gn_G)
     float* tail_stats;                 // optional [nhyp][(HW / 64) * tail_cols][2]: (sum, sum of squares) of what each wave tile wrote
     int tail_cols;                     // 96-column wave tiles across Cout
+    // The launch's own GroupNorm (ConvArgs::gn_self; the tap-resident kernel's lean epilogue only): out = SiLU(GN(conv)) [+ emb] [+ resid];
+    // gn_gamma / gn_beta / gn_G / d_cpg above, stat_rows = rows per block of the column sums it keeps in LDS (64, or 16 on 16-pixel maps), resid = ConvArgs::gn_resid
+    int gn_self;
+    int gn_cpg;                        // Cout / gn_G
+    float gn_eps;
+    const float* gn_emb; int gn_emb_stride;
 };
 
 }  // namespace

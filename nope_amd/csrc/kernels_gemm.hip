@@ -414,7 +414,7 @@ static ConvFacts conv_facts(int dt, const ConvArgs& a, const ConvSwitches& s) {
 static int splitk_factor(const ConvArgs& a, const ConvFacts& f) {
     const ConvSizes& z = f.z;
     if (f.hsplit > 1) return f.hsplit;      // long 3x3 convs with few tiles: split-K on the tap-resident kernel (its reduce kernel also serves a colstats request)
-    if (a.colstats || a.pn_ms || a.mode == NOPE_CONV_UP2P || a.mode == NOPE_CONV_UP2) return 1;
+    if (a.colstats || a.gn_self || a.pn_ms || a.mode == NOPE_CONV_UP2P || a.mode == NOPE_CONV_UP2) return 1;      // (gn_self: planned as the launch with fused statistics it replaces)
     if (z.Cin % z.bk) return 1;
     if (f.small >= 0) return 1;          // the small-tile kernel has enough workgroups without splitting K
     const long long tiles = (long long)cdiv((int)z.M, BM) * cdiv(a.Cout, BN);
@@ -462,7 +462,7 @@ static KernelChoice choose_kernel(int dt, const ConvArgs& a, const ConvSwitches&
     if (a.splitk_ws && f.hsplit > 1 && (size_t)f.hsplit * (size_t)z.M * a.Cout * 4 <= a.splitk_bytes) { pl.pp = pl.halo = true; pl.hsplit = f.hsplit; return pl; }      // the split only where the scratch holds it
     pl.small = f.small;
     if (pl.small >= 0) return pl;
-    const bool small3x3 = a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && !a.colstats && !a.pn_ms && !a.out_nchw && !a.splitk_ws &&
+    const bool small3x3 = a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && !a.colstats && !a.gn_self && !a.pn_ms && !a.out_nchw && !a.splitk_ws &&
                           a.Hs * a.Ws <= POSMAJOR_MAX_HW;
     const bool posmajor128 = small3x3 && a.nhyp % BM == 0 && !(variant & 8) && variant != 4;
     // (short K loops -- the 1x1 convs around the attention blocks, 2-3 K steps per tile -- stay on the 128 x 192 kernel, whose two
@@ -550,6 +550,9 @@ static int plan_requests(const ConvArgs& a, const ConvSwitches& s, const ConvFac
     // (gn_G >= 1 is also what makes epilogue_wide's `tz` -- conv_gemm_common.h: a zero formed from `gn_G <= 0` -- a zero)
     if ((a.gn_ms || a.tail_stats) && (!a.gn_ms || !a.gn_gamma || !a.gn_beta || !a.resid || a.gn_G < 1 || a.Cout % a.gn_G || a.act || a.pn_ms || a.colstats ||
                                       ((uintptr_t)a.gn_ms & 7))) return NOPE_ERR_ARG;
+    // The launch's own GroupNorm (ConvArgs::gn_self): complete arguments, none of the forms it replaces or cannot sit next to
+    if (a.gn_self && (!a.gn_gamma || !a.gn_beta || a.gn_G < 1 || a.Cout % a.gn_G || a.gn_ms || a.tail_stats || a.resid || a.colstats || a.act || a.pn_ms || a.geglu ||
+                      a.out_nchw || (a.gn_emb && a.gn_emb_stride < a.Cout))) return NOPE_ERR_ARG;
     return NOPE_OK;
 }
 
@@ -740,6 +743,21 @@ static int plan_epilogue(ConvLaunch& L, const ConvArgs& a, const ConvSwitches& s
         p.d_cpg = make_fastdiv((unsigned)cpg);
         p.tail_stats = a.tail_stats; p.tail_cols = cdiv(a.Cout, 96);
     }
+    if (a.gn_self) {
+        // the launch's own GroupNorm lives in ONE epilogue too: the lean row walk of the tap-resident kernel, where a 256-row tile holds
+        // whole samples (maps of 16, 64 or 256 pixels) and a 192-column tile whole groups of whole 4-channel chunks, in one launch (no split-K); on 16-pixel maps the
+        // column sums take the LDS a tile walk's next prologue would write, so one tile per workgroup there.  Any other launch is refused, never run without it.
+        const long long HW = (long long)p.Hm * p.Wm;
+        const int cpg = a.Cout / a.gn_G;
+        if (!(pick.halo && !phased && p.lean && a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && p.splits == 1 && (HW == 16 || HW == 64 || HW == 256) && M % 256 == 0 &&
+              cpg % 4 == 0 && BN % cpg == 0 && (HW != 16 || p.persist_iters == 1) && s.variant == 0 && !s.pp_variant.set))
+            return NOPE_ERR_UNSUPPORTED;
+        p.gn_self = 1; p.gn_gamma = a.gn_gamma; p.gn_beta = a.gn_beta; p.gn_G = a.gn_G; p.gn_cpg = cpg; p.gn_eps = a.gn_eps;
+        p.d_cpg = make_fastdiv((unsigned)cpg);
+        p.gn_emb = a.gn_emb; p.gn_emb_stride = a.gn_emb_stride;
+        p.resid = (const unsigned char*)a.gn_resid;
+        p.stat_rows = HW == 16 ? 16 : 64;
+    }
     return NOPE_OK;
 }
 
@@ -800,7 +818,7 @@ static void trace_conv(const ConvLaunch& L) {
                                                  p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z, p.xcd_map, p.xcd_gn);
     else fprintf(stderr, "conv %s mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u posmajor %d persist %d xcd %d/%d%s%s\n",
                  names[L.kind], p.mode, p.ntaps, Cin, p.Cout, (long long)p.M, p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z,
-                 p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, p.geglu ? " geglu" : L.x2 ? " x2" : "", p.gn_ms ? " lean gn-tail" : p.lean ? " lean" : "");
+                 p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, p.geglu ? " geglu" : L.x2 ? " x2" : "", p.gn_ms ? " lean gn-tail" : p.gn_self ? " lean gn-self" : p.lean ? " lean" : "");
 }
 
 // fn((T*)nullptr) with T the type a tensor of `dt` is stored in (the reduce kernels of a split launch write it)

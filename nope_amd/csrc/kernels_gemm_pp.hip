@@ -472,9 +472,33 @@ constexpr int TIMELINE_STAMPS = 720;  // per group; 5 per K step (tuning instant
 // Earlier forms, both bit-identical and slower: six positions per chunk with pieces issued in two MFMA-less ones (two exposed L2 round trips
 // per chunk: 0.63 of the K steps' rate, profiles/r06v_*), five positions with one light position (0.78, r06w_*).  Both groups pass two
 // barriers per K step.  Same K order as the per-tap kernel (chunk outer, tap inner): bit-identical to it.
-template <class T, bool TIMELINE = false, bool SPLIT = false, bool SHIFT = true, bool LEAN = false, bool UP = false>
+// SELF (the kernel's own GroupNorm: ConvParams::gn_self; epilogue_wide, LEANM = 3): at the 16 x 16, 8 x 8 and 4 x 4
+// levels a 256-row tile holds whole samples and a 192-column tile whole groups, so the workgroup owns every number (mean, rstd) needs -- the column
+// sums stay in LDS, two workgroup barriers in the epilogue, and the row walk stores SiLU(GN(conv)) [+ emb] [+ residual]: the GroupNorm pass that
+// would read the tensor back is not launched.  Its own instantiation: the others keep their code and their registers.
+// The LDS of the form (floats): per-row-block column sums cs_s / cs_q [row blocks][192] and (mean, rstd) [samples][groups][2].
+//   64-row blocks (4 per tile): cs_s and (mean, rstd) in the rows of A stage 1 behind group 1's panels, cs_q behind the ring -- nothing the next
+//   tile's prologue writes (it is in flight during the epilogue of a tile walk);
+//   16-row blocks (16 per tile, the 4 x 4 level): B stage 0 and the first half of B stage 1 -- free once the K loop is over; conv_plan grants the
+//   form there only to launches of one tile per workgroup (no prologue in flight).
+template <class T, bool TIMELINE, bool SELF> struct HaloLds {
+    static constexpr int RB = 128, B_STAGE = BN * RB, A_BASE = 3 * B_STAGE, ZROW = HALO_ROWS * RB, A_STAGE = ZROW + RB, RING = A_BASE + 2 * A_STAGE;
+    static constexpr int PANELS = PP_WAVES * Ep<T>::WAVE_BYTES;
+    static constexpr int SELF_S = A_BASE + A_STAGE + 4 * Ep<T>::WAVE_BYTES, SELF_MS = SELF_S + 4 * BN * 4, SELF_Q = RING;      // (64-row blocks)
+    static constexpr int SELF16_S = 0, SELF16_Q = 16 * BN * 4, SELF16_MS = 2 * SELF16_Q;                                      // (16-row blocks)
+    static constexpr int SELF_MS_BYTES = 4 * (BN / 4) * 2 * 4;          // 4 samples x 48 groups of 4 channels (16 samples in the 16-row form: four times that)
+    static constexpr int USED = SELF ? SELF_Q + 4 * BN * 4 : RING > PANELS ? RING : PANELS;
+    static constexpr int BYTES = USED + (TIMELINE ? 2 * TIMELINE_STAMPS * 4 : 0);
+    static_assert(!SELF || (Tile<T>::TM == 32 && SELF_MS + SELF_MS_BYTES <= A_BASE + A_STAGE + ZROW && SELF16_MS + 4 * SELF_MS_BYTES <= B_STAGE + B_STAGE / 2),
+                  "the GroupNorm scratch lies outside the panels, the zero rows and what a prologue writes");
+};
+
+// (No split-K launch is lean, so the pair SPLIT_ && LEAN names this form: the existing instantiations keep their names.)
+template <class T, bool TIMELINE = false, bool SPLIT_ = false, bool SHIFT = true, bool LEAN = false, bool UP = false>
 __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvParams p) {
+    constexpr bool SELF = SPLIT_ && LEAN, SPLIT = SPLIT_ && !LEAN;
     static_assert(!UP || (!TIMELINE && !SPLIT && !LEAN), "the phase-conv form: one tile per workgroup, generic wide epilogue");
+    static_assert(!SELF || (!TIMELINE && !UP && sizeof(T) == 4), "the kernel's own GroupNorm: the lean epilogue, f32 storage");
     typedef Tile<T> TL;
     constexpr int VEC = Elt<T>::VEC;
     constexpr unsigned ES = (unsigned)sizeof(T);
@@ -486,11 +510,13 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
     constexpr int A_STAGE = ZROW + RB;
     constexpr int RING = A_BASE + 2 * A_STAGE;
     constexpr int PANELS = PP_WAVES * Ep<T>::WAVE_BYTES;
-    constexpr int LDS_USED = RING > PANELS ? RING : PANELS;
-    constexpr int LDS_BYTES = LDS_USED + (TIMELINE ? 2 * TIMELINE_STAMPS * 4 : 0);
+    typedef HaloLds<T, TIMELINE, SELF> HL;
+    constexpr int LDS_USED = HL::USED;
+    constexpr int LDS_BYTES = HL::BYTES;
     constexpr int KS = RB / 16 / TL::STEP_SLOTS, RAW = TL::RAW, KK = KS * RAW;
+    static_assert(HL::RING == RING && HL::PANELS == PANELS && (SELF || LDS_USED == (RING > PANELS ? RING : PANELS)), "HaloLds restates this layout");
     static_assert(LDS_BYTES <= 160 * 1024 && A_STAGE < 65536 && 2 * B_STAGE + BN * RB < 65536 + B_STAGE && 2 * B_STAGE + 2 * Tile<T>::TM * RB < 65536, "LDS budget / ds_read immediates (16 bits)");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];     // the ONLY LDS object (cdna_hip_programming.md, section 5 trap (a))
 
     const int tid = threadIdx.x;
     if (p.variant & 128) { if (tid == 9999) lds[0] = 1; return; }   // tuning only (NOPE_PP_VARIANT): launch cost of the grid
@@ -1126,7 +1152,12 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
             }
             return;
         } else if constexpr (TIMELINE) epilogue_wide<T, false, true>(p, acc, m_this, n0, wm, wn, lane, lds_panel, stamp, x2_out);
-        else epilogue_wide<T, false, true, NoStamp, false, LEAN ? 1 : 0>(p, acc, m_this, n0, wm, wn, lane, lds_panel, NoStamp(), x2_out);
+        else if constexpr (SELF) {
+            const bool s16 = p.stat_rows == 16;                    // (wave-uniform; see HaloLds for the placement)
+            const SelfLds sl = {reinterpret_cast<float*>(lds + (s16 ? HL::SELF16_S : HL::SELF_S)), reinterpret_cast<float*>(lds + (s16 ? HL::SELF16_Q : HL::SELF_Q)),
+                                reinterpret_cast<float*>(lds + (s16 ? HL::SELF16_MS : HL::SELF_MS))};
+            epilogue_wide<T, false, true, NoStamp, false, 3>(p, acc, m_this, n0, wm, wn, lane, lds_panel, NoStamp(), x2_out, sl);
+        } else epilogue_wide<T, false, true, NoStamp, false, LEAN ? 1 : 0>(p, acc, m_this, n0, wm, wn, lane, lds_panel, NoStamp(), x2_out);
         if (more) {
 #pragma unroll
             for (int i = 0; i < TL::MT; ++i)
@@ -1214,6 +1245,12 @@ void launch_conv_halo(int dt, const void* params, dim3 grid, hipStream_t s) {
         else if (dt == NOPE_F16X2 && p.x2_t_zero) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, true, false>), grid, block, 0, s, p);
         else if (dt == NOPE_F16X2) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((conv3x3_halo_kernel<bf16_t, false, true>), grid, block, 0, s, p);
+        return;
+    }
+    if (p.gn_self) {                                   // (conv_plan: lean, f32 storage in bf16x3 / f16x2; <.., SPLIT_ = true, .., LEAN = true>: the form's own instantiation)
+        if (dt == NOPE_BF16X3) hipLaunchKernelGGL((conv3x3_halo_kernel<f32s_t, false, true, true, true>), grid, block, 0, s, p);
+        else if (p.x2_t_zero) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, true, false, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, true, true, true>), grid, block, 0, s, p);
         return;
     }
     if (p.lean && dt == NOPE_BF16X3) { hipLaunchKernelGGL((conv3x3_halo_kernel<f32s_t, false, false, true, true>), grid, block, 0, s, p); return; }

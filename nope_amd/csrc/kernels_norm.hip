@@ -137,9 +137,8 @@ template <class Emit>
 __device__ __forceinline__ void group_sums(const float* ch_s, const float* ch_q, int cpg, int G, int tid, Emit emit) {
     const int lane = tid & 63;
     for (int g = tid >> 6; g < G; g += NT / 64) {
-        float S = 0.f, Q = 0.f;
-        for (int c = lane; c < cpg; c += 64) { S += ch_s[g * cpg + c]; Q += ch_q[g * cpg + c]; }
-        S = wave_sum(S); Q = wave_sum(Q);
+        float S, Q;
+        gn_group_sum(cpg, lane, [&](int c) { return f32x2_t{ch_s[g * cpg + c], ch_q[g * cpg + c]}; }, S, Q);
         if (lane == 0) emit(g, S, Q);
     }
 }
@@ -148,20 +147,8 @@ __device__ __forceinline__ void group_sums(const float* ch_s, const float* ch_q,
 // flight, then the adds in row-block order.  One copy for gn_fold_kernel, gn_colstats_finalize_kernel and gn_apply_kernel's FOLD: same order, same bits.
 __device__ __forceinline__ void fold_columns(const float* base, int nb, int C, int tid, float* ch_s, float* ch_q) {
     for (int c = tid; c < C; c += NT) {
-        float s = 0.f, q = 0.f;
-        int b = 0;
-        for (; b + 8 <= nb; b += 8) {
-            f32x2 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x2*>(base + ((size_t)(b + u) * C + c) * 2);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { s += v[u][0]; q += v[u][1]; }
-        }
-        for (; b < nb; ++b) {
-            const f32x2 v = *reinterpret_cast<const f32x2*>(base + ((size_t)b * C + c) * 2);
-            s += v[0]; q += v[1];
-        }
-        ch_s[c] = s; ch_q[c] = q;
+        const f32x2_t r = gn_fold_column(nb, [&](int b) { return *reinterpret_cast<const f32x2_t*>(base + ((size_t)b * C + c) * 2); });
+        ch_s[c] = r[0]; ch_q[c] = r[1];
     }
 }
 

@@ -302,6 +302,35 @@ __device__ __forceinline__ void gn_mean_rstd(float S, float Q, float cnt, float 
     var = var > 0.f ? var : 0.f;
     rstd = 1.0f / sqrtf(var + eps);
 }
+// The two steps from a conv epilogue's per-row-block column statistics to a group's (sum, sum of squares), one copy for everyone who must agree on
+// the bits: gn_fold_kernel, gn_colstats_finalize_kernel, gn_apply_kernel's FOLD (kernels_norm.hip: fold_columns, group_sums) and the conv epilogue
+// that normalises its own output (epilogue_wide, LEANM = 3).
+// One channel over nb row blocks, ld(b) = the (sum, sum of squares) entry of block b: 8 independent loads in flight, then the adds in row-block order
+template <class Ld>
+__device__ __forceinline__ f32x2_t gn_fold_column(int nb, Ld ld) {
+    float s = 0.f, q = 0.f;
+    int b = 0;
+    for (; b + 8 <= nb; b += 8) {
+        f32x2_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = ld(b + u);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { s += v[u][0]; q += v[u][1]; }
+    }
+    for (; b < nb; ++b) {
+        const f32x2_t v = ld(b);
+        s += v[0]; q += v[1];
+    }
+    return f32x2_t{s, q};
+}
+// One group of cpg channels, ch(c) = channel c's folded (sum, sum of squares): a lane adds every 64th channel in channel order, wave_sum's fixed
+// butterfly folds the 64 lane sums (every lane of the wave must call it)
+template <class Ch>
+__device__ __forceinline__ void gn_group_sum(int cpg, int lane, Ch ch, float& S, float& Q) {
+    S = 0.f; Q = 0.f;
+    for (int c = lane; c < cpg; c += 64) { const f32x2_t v = ch(c); S += v[0]; Q += v[1]; }
+    S = wave_sum(S); Q = wave_sum(Q);
+}
 
 // Keeps a value (and the loads that produced it) alive in a tuning build that skips its consumer -- without this the
 // compiler deletes the loads too and the ablation measures less than it claims (cdna_hip_programming.md rule 17).
@@ -415,6 +444,17 @@ struct ConvArgs {
     int gn_G = 0;
     float* tail_stats = nullptr;     // optional, with gn_ms: [nhyp][conv_tail_stat_blocks()][2] (sum, sum of squares) of the values written, one writer per
                                      // entry, fixed order: the GroupNorm(1) partials of the output (launch_gn_finalize), as GnApplyArgs::out_stats
+    // The conv's OWN GroupNorm (a ResnetBlock's conv -> GroupNorm -> SiLU [-> + emb] [-> + x] in one launch, unet_runtime.hip):
+    //   out[m,n] = SiLU(conv[m,n] * a + b) [+ gn_emb[s][n]] [+ gn_resid[m,n]],  (mean, rstd) of conv over sample s, group g -- formed inside the launch
+    // with the column sums, the fold order and the arithmetic of the conv's fused statistics + launch_gn_apply: bit-identical to those two launches.
+    // gn_gamma / gn_beta / gn_G as above; gn_ms, resid, colstats, act and a fused PreNorm stay unset.  Only a launch that conv_plan puts on the
+    // tap-resident kernel with the lean epilogue takes it (maps of 16, 64 or 256 pixels, M % 256 == 0, groups of whole 4-channel chunks that lie
+    // inside one 192-column tile, no split-K); NOPE_ERR_UNSUPPORTED otherwise, nothing launched.
+    int gn_self = 0;
+    float gn_eps = 1e-5f;
+    const float* gn_emb = nullptr;   // optional [nhyp][gn_emb_stride]: row s, columns [0, Cout)
+    int gn_emb_stride = 0;
+    const void* gn_resid = nullptr;  // optional NHWC [M][Cout], added last (one sample per output sample)
 };
 int launch_conv(int dt, const ConvArgs& a, hipStream_t s);
 bool conv_geglu_fusable(int dt, const ConvArgs& a);   // would launch_conv take this conv with geglu = 1?

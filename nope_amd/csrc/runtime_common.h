@@ -147,6 +147,8 @@ struct ConvOpts {
     // GroupNorm tail on the residual (ConvArgs::gn_*): out = conv + SiLU(GN(resid)), the norm's affine, its groups, (mean, rstd) [nhyp][G][2] of resid
     // and, optionally, where the GroupNorm(1) partials of the output go (ConvArgs::tail_stats)
     const NormW* gn = nullptr; int gn_G = 0; const float* gn_ms = nullptr; float* tail_stats = nullptr;
+    // The conv's own GroupNorm (ConvArgs::gn_self): out = SiLU(GN(conv)) [+ emb row] [+ gn_resid], the norm's affine in `gn`, its groups in gn_G
+    bool gn_self = false; const float* gn_emb = nullptr; int gn_emb_stride = 0; const void* gn_resid = nullptr;
 };
 inline ConvOpts with_resid(const void* resid) { ConvOpts o; o.resid = resid; return o; }
 inline ConvOpts to_nchw(int out_dt) { ConvOpts o; o.out_nchw = 1; o.out_dt = out_dt; return o; }
@@ -198,6 +200,7 @@ template <class N> struct FwdCore {
         ca.out = out; ca.Cout = c.Cout; ca.nhyp = nhyp; ca.out_nchw = o.out_nchw; ca.out_dt = o.out_dt;
         if (c.w_x2 && c.x2_id >= 0 && !net->x2r.off) { ca.w_x2 = c.w_x2; ca.x2_t_zero = net->x2r.t_zero(c.x2_id) ? 1 : 0; }
         if (o.gn) { ca.gn_ms = o.gn_ms; ca.gn_gamma = o.gn->gamma; ca.gn_beta = o.gn->beta; ca.gn_G = o.gn_G; ca.tail_stats = o.tail_stats; }
+        if (o.gn && o.gn_self) { ca.gn_self = 1; ca.gn_emb = o.gn_emb; ca.gn_emb_stride = o.gn_emb_stride; ca.gn_resid = o.gn_resid; }
         return true;
     }
     // Second half: the plan of the filled ConvArgs (made once: the tracking, a profile and launch_conv read the same decisions), tracked -- a

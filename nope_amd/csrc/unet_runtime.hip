@@ -21,6 +21,11 @@
 //     cat(cur, r) with r per reference, so conv = conv(W[:, :C], cur) + Sr, Sr = conv(W[:, C:], r) + bias per reference; the per-template
 //     launch has half the K and the GroupNorm that follows forms cur' + Sr.  Summation order changes, nothing else: the shared parts run
 //     in f32 / bf16x3 even under NOPE_F16X2 (Fwd::resnet);
+//   * NOPE_GN_EPI (read per forward; bit 0 | bit 1, default 3, 0 = neither; f32 activation storage in bf16x3 / f16x2): at the 16 x 16, 8 x 8 and
+//     4 x 4 levels a ResnetBlock's 3x3 conv on the tap-resident kernel normalises its own output -- GroupNorm + SiLU (+ embedding row, + identity
+//     residual) in its epilogue, the statistics formed in LDS by the workgroup that owns the samples -- so the GroupNorm pass over the tensor is
+//     not launched.  Bit 0 = block1, bit 1 = block2 of blocks without a res_conv that no attention follows.  Bit-identical to the two launches,
+//     taken only where conv_plan grants it (Fwd::conv_gn_self);
 //   * the 19 per-block `Linear(SiLU(c))` embeddings (model_utils.py:261-265,274-275) are one
 //     f32 GEMM against the row-concatenated weights;
 //   * a bump arena over caller-provided workspace: no allocation, no host sync, one stream.
@@ -87,7 +92,7 @@ struct nope_unet : rt::Net {      // (dt / sdt / x2 / x2r / allocs: rt::Net, run
     mutable std::vector<UGraph> graphs;
     mutable bool graphs_ok = true;           // cleared when capture is unavailable: direct launches from then on
     mutable std::mutex graph_mu;
-    mutable int graph_split = -1;            // NOPE_SHARED_SPLIT | NOPE_RES_TAIL << 2 the cached graphs were captured under
+    mutable int graph_split = -1;            // NOPE_SHARED_SPLIT | NOPE_RES_TAIL << 2 | NOPE_GN_EPI << 4 the cached graphs were captured under
     mutable int graph_replays = 0;           // forwards served by a graph replay since create (tests assert the path really ran)
     long long graph_max = 0;                 // largest n_hyp * H * W that replays a graph; 0 = off
 };
@@ -191,6 +196,7 @@ struct Fwd : rt::FwdCore<nope_unet> {
     const float* emb_all = nullptr;
     int pn_blocks = 0;             // entries per hypothesis of pn_partial as its last producer laid them out (gn_apply_blocks, or conv_tail_stat_blocks)
     int split = 0;                 // NOPE_SHARED_SPLIT of this forward: bit 0 = downs[0][0].block2, bit 1 = final_res_block.block1
+    int gn_epi = 0;                // NOPE_GN_EPI of this forward: bit 0 = block1, bit 1 = block2 with an identity residual (conv_gn_self)
 
     // run `fn` as a forward over n samples (the per-reference launches: profiled, traced and range-tracked like every other)
     template <class F> void over(int n, F fn) { const int keep = nhyp; nhyp = n; fn(); nhyp = keep; }
@@ -305,6 +311,26 @@ struct Fwd : rt::FwdCore<nope_unet> {
         return true;
     }
 
+    // A ResnetBlock's conv with its OWN GroupNorm in ONE launch: out = SiLU(GN(conv(a [cat b]))) [+ the embedding row] [+ resid] (ConvArgs::gn_self).  At the
+    // 16 x 16, 8 x 8 and 4 x 4 levels a 256-row tile of the tap-resident kernel holds whole samples and a 192-column tile whole groups, so the workgroup
+    // that computes a tile forms (mean, rstd) itself and the GroupNorm pass that would read the tensor back is never launched -- with that pass's
+    // fold order and arithmetic: bit-identical to the two launches.  Taken where conv_plan grants it (asked, never assumed: split-K launches, the
+    // 32 x 32 level, the other kernels and NOPE_EPILOGUE_LEAN=0 say no); a workspace-size query always sizes the two launches.  False: not taken,
+    // nothing launched.  NOPE_GN_EPI: bit 0 = block1 (conv -> GN -> SiLU -> + emb), bit 1 = block2 with an identity residual (no res_conv, not
+    // followed by attention, no fused projection, no shared addend); 0 = the two launches everywhere.
+    bool conv_gn_self(const PackedConv& c, const Act& a, const Act* b, void* out, const NormW& nm, int emb_off, const void* resid) {
+        const int G = net->cfg.groups;
+        if (!live() || net->sdt != NOPE_F32 || net->dt == NOPE_F32 || G < 1 || c.Cout % G) return false;
+        ConvOpts o;
+        o.gn = &nm; o.gn_G = G; o.gn_self = true; o.gn_resid = resid; o.track_out = true;
+        if (emb_off >= 0) { o.gn_emb = emb_all + emb_off; o.gn_emb_stride = net->emb_total; }
+        ConvArgs ca;
+        if (!conv_args(ca, c, a, b, out, a.H, a.W, o)) return false;
+        if (conv_splitk_factor(net->dt, ca) > 1 || conv_plan(net->dt, ca).err != NOPE_OK) return false;
+        conv(c, a, b, out, a.H, a.W, o);
+        return true;
+    }
+
     // ResnetBlock, model_utils.py:271-279.  `a` may be shared by a.rep hypotheses (rep > 1 only for the very first block, where b == nullptr).
     // `next_is_attention`: also emit the GroupNorm(1) partials of the block's output into pn_partial.
     // tail: fused into the block's last pass where gn() can; returns whether it was (then `out` holds the un-normalised conv output and
@@ -369,10 +395,12 @@ struct Fwd : rt::FwdCore<nope_unet> {
             over(ns, [&] { conv(R.c1, per_ref(a), nullptr, t1s, a.H, a.W, with_stats(g1.stats)); });
             g1.x_rep = a.rep;
             gn(R.n1, G, t1s, t1, HW, g1);
-        } else {
+        } else if (!((gn_epi & 1) && conv_gn_self(R.c1, a, b, t1, R.n1, emb_off, nullptr))) {
             conv(R.c1, a, b, t1, a.H, a.W, with_stats(g1.stats));
             gn(R.n1, G, t1, t1, HW, g1);
         }
+        if ((gn_epi & 2) && !R.has_res && !b && !next_is_attention && !tail.proj && a.rep == 1 &&
+            conv_gn_self(R.c2, Act{t1, R.c1.Cout, a.H, a.W}, nullptr, out, R.n2, -1, a.p)) { ar.off = mark; return false; }
         conv(R.c2, Act{t1, R.c1.Cout, a.H, a.W}, nullptr, out, a.H, a.W, with_stats(g2.stats));
         if (R.has_res) {
             void* t3 = alloc_act(M * R.res.Cout);      // (allocated under the one-pass form too: the workspace of a shape does not depend on NOPE_RES_TAIL)
@@ -436,6 +464,7 @@ int run_forward(const nope_unet* net, const FwdReq& q, void* ws, size_t ws_bytes
     Fwd f;
     f.begin(net, n_hyp, ws, ws_bytes, s, dry);
     f.split = q.split;
+    f.gn_epi = NOPE_ENV("NOPE_GN_EPI", 3) & 3;
     const int HW = H * W;
     const int* dims = net->dims;
 
@@ -797,7 +826,7 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
     q.n_src = n_src; q.x_rep = x_rep; q.n_hyp = n_hyp; q.H = H; q.W = W; q.split = split;
     if (!want_graph) return run_forward(net, q, base, avail, s);
     std::lock_guard<std::mutex> lock(net->graph_mu);
-    const int plan_key = split | (NOPE_ENV("NOPE_RES_TAIL", 1) & 3) << 2;      // the switches read per forward that change the launch sequence
+    const int plan_key = split | (NOPE_ENV("NOPE_RES_TAIL", 1) & 3) << 2 | (NOPE_ENV("NOPE_GN_EPI", 3) & 3) << 4;      // the switches read per forward that change the launch sequence
     if (net->graph_split != plan_key) {        // the launch plan changes: cached graphs are stale (as in nope_unet_x2_enable)
         for (const UGraph& g : net->graphs) hipGraphExecDestroy(g.exec);
         net->graphs.clear();

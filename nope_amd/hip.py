@@ -16,7 +16,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 18                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 19                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -85,7 +85,8 @@ class ConvOp(C.Structure):
                 ("Cout", _i), ("n_hyp", _i), ("out_nchw", _i), ("out_dtype", _i), ("act_relu", _i), ("splitk_ws", _vp), ("splitk_bytes", _sz),
                 ("colstats", _vp), ("stat_rows", _i), ("pn_ms", _vp), ("pn_c0", _vp), ("pn_c1", _vp),
                 ("tail_colstats", _vp), ("tail_stat_blocks", _i), ("gn_gamma", _vp), ("gn_beta", _vp), ("gn_G", _i), ("gn_eps", C.c_float),
-                ("gn_ms", _vp), ("tail_stats", _vp), ("amax_slot", _vp), ("amax_out", _vp)]
+                ("gn_ms", _vp), ("tail_stats", _vp), ("amax_slot", _vp), ("amax_out", _vp),
+                ("gn_emb", _vp), ("gn_emb_stride", _i), ("gn_self", _i), ("gn_resid_rep", _i)]
 
 
 class ConvOpInfo(C.Structure):
@@ -1330,6 +1331,24 @@ def op_conv_gn_tail(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional
     if want_amax:
         extras["amax"] = float(amax.item())
     return s.out, extras
+
+
+def op_conv_gn_self(dt: int, src1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor, groups: int,
+                    emb: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, src2: Optional[torch.Tensor] = None, eps: float = 1e-5,
+                    split_k: bool = False, want_amax: bool = False, x2_shift: int = 0, out: Optional[torch.Tensor] = None):
+    """SiLU(GroupNorm(groups)(conv3x3(src1 [cat src2]) + bias)) [+ emb[sample]] [+ resid] in ONE launch (nope_conv_op's gn_self, include/nope_hip.h):
+    the conv forms the statistics of its own output.  A combination the launcher refuses raises NopeError (NOPE_ERR_UNSUPPORTED) with nothing
+    launched; `out` (optional) is the buffer to write, so a caller can see that a refusal left it alone.  Returns out, or (out, max |out|)."""
+    s = _conv_setup(dt, src1, w, bias, src2, CONV_PLAIN, 1, None, False, F32, split_k, x2_shift)
+    if out is not None:
+        assert tuple(out.shape) == tuple(s.out.shape) and out.dtype == s.out.dtype and out.is_contiguous()
+        s.op["out"] = out
+    e = None if emb is None else _f32c(emb)
+    slot, amax = _amax_scratch(src1.device) if want_amax else (None, None)
+    _conv_call(_stream(src1), resid=resid, gn_gamma=_f32c(gamma), gn_beta=_f32c(beta), gn_G=groups, gn_eps=float(eps), gn_self=1, gn_emb=e,
+               gn_emb_stride=0 if e is None else e.shape[1], amax_slot=slot, amax_out=amax, **s.op)
+    res = s.op["out"]
+    return (res, float(amax.item())) if want_amax else res
 
 
 def op_gn_apply_blocks(dt: int, hw: int, c: int, n_hyp: int) -> int:
