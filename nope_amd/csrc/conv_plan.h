@@ -83,6 +83,7 @@ struct ConvParams {
     int gn_cpg;                        // Cout / gn_G
     float gn_eps;
     const float* gn_emb; int gn_emb_stride;
+    int padskip;                       // 1: the tap-resident kernel's form for 4 x 4 maps that stages a tile in (position, sample) order and skips the MFMA blocks that lie wholly in the padding (conv3x3_halo_kernel, PADSKIP)
 };
 
 }  // namespace

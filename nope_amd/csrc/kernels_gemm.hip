@@ -263,7 +263,7 @@ struct OptSwitch { bool set; int val; };      // a switch for which "unset" is n
 struct ConvSwitches {
     int pp, variant, small_mode, small_max_tiles, small_1x1_maxk, small_deep_max, small_kg2_max, halo_split_min_chunks, halo_split_max_tiles, halo_min_tiles, halo_persist, up2p_halo;
     int stream, stream_grid, stream_min_iters, persist_grid, geglu_fused;
-    bool halo_split, x2_small, x2_pp, geglu_fused_f32, stats16, nchw_staged, xcd_one_panel, xcd_any, persist, lean;
+    bool halo_split, x2_small, x2_pp, geglu_fused_f32, stats16, nchw_staged, xcd_one_panel, xcd_any, persist, lean, halo_padskip;
     OptSwitch small_tile, xcd_gn, pp_variant;
 };
 static ConvSwitches read_switches(int dt) {      // dt: a base type (the default of NOPE_CONV_PP depends on it)
@@ -282,6 +282,7 @@ static ConvSwitches read_switches(int dt) {      // dt: a base type (the default
     s.halo_min_tiles = NOPE_ENV("NOPE_HALO_MIN_TILES", 128);                 // long 3x3 convs take the tap-resident kernel from this many tiles on
     s.halo_persist = NOPE_ENV("NOPE_HALO_PERSIST", 256);                     // workgroups of its tile walk (0: one tile per workgroup)
     s.up2p_halo = NOPE_ENV("NOPE_UP2P_HALO", 1);                             // phase convs tap-resident: 0 never, 1 two-pass layers, 2 bf16x3 too
+    s.halo_padskip = NOPE_ENV("NOPE_HALO_PADSKIP", 1) != 0;                  // 0: 4 x 4 maps in (sample, position) order, every block-tap executed (A/B)
     s.stream = NOPE_ENV("NOPE_CONV_STREAM", 0);                              // streaming 1x1 kernel: bit 0 the 128 x 192 kernel's launches, bit 1 the per-tap ping-pong kernel's
     s.stream_grid = NOPE_ENV("NOPE_STREAM_GRID", 256);                       // its workgroups: one per CU (the tests walk small grids); a multiple of 8, else 256
     if (s.stream_grid < 8 || s.stream_grid % 8) s.stream_grid = 256;
@@ -448,7 +449,8 @@ int conv_tail_stat_blocks(int HW, int Cout) { return HW / 64 * cdiv(Cout, 96); }
 // Which kernel a conv asks for.  NOPE_CONV_PP (tuning; default 3): bit 0 = the 256 x 192 ping-pong kernels for launches with
 // at least one 256-row tile per CU, bit 1 = also for the small-map 3x3 convs that would otherwise run position-major on
 // the 128 x 192 kernel (they then run in standard row order, all 9 taps, on the tap-resident kernel: 239 vs 257 us for
-// 1536 -> 1536 at 4 x 4 x 512 although it executes the 31 % of MACs the position-major order skips), bit 2 = those run position-major on the
+// 1536 -> 1536 at 4 x 4 x 512 although it executed the 31 % of MACs the position-major order skips; since then the tap-resident kernel's PADSKIP form,
+// plan_epilogue, leaves out those that are padding for a whole 32-row block of a (position, sample) stage, 1/6 of the K loop), bit 2 = those run position-major on the
 // ping-pong kernel (needs nhyp % 256 == 0), bit 3 = no minimum tile count (tests: small shapes on the ping-pong kernel),
 // bit 4 = 3x3 convs per tap on the ping-pong kernel instead of the tap-resident (halo) kernel.
 struct KernelChoice { bool pp, posmajor, halo; int small; int hsplit; bool stream; };      // hsplit > 1: tap-resident kernel with that many K splits; stream: asked for -- plan_walks keeps it only if the grid fits
@@ -758,6 +760,12 @@ static int plan_epilogue(ConvLaunch& L, const ConvArgs& a, const ConvSwitches& s
         p.resid = (const unsigned char*)a.gn_resid;
         p.stat_rows = HW == 16 ? 16 : 64;
     }
+    // The tap-resident kernel's padding-skipping form (conv3x3_halo_kernel, PADSKIP) for the 4 x 4 level: a 256-row tile of 16 whole samples staged in
+    // (position, sample) order, 12 of the 72 MFMA block-taps of a channel chunk -- those that lie wholly in the zero padding -- not executed, the
+    // accumulators exchanged through LDS before the unchanged lean epilogue (so one tile per workgroup: the exchange takes the LDS a walk's next
+    // prologue would write).  A flag of the same launch kind; results are the sample-major form's.  NOPE_HALO_PADSKIP=0: that form (A/B).
+    p.padskip = (s.halo_padskip && pick.halo && !phased && p.lean && a.mode == NOPE_CONV_PLAIN && a.ntaps == 9 && a.Hs == 4 && a.Ws == 4 && M % 256 == 0 && p.splits == 1 &&
+                 p.persist_iters == 1 && a.rep1 == 1 && !(a.C2 > 0 && a.rep2 > 1) && s.variant == 0 && !s.pp_variant.set) ? 1 : 0;
     return NOPE_OK;
 }
 
@@ -816,9 +824,9 @@ static void trace_conv(const ConvLaunch& L) {
     const int Cin = p.C1 + p.C2;
     if (L.kind == NOPE_CONV_KERNEL_SMALL) fprintf(stderr, "conv small%d mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u xcd %d/%d\n", L.small, p.mode, p.ntaps, Cin, p.Cout, (long long)p.M,
                                                  p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z, p.xcd_map, p.xcd_gn);
-    else fprintf(stderr, "conv %s mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u posmajor %d persist %d xcd %d/%d%s%s\n",
+    else fprintf(stderr, "conv %s mode %d taps %d Cin %d Cout %d M %lld tiles %dx%d grid %u,%u,%u posmajor %d persist %d xcd %d/%d%s%s%s\n",
                  names[L.kind], p.mode, p.ntaps, Cin, p.Cout, (long long)p.M, p.tiles_m, p.tiles_n, L.grid.x, L.grid.y, L.grid.z,
-                 p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, p.geglu ? " geglu" : L.x2 ? " x2" : "", p.gn_ms ? " lean gn-tail" : p.gn_self ? " lean gn-self" : p.lean ? " lean" : "");
+                 p.posmajor, p.persist_iters, p.xcd_map, p.xcd_gn, p.padskip ? " padskip" : "", p.geglu ? " geglu" : L.x2 ? " x2" : "", p.gn_ms ? " lean gn-tail" : p.gn_self ? " lean gn-self" : p.lean ? " lean" : "");
 }
 
 // fn((T*)nullptr) with T the type a tensor of `dt` is stored in (the reduce kernels of a split launch write it)

@@ -445,6 +445,13 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv_gemm_pp_kernel(ConvPara
 // fragment addresses are one register per K sub-step plus instruction immediates (the B ring sits at LDS offset 0 so
 // they fit 16 bits), and the K offsets of the DMA pieces travel in the scalar offset operand: ~20 ds_read + 4 DMA +
 // a few dozen scalar/vector instructions per step.
+// How the PADSKIP form of conv3x3_halo_kernel leaves a block-tap out (compile time, A/B builds: build.py --variant): bit 0 = its fragment reads are skipped
+// too, not only its MFMAs; bit 1 = at the taps where one group skips, the MFMAs run fragment row by fragment row, the row that may be skipped LAST and
+// behind ONE wave-uniform branch (each accumulator still sees its products in the same order).  Without bit 1 the branch sits inside every MFMA group
+// of the phase: six branches cut the phase into blocks the register allocator cannot hold 96 accumulators across -- 16 .. 240 bytes of scratch.
+#ifndef NOPE_PADSKIP_FORM
+#define NOPE_PADSKIP_FORM 3
+#endif
 constexpr int HALO_ROWS = 328;       // 256 + 2 * (32 + 1), rounded up to whole 8-row pieces: maps up to 32 pixels wide
 constexpr int HALO_MAX_W = 32;
 
@@ -494,11 +501,26 @@ template <class T, bool TIMELINE, bool SELF> struct HaloLds {
 };
 
 // (No split-K launch is lean, so the pair SPLIT_ && LEAN names this form: the existing instantiations keep their names.)
-template <class T, bool TIMELINE = false, bool SPLIT_ = false, bool SHIFT = true, bool LEAN = false, bool UP = false>
+// PADSKIP (ConvParams::padskip; 4 x 4 maps, f32 storage, lean epilogue, one tile per workgroup): a 256-row tile is 16 whole samples x 16 positions and
+// is staged in (position, sample) order -- stage row s = pos * 16 + n_local, no halo: every neighbour outside the tile's own 256 rows is padding -- so
+// a 32-row MFMA block is two POSITIONS of all 16 samples, and a tap that is padding for both is padding for the whole block: blocks 0, 1 (y = 0) at
+// the three taps with dy = -1, blocks 6, 7 (y = 3) at the three with dy = +1 -- 12 of the 72 block-taps of a chunk, fragment reads and MFMAs of every
+// term, are not executed (they would have added exact zeros).  Wave row wm holds blocks {0, 2} / {1, 3} / {4, 6} / {5, 7} (its two fragment rows 64
+// stage rows apart), so BOTH wave rows of a group skip at the same taps -- group 0 at taps 0..2, group 1 at taps 6..8 -- and the group's COMPUTE
+// phase there, which lasts as long as its busiest wave, is half as long: 15 phase units per chunk in place of 18.  Loading is the resident form's:
+// a piece is 8 consecutive stage rows of one 128-byte line each, its global offset linear in the piece index (piece i of a wave: position
+// (wave >> 1) + 4 i of sample 8 (wave & 1) + rsub); a tap is the constant stage-row offset (4 dy + dx) * 16; the in-place rewrite works per stage row.
+// After the K loop the waves exchange accumulators through LDS (free then: one tile per workgroup), one 32-column block at a time, so that every wave
+// holds exactly the array of the sample-major form and the epilogue -- whose summation orders make the fused forms bit-identical to the unfused
+// ones -- is called unchanged.
+// (No timeline launch is lean, so the pair TIMELINE_ && LEAN names this form: the existing instantiations keep their names.)
+template <class T, bool TIMELINE_ = false, bool SPLIT_ = false, bool SHIFT = true, bool LEAN = false, bool UP = false>
 __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvParams p) {
     constexpr bool SELF = SPLIT_ && LEAN, SPLIT = SPLIT_ && !LEAN;
+    constexpr bool PADSKIP = TIMELINE_ && LEAN, TIMELINE = TIMELINE_ && !LEAN;
     static_assert(!UP || (!TIMELINE && !SPLIT && !LEAN), "the phase-conv form: one tile per workgroup, generic wide epilogue");
     static_assert(!SELF || (!TIMELINE && !UP && sizeof(T) == 4), "the kernel's own GroupNorm: the lean epilogue, f32 storage");
+    static_assert(!PADSKIP || (!UP && sizeof(T) == 4 && Tile<T>::TM == 32), "the padding-skipping form: f32 storage on the 32 x 32 tiles, lean epilogue");
     typedef Tile<T> TL;
     constexpr int VEC = Elt<T>::VEC;
     constexpr unsigned ES = (unsigned)sizeof(T);
@@ -556,7 +578,8 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
     const int W = p.Ws, HW = p.Hs * p.Ws;
     const int halo = W + 1;
     const int Cin = p.C1 + p.C2;
-    const int npieces = (PP_BM + 2 * halo + 7) >> 3;               // 8-row pieces of a stage (33 .. 41)
+    const int npieces = PADSKIP ? PP_BM >> 3 : (PP_BM + 2 * halo + 7) >> 3;      // 8-row pieces of a stage (33 .. 41; PADSKIP: no halo, 32)
+    constexpr int FSTRIDE = PADSKIP ? 64 : TL::TM;                 // stage rows between a wave's fragment rows
     const int ph_y = UP ? ((int)blockIdx.y >> 1) : 0, ph_x = UP ? ((int)blockIdx.y & 1) : 0;      // UP: the output phase of this workgroup
     constexpr unsigned NTAPS = UP ? 4u : 9u;
 
@@ -574,8 +597,10 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
     const int rsub = lane >> 3, lslot = lane & 7;
     const int r0 = 8 * wave + rsub;
     const unsigned a_cs = (unsigned)((lslot ^ swz_of<RB>(r0)) * VEC);
-    unsigned a_base1 = (unsigned)((m0 - halo + r0) * p.C1 + (int)a_cs) * ES;
-    const unsigned a_step1 = 64u * (unsigned)p.C1 * ES;
+    // (PADSKIP: stage row 64 i + r0 holds position (wave >> 1) + 4 i of the tile's sample 8 (wave & 1) + rsub: tile row ps_row0 + 4 i)
+    const int ps_row0 = PADSKIP ? ((wave & 1) * 8 + rsub) * 16 + (wave >> 1) : 0;
+    unsigned a_base1 = (unsigned)((PADSKIP ? m0 + ps_row0 : m0 - halo + r0) * p.C1 + (int)a_cs) * ES;
+    const unsigned a_step1 = (PADSKIP ? 4u : 64u) * (unsigned)p.C1 * ES;
     const bool a_has4 = wave + 32 < npieces, a_has5 = wave + 40 < npieces;      // (pieces 0..3 of a wave always exist)
     unsigned char* const a_dst = lds + A_BASE + wave * 1024;                    // + stage * A_STAGE + i * 8192
     // piece i of this wave for the chunk described by (first, a_soff).  The channel offset rides in the scalar operand (it stays
@@ -590,7 +615,7 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
 #define NOPE_HALO_SET_OFF2()                                                                                                     \
     do {                                                                                                                         \
         _Pragma("unroll") for (int i = 0; i < 6; ++i) {                                                                           \
-            const int m = m0 - halo + r0 + 64 * i;                                                                               \
+            const int m = PADSKIP ? m0 + ps_row0 + 4 * i : m0 - halo + r0 + 64 * i;                                              \
             unsigned o = (unsigned)(m * p.C2 + (int)a_cs) * ES;                                                                  \
             if (a_rep2) {                                                                                                        \
                 const unsigned b = p.d_hw.div((unsigned)(m < 0 ? 0 : m)), r = (unsigned)m - b * (unsigned)HW;                    \
@@ -744,16 +769,28 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
     // 80 fragment registers, and a spilled table is reloaded through vmcnt, which would drain the DMA queue.
     unsigned f_mask[TL::MT];
     const int fslot = TL::frag_slot(lane);
+    const int ps_blk0 = (wm & 1) + 4 * (wm >> 1);                 // PADSKIP: fragment row i of wave row wm is the 32-row block ps_blk0 + 2 i of the stage
 #pragma unroll
     for (int i = 0; i < TL::MT; ++i) {
+        if constexpr (PADSKIP) {                                   // the position of stage row s is s >> 4, on the 4 x 4 map
+            const int pos = ((ps_blk0 + 2 * i) * 32 + TL::frag_row(lane)) >> 4;
+            const int oy = pos >> 2, ox = pos & 3;
+            const unsigned vx = (ox > 0 ? 1u : 0u) | 2u | (ox < 3 ? 4u : 0u);
+            f_mask[i] = (oy > 0 ? vx : 0u) | (vx << 3) | (oy < 3 ? vx << 6 : 0u);
+        } else {
         const int il = wm * 64 + i * TL::TM + TL::frag_row(lane);
         const unsigned m = (unsigned)(m0 + il);
         const unsigned b = p.d_hw.div(m), r = m - b * (unsigned)HW;
         const int oy = (int)p.d_w.div(r), ox = (int)r - oy * W;
         const unsigned vx = (ox > 0 ? 1u : 0u) | 2u | (ox + 1 < W ? 4u : 0u);
         f_mask[i] = (oy > 0 ? vx : 0u) | (vx << 3) | (oy + 1 < p.Hs ? vx << 6 : 0u);
+        }
     }
-    const int f_row0 = wm * 64 + TL::frag_row(lane) + halo;       // fragment row i sits i * TM stage rows further
+    const int f_row0 = PADSKIP ? ps_blk0 * 32 + TL::frag_row(lane) : wm * 64 + TL::frag_row(lane) + halo;       // fragment row i sits i * FSTRIDE stage rows further
+    // PADSKIP: the block-taps that lie wholly in the padding (fragment row i of this wave at tap `tap`): wave-uniform, `i` and `tap` are unrolled
+    auto ps_skip = [&](int i, int tap) __attribute__((always_inline)) -> bool {
+        return PADSKIP && (tap < 3 ? (i == 0 && grp == 0) : tap >= 6 ? (i == 1 && grp == 1) : false);
+    };
     // B: the swizzle of rows wn*96 + j*TM + l does not depend on j (48 wn and j TM / 2 are multiples of 8): one address per
     // K sub-step, tile j and ring stage are immediates
     int fbk[KK];
@@ -802,7 +839,7 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
     }
     // A workgroup walks `iters` tiles of the same weight panel, gridDim.x / 8 M tiles apart (a multiple of the image size:
     // checked by the launcher, so the padding masks above hold for every tile of the walk).
-    const int iters = !UP && TL::TM == 32 && p.persist_iters > 1 ? p.persist_iters : 1;
+    const int iters = !UP && !PADSKIP && TL::TM == 32 && p.persist_iters > 1 ? p.persist_iters : 1;      // (PADSKIP: the accumulator exchange takes the whole LDS, conv_plan grants it to one tile per workgroup)
     const int walk_rows = (int)(gridDim.x >> 3) / (p.xcd_map == 2 ? p.tiles_n / p.xcd_gn : 1) * PP_BM;
     tile_prologue();
     // Tuning only (NOPE_PP_VARIANT & 2048): touch the workgroup's whole weight stream up front -- one 4-byte load per 128-byte weight row
@@ -869,10 +906,10 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
             u32x4 af[KS][RAW][TL::MT], bfr[KS][RAW][TL::NTL];
             int fa[TL::MT];
             auto tap_addresses = [&](int tp, int (&dst)[TL::MT]) __attribute__((always_inline)) {
-                const int toff = (tp / 3 - 1) * W + (tp % 3 - 1);          // scalar: the tap's row offset along the flat pixel axis
+                const int toff = PADSKIP ? ((tp / 3 - 1) * 4 + (tp % 3 - 1)) * 16 : (tp / 3 - 1) * W + (tp % 3 - 1);      // scalar: the tap's row offset along the flat pixel axis (PADSKIP: 16 stage rows per position)
 #pragma unroll
                 for (int i = 0; i < TL::MT; ++i) {
-                    const int rr = frow + i * TL::TM + toff;
+                    const int rr = frow + i * FSTRIDE + toff;
                     const int off = A_BASE + (rr << 7) + (((fslot ^ (rr >> 1)) & 7) << 4);
                     dst[i] = ((f_mask[i] >> tp) & 1u) ? off : A_BASE + ZROW;   // (absolute, stage 0)
                 }
@@ -889,7 +926,10 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
 #pragma unroll
-                for (int i = 0; i < TL::MT; ++i) af[kk / RAW][kk % RAW][i] = ld16(lds + (fa[i] ^ (raw_slot<T>(kk) << 4)) + par * A_STAGE);
+                for (int i = 0; i < TL::MT; ++i) {
+                    if constexpr (PADSKIP && (NOPE_PADSKIP_FORM & 1)) { if (ps_skip(i, tap)) continue; }
+                    af[kk / RAW][kk % RAW][i] = ld16(lds + (fa[i] ^ (raw_slot<T>(kk) << 4)) + par * A_STAGE);
+                }
 #pragma unroll
                 for (int j = 0; j < TL::NTL; ++j) bfr[kk / RAW][kk % RAW][j] = ld16(lds + fbk[kk] + ((tap % 3) * B_STAGE + j * TL::TM * RB));
             }
@@ -907,6 +947,8 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
                 //  re-converts whatever the other stage holds, which nothing reads before the next tile's prologue refills it.)
                 constexpr bool CV = CV_IN_COMPUTE;
                 const bool cv_c = CV && tap >= 1 && tap <= 4;
+                const bool ps_tap = PADSKIP && (tap < 3 || tap >= 6);      // a tap at which one group skips fragment row ps_i
+                const int ps_i = tap < 3 ? 0 : 1;
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
@@ -924,9 +966,12 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
                             tap_addresses((tap + 1) % 9, fa_next);
                         }
 #pragma unroll
-                        for (int i = 0; i < TL::MT; ++i)
+                        for (int i = 0; i < TL::MT; ++i) {
+                            if constexpr (PADSKIP && (NOPE_PADSKIP_FORM & 2)) { if (ps_tap && i == ps_i) continue; }
+                            else if constexpr (PADSKIP) { if (ps_skip(i, tap)) continue; }
 #pragma unroll
                             for (int j = 0; j < TL::NTL; ++j) TL::mma(t, af[ks], bfr[ks], i, j, acc[i][j], x2_sc);
+                        }
                         if (cv_c && g == 2) {
                             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);         // the read
                             __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);         // three MFMAs cover its latency
@@ -945,6 +990,16 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
+                if constexpr (PADSKIP && (NOPE_PADSKIP_FORM & 2)) {
+                    if (ps_tap && !ps_skip(ps_i, tap)) {
+#pragma unroll
+                        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                            for (int t = 0; t < TL::TERMS; ++t)
+#pragma unroll
+                                for (int j = 0; j < TL::NTL; ++j) TL::mma(t, af[ks], bfr[ks], ps_i, j, acc[ps_i][j], x2_sc);
+                    }
+                }
             } else {
 #pragma unroll
                 for (int kk = 0; kk < KK; ++kk) {
@@ -1100,7 +1155,7 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
     if constexpr (FA_AHEAD && !UP) {                               // tap 0 of the first step (the row geometry is the same for every tile of a walk)
 #pragma unroll
         for (int i = 0; i < TL::MT; ++i) {
-            const int rr = f_row0 + i * TL::TM - W - 1;
+            const int rr = f_row0 + i * FSTRIDE - (PADSKIP ? 5 * 16 : W + 1);
             fa_next[i] = (f_mask[i] & 1u) ? A_BASE + (rr << 7) + (((fslot ^ (rr >> 1)) & 7) << 4) : A_BASE + ZROW;
         }
     }
@@ -1136,6 +1191,38 @@ __global__ __launch_bounds__(PP_WAVES * 64, 2) void conv3x3_halo_kernel(ConvPara
         // prologue now -- it lands while the panels are filled -- and wait for it before the first store of the epilogue
         // (so the K loop's vmcnt never has to wait for a prologue behind a queue of stores).
         if constexpr (X2 && NOPE_X2_KERNEL_AMAX) x2_publish_amax(p, x2_amax, lane);
+        if constexpr (PADSKIP) {
+            // The accumulator exchange: this wave's rows are the stage rows of blocks ps_blk0, ps_blk0 + 2 -- stage row s = tile row
+            // (s & 15) * 16 + (s >> 4) -- and the epilogue wants tile rows wm * 64 .. + 63 in the same C/D layout.  One 32-column block j of every wave
+            // at a time: [wave column][tile row][32 columns] floats = 64 KiB, two regions in turn, so one barrier per block separates the writes of
+            // block j from its reads AND the reads of block j - 1 from the writes of block j + 1 into the same region (a wave waits for its own reads
+            // before it arrives).  The values are moved, not recomputed: each element has seen the products of the sample-major form in its K order.
+            static_assert(2 * 65536 <= LDS_USED, "two exchange regions");
+            int xlane = lane;
+            NOPE_OPAQUE_VGPR(xlane);                               // (keeps the exchange's lane arithmetic here, out of the K loop's registers)
+            float* const xch = reinterpret_cast<float*>(lds) + wn * (PP_BM * 32) + TL::out_col(xlane);
+#pragma unroll
+            for (int j = 0; j < TL::NTL; ++j) {
+                float* const reg = xch + (j & 1) * (2 * PP_BM * 32);
+#pragma unroll
+                for (int i = 0; i < TL::MT; ++i)
+#pragma unroll
+                    for (int r = 0; r < TL::R; ++r) {
+                        const int s = (ps_blk0 + 2 * i) * 32 + TL::out_row(xlane, r);
+                        reg[((s & 15) * 16 + (s >> 4)) * 32] = acc[i][j][r];
+                    }
+                __builtin_amdgcn_s_waitcnt(WAIT_LGKMCNT0);
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < TL::MT; ++i)
+#pragma unroll
+                    for (int r = 0; r < TL::R; ++r) acc[i][j][r] = reg[(wm * 64 + i * TL::TM + TL::out_row(xlane, r)) * 32];
+            }
+            __builtin_amdgcn_s_waitcnt(WAIT_LGKMCNT0);             // my reads are done: behind the barrier the epilogue's panels and column sums may take the LDS
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+        }
         const int m_this = m0;
         const bool more = it + 1 < iters;
         if (more) {
@@ -1245,6 +1332,16 @@ void launch_conv_halo(int dt, const void* params, dim3 grid, hipStream_t s) {
         else if (dt == NOPE_F16X2 && p.x2_t_zero) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, true, false>), grid, block, 0, s, p);
         else if (dt == NOPE_F16X2) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, false, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((conv3x3_halo_kernel<bf16_t, false, true>), grid, block, 0, s, p);
+        return;
+    }
+    if (p.padskip) {                                   // (conv_plan: 4 x 4 maps, lean or the kernel's own GroupNorm, one tile per workgroup; <.., TIMELINE_ = true, .., LEAN = true>: the form's own instantiations)
+        if (p.gn_self) {
+            if (dt == NOPE_BF16X3) hipLaunchKernelGGL((conv3x3_halo_kernel<f32s_t, true, true, true, true>), grid, block, 0, s, p);
+            else if (p.x2_t_zero) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, true, true, false, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, true, true, true, true>), grid, block, 0, s, p);
+        } else if (dt == NOPE_BF16X3) hipLaunchKernelGGL((conv3x3_halo_kernel<f32s_t, true, false, true, true>), grid, block, 0, s, p);
+        else if (p.x2_t_zero) hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, true, false, false, true>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((conv3x3_halo_kernel<f16x2_t, true, false, true, true>), grid, block, 0, s, p);
         return;
     }
     if (p.gn_self) {                                   // (conv_plan: lean, f32 storage in bf16x3 / f16x2; <.., SPLIT_ = true, .., LEAN = true>: the form's own instantiation)

@@ -92,7 +92,7 @@ struct nope_unet : rt::Net {      // (dt / sdt / x2 / x2r / allocs: rt::Net, run
     mutable std::vector<UGraph> graphs;
     mutable bool graphs_ok = true;           // cleared when capture is unavailable: direct launches from then on
     mutable std::mutex graph_mu;
-    mutable int graph_split = -1;            // NOPE_SHARED_SPLIT | NOPE_RES_TAIL << 2 | NOPE_GN_EPI << 4 the cached graphs were captured under
+    mutable int graph_split = -1;            // NOPE_SHARED_SPLIT | NOPE_RES_TAIL << 2 | NOPE_GN_EPI << 4 | NOPE_HALO_PADSKIP << 6 the cached graphs were captured under
     mutable int graph_replays = 0;           // forwards served by a graph replay since create (tests assert the path really ran)
     long long graph_max = 0;                 // largest n_hyp * H * W that replays a graph; 0 = off
 };
@@ -826,7 +826,8 @@ int nope_unet_forward(const nope_unet* net, const float* x, int n_src, int x_rep
     q.n_src = n_src; q.x_rep = x_rep; q.n_hyp = n_hyp; q.H = H; q.W = W; q.split = split;
     if (!want_graph) return run_forward(net, q, base, avail, s);
     std::lock_guard<std::mutex> lock(net->graph_mu);
-    const int plan_key = split | (NOPE_ENV("NOPE_RES_TAIL", 1) & 3) << 2 | (NOPE_ENV("NOPE_GN_EPI", 3) & 3) << 4;      // the switches read per forward that change the launch sequence
+    const int plan_key = split | (NOPE_ENV("NOPE_RES_TAIL", 1) & 3) << 2 | (NOPE_ENV("NOPE_GN_EPI", 3) & 3) << 4 |
+                         (NOPE_ENV("NOPE_HALO_PADSKIP", 1) != 0) << 6;      // the switches read per forward that change the launch sequence, and the conv planner's NOPE_HALO_PADSKIP (another kernel form in the captured launches)
     if (net->graph_split != plan_key) {        // the launch plan changes: cached graphs are stale (as in nope_unet_x2_enable)
         for (const UGraph& g : net->graphs) hipGraphExecDestroy(g.exec);
         net->graphs.clear();
