@@ -92,9 +92,10 @@ typedef void* nope_stream_t;
  *     nope_op_conv_ws, nope_op_conv_ex, nope_op_conv_gn_tail, nope_op_conv_splitk_bytes, nope_op_conv_stat_rows, nope_op_conv_tail_stat_blocks,
  *     nope_op_group_norm_ex and nope_op_group_norm_shared);
  * 18: nope_op_pose_modes;
- * 19: nope_conv_op gains gn_emb, gn_emb_stride, gn_self, gn_resid_rep (the conv's own GroupNorm).  Callers compare nope_abi_version() against the header they were
+ * 19: nope_conv_op gains gn_emb, gn_emb_stride, gn_self, gn_resid_rep (the conv's own GroupNorm);
+ * 20: nope_op_c2f_expand, nope_op_c2f_commit.  Callers compare nope_abi_version() against the header they were
  * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 19
+#define NOPE_ABI_VERSION 20
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -181,6 +182,47 @@ int nope_op_pose_modes(const float* similarity, int64_t similarity_ld, const dou
                        const int* symmetry, double temperature, double radius_rad, int max_modes, int fill, float* prob, int64_t prob_ld,
                        float* entropy, int64_t* mode_idx, float* mode_score, float* mode_mass, int* mode_count, int* n_modes, int* status,
                        int B, nope_stream_t stream);
+
+/* (ABI 20) Coarse-to-fine pose retrieval over nested viewpoint grids.  No reference counterpart: the reference
+ * scores every pose of the grid (src/model/model.py:313,323).  Icosphere levels are nested, so a query can be scored in stages: the coarsest
+ * level, then the finer-level neighbours of its best few poses, and so on.  The caller's loop (nope_amd/search.py: coarse_to_fine_search):
+ *     nope_op_c2f_expand (no seeds);  scores of `rows` (nope_unet_forward + nope_similarity);  nope_op_c2f_commit
+ *     stages x { nope_topk of the sparse row -> seeds;  nope_op_c2f_expand;  scores of `rows`;  nope_op_c2f_commit };  nope_topk
+ * The sparse score row holds -inf where nothing was evaluated: an ordinary input to nope_topk, nope_op_pose_modes and nope_op_refine_select.
+ * Both entries: one workgroup per query, no workspace, nothing read by the host, no floating-point atomics, plain vector stores only, and
+ * byte-identical output from run to run (the slot of a candidate comes from a block-wide prefix scan, never from thread timing).
+ *
+ * nope_op_c2f_expand chooses this stage's candidates and gathers their pose rows.
+ *   template_poses  (B|1, N, 3, 3) f64, sample stride pose_stride_b elements (0 = one grid for every query, as nope_op_pose_modes)
+ *   stage_of        (N) int32: the first stage at which a pose is eligible; shared by the batch
+ *   state           (B, N) uint8, in/out: 0 = not evaluated, 1 = evaluated or chosen
+ *   seeds           (B, n_seeds) int64, as nope_topk writes them; n_seeds in [0, 16] (0: may be NULL)
+ *   all_relativeR   (B, N, 6) f32
+ * A pose p is eligible when stage_of[p] <= max_stage and state[b, p] == 0.  n_seeds == 0 (stage 0): every eligible pose is a candidate, in
+ * ascending index order.  Otherwise, for each seed in the given order: the eligible poses p != seed with d(poses[p], poses[seed]) <=
+ * radius_rad (a NaN distance never qualifies), in ascending index order; a pose is a candidate once, under the first seed that reaches it.
+ * The seed itself is never a candidate of its own pass: it is already evaluated.  The first `capacity` candidates of that sequence are
+ * emitted and get state = 1; the rest are dropped: their state stays 0 and n_dropped[b] counts each of them once.
+ * The distance d is f64.  dist_kind 0, rotation: theta(A, B) = acos(clamp((tr(A B^T) - 1) / 2, -1, 1)), exactly nope_op_pose_modes'.
+ * dist_kind 1, viewpoint: the clamped acos of the cosine between the third ROWS P[2, :] (norms floored at 1e-8) -- the camera's optical
+ * axis in the object frame.  It is NOT nope_op_pose_modes' symmetry class 2, whose axis -inv(P)[2, :] is the third column and depends on
+ * the elevation only.
+ *   cand       (B, capacity) int32: the candidates in emission order, then -1
+ *   n_cand, n_dropped  (B) int32
+ *   rows       (B, capacity, 6) f32: the exact bits of all_relativeR[b, cand].  A padded slot carries the row of the query's first valid
+ *              seed (n_seeds == 0, or no valid seed: the row of pose 0): the U-Net sees a finite pose, and its score is discarded.
+ *   status     one device int, zeroed by the call: bit 0 = a query overflowed `capacity`, bit 1 = a seed outside [0, N) (it is skipped).
+ * NOPE_ERR_ARG, before anything is launched or written: N < 1; capacity < 1; n_seeds outside [0, 16]; radius_rad NaN or < 0 with
+ * n_seeds > 0; dist_kind not 0 or 1; a missing pointer.  "Reached by an earlier seed" is a flag in LDS, laid out as nope_op_pose_modes'
+ * alive flags: N <= 262144, NOPE_ERR_UNSUPPORTED beyond.
+ *
+ * nope_op_c2f_commit writes scores[b, j] ((B, capacity) f32) into similarity[b, cand[b, j]] ((B, N) f32, row stride similarity_ld >= N)
+ * for every 0 <= cand < N, bit for bit (NaN included); -1 is skipped; nothing else is touched, columns >= N included. */
+int nope_op_c2f_expand(const double* template_poses, int64_t pose_stride_b, int N, const int* stage_of, int max_stage, uint8_t* state,
+                       const int64_t* seeds, int n_seeds, double radius_rad, int dist_kind, const float* all_relativeR, int capacity, int* cand,
+                       int* n_cand, int* n_dropped, float* rows, int* status, int B, nope_stream_t stream);
+int nope_op_c2f_commit(const float* scores, const int* cand, int capacity, int N, float* similarity, int64_t similarity_ld, int B,
+                       nope_stream_t stream);
 
 /* (ABI 15) Sub-grid pose refinement: Gauss-Newton on SO(3) through the U-Net.  No reference counterpart: the reference's prediction is
  * template_poses[nearest_idx] (src/model/model.py:352-354), a vertex of the template grid (26 templates: ~32 degrees apart).  The U-Net is a

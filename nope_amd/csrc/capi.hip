@@ -134,6 +134,18 @@ int nope_op_pose_modes(const float* similarity, int64_t similarity_ld, const dou
                              status, B, (hipStream_t)stream);
 }
 
+int nope_op_c2f_expand(const double* template_poses, int64_t pose_stride_b, int N, const int* stage_of, int max_stage, uint8_t* state,
+                       const int64_t* seeds, int n_seeds, double radius_rad, int dist_kind, const float* all_relativeR, int capacity, int* cand,
+                       int* n_cand, int* n_dropped, float* rows, int* status, int B, nope_stream_t stream) {
+    return launch_c2f_expand(template_poses, (long long)pose_stride_b, N, stage_of, max_stage, state, (const long long*)seeds, n_seeds, radius_rad,
+                             dist_kind, all_relativeR, capacity, cand, n_cand, n_dropped, rows, status, B, (hipStream_t)stream);
+}
+
+int nope_op_c2f_commit(const float* scores, const int* cand, int capacity, int N, float* similarity, int64_t similarity_ld, int B,
+                       nope_stream_t stream) {
+    return launch_c2f_commit(scores, cand, capacity, N, similarity, (long long)similarity_ld, B, (hipStream_t)stream);
+}
+
 int nope_op_refine_init(const float* all_relativeR, int64_t N, const int64_t* idx, double* dR, double* dR_init, float* poses, int* status,
                         int B, int k, double fd_step, nope_stream_t stream) {
     return launch_refine_init(all_relativeR, (long long)N, (const long long*)idx, dR, dR_init, poses, status, B, k, fd_step, (hipStream_t)stream);

@@ -574,6 +574,11 @@ int launch_pose_modes(const float* sim, long long sim_ld, const double* poses, l
                       double temperature, double radius_rad, int max_modes, int fill, float* prob, long long prob_ld, float* entropy,
                       long long* mode_idx, float* mode_score, float* mode_mass, int* mode_count, int* n_modes, int* status, int B,
                       hipStream_t s);
+// coarse-to-fine retrieval over nested grids (kernels_search.hip)
+int launch_c2f_expand(const double* poses, long long stride_b, int N, const int* stage_of, int max_stage, unsigned char* state,
+                      const long long* seeds, int n_seeds, double radius_rad, int dist_kind, const float* all_rel, int capacity, int* cand,
+                      int* n_cand, int* n_dropped, float* rows, int* status, int B, hipStream_t s);
+int launch_c2f_commit(const float* scores, const int* cand, int capacity, int N, float* sim, long long sim_ld, int B, hipStream_t s);
 // sub-grid pose refinement (kernels_refine.hip)
 int launch_refine_init(const float* all_rel, long long N, const long long* idx, double* dR, double* dR0, float* poses, int* status, int B, int k,
                        double h, hipStream_t s);

@@ -144,7 +144,8 @@ def geodesic_deg(predR: torch.Tensor, gtR: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False,
-                  errors_out: Optional[list] = None, refine_iters: int = 0, distinct_deg: Optional[float] = None, temperature: float = 1.0):
+                  errors_out: Optional[list] = None, refine_iters: int = 0, distinct_deg: Optional[float] = None, temperature: float = 1.0,
+                  coarse_to_fine=None):
     """The body of PoseConditional.eval_geodesic (model.py:268-376).  visualize (effective with a decoding encoder and model.save_dir only,
     model.py:269-274; needs batch["gt_templates"] (B, N, 3, S, S)): the three kinds of pictures and the video under save_dir/media
     (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions.  errors_out: a list that
@@ -154,7 +155,11 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     either; None: nothing changes): the distinct pose modes of the scores within that radius (hip.op_pose_modes at `temperature`, the batch's
     symmetry classes) are scored as well -- the same metric keys under "modes/", computed on the mode seeds, plus the batch means
     "modes/entropy" (nats) and "modes/n_modes"; with refine_iters > 0 the refinement starts from the mode seeds as well and reports under
-    "modes_refined/"; the saved predictions gain `mode_idx`, `mode_mass` and `entropy`."""
+    "modes_refined/"; the saved predictions gain `mode_idx`, `mode_mass` and `entropy`.  coarse_to_fine (no reference counterpart; None: nothing
+    changes; True or a dict of PoseConditional.retrieve_coarse_to_fine's keyword arguments): the exhaustive path runs as always and the search
+    in stages over the nested grid (nope_amd/search.py) runs next to it -- the same metric keys under "c2f/", computed on the search's
+    nearest_idx, "c2f/evaluated_frac" (the share of the grid that got a U-Net pass, batch mean) and "c2f/top1_agree" (the share of queries
+    whose top-1 is the exhaustive one); the saved predictions gain `c2f_similarity` and `c2f_idx`."""
     visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
     if visualize and "gt_templates" not in batch:
         raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
@@ -203,6 +208,15 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
             res.update({f"modes_refined/{k}": float(v) for k, v in refined.items()})
         if save_path:
             extra.update(mode_idx=modes.idx.cpu().numpy(), mode_mass=modes.mass.cpu().numpy(), entropy=modes.entropy.cpu().numpy())
+    if coarse_to_fine is not None and coarse_to_fine is not False:
+        c2f = model.retrieve_coarse_to_fine(query, reference, batch["all_relativeR"], batch["template_poses"][:1],
+                                            **({} if coarse_to_fine is True else dict(coarse_to_fine)))
+        _, c_metric = GeodesicError(list(thresholds)).from_indices(batch["template_poses"][:1], c2f.nearest_idx, batch["query_pose"], sym)
+        res.update({f"c2f/{k}": float(v) for k, v in c_metric.items()})
+        res["c2f/evaluated_frac"] = float(c2f.n_evaluated.float().mean()) / similarity.shape[1]
+        res["c2f/top1_agree"] = float((c2f.nearest_idx[:, 0] == nearest_idx[:, 0]).float().mean())
+        if save_path:
+            extra.update(c2f_similarity=c2f.similarity.cpu().numpy(), c2f_idx=c2f.nearest_idx.cpu().numpy())
     if save_path:
         if visualize:       # model.py:334-339,367-375: the un-resized grid of the last picture
             extra["vis_imgs"] = hip.op_vis_grid(retrieved)[0].cpu().numpy()
@@ -278,12 +292,17 @@ def main(argv=None):
     ap.add_argument("--distinct-deg", type=float, default=None, metavar="D",
                     help="also score the distinct pose modes of the similarity within D degrees (modes/...: their seeds, the entropy, the mode count)")
     ap.add_argument("--temperature", type=float, default=1.0, metavar="T", help="with --distinct-deg: the softmax temperature, in score units")
+    ap.add_argument("--coarse-to-fine", action="store_true",
+                    help="with --pose-level: also retrieve in stages over the nested grid and print its scores (c2f/...: the metrics, the evaluated share, the agreement with the exhaustive top-1)")
+    ap.add_argument("--c2f-seeds", type=int, default=3, metavar="M", help="with --coarse-to-fine: the best M poses of a stage seed the next")
     a = ap.parse_args(argv)
     if a.data_root:
-        if a.refine or a.distinct_deg is not None:
-            ap.error("--refine / --distinct-deg apply to the synthetic batch (a split's pooled scores carry neither)")
+        if a.refine or a.distinct_deg is not None or a.coarse_to_fine:
+            ap.error("--refine / --distinct-deg / --coarse-to-fine apply to the synthetic batch (a split's pooled scores carry none of them)")
         return main_dataset(a, ap)
     a.size = a.size or 128
+    if a.coarse_to_fine and a.pose_level is None:
+        ap.error("--coarse-to-fine needs --pose-level (a nested icosphere grid; random poses have no levels)")
     if a.visualize and (a.encoder != "vae" or not a.save_dir):
         ap.error("--visualize needs --encoder vae (the template encoder decodes nothing, model.py:269-274) and --save-dir")
     if not torch.cuda.is_available():
@@ -291,11 +310,15 @@ def main(argv=None):
     model = build_model(a.seed, a.dtype, a.bank_dtype, "cuda", save_dir=a.save_dir, encoder=a.encoder)
     batches = {f"shapeNet_{a.category}": synthetic_batch(a.batch, a.templates, a.size, a.seed, "cuda", pose_level=a.pose_level,
                                                                   pose_root=a.pose_root, gt_templates=a.visualize)}
+    c2f = None
+    if a.coarse_to_fine:
+        from .poses import grid_stages
+        c2f = dict(seeds=a.c2f_seeds, stage_of=grid_stages(a.pose_level, "upper", root=a.pose_root))
     for name, batch in batches.items():                         # test_step, model.py:550-565
         t0 = time.time()
         save = os.path.join(a.save_dir, "predictions", f"pred_step0_rank{model.global_rank}") if a.save_dir else None
         sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize, refine_iters=a.refine, distinct_deg=a.distinct_deg,
-                                      temperature=a.temperature)
+                                      temperature=a.temperature, coarse_to_fine=c2f)
         torch.cuda.synchronize()
         res.update(dataloader=name, seconds=time.time() - t0, nearest_idx=idx.tolist())
         print(json.dumps(res))

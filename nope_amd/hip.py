@@ -16,7 +16,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 19                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 20                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -113,6 +113,8 @@ _PROTOS = {
     "nope_topk_merge": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nope_op_geodesic": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "nope_op_pose_modes": (_i, [_vp, _i64, _vp, _i64, _i, _vp, C.c_double, C.c_double, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "nope_op_c2f_expand": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, C.c_double, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "nope_op_c2f_commit": (_i, [_vp, _vp, _i, _i, _vp, _i64, _i, _vp]),
     "nope_op_refine_init": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp]),
     "nope_op_refine_normal_eq_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nope_op_refine_normal_eq": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _sz, _vp]),
@@ -490,6 +492,86 @@ def _pose_modes_call(similarity, ld, poses, stride_b, N, sym, temperature, radiu
                                      _ptr(out.mass), _ptr(out.count), _ptr(out.n_modes), _ptr(status), similarity.shape[0],
                                      _stream(similarity)), "nope_op_pose_modes")
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# coarse-to-fine retrieval over nested grids (csrc/kernels_search.hip; the loop is nope_amd/search.py)
+# --------------------------------------------------------------------------------------------
+C2F_OVERFLOW, C2F_BAD_SEED = 1, 2            # bits of op_c2f_expand's status
+C2F_ROTATION, C2F_VIEWPOINT = 0, 1           # dist_kind
+C2F_MAX_SEEDS = 16
+
+
+class C2FExpand(NamedTuple):
+    """op_c2f_expand: cand (B, M) int32 (the candidates in emission order, then -1), n_cand, n_dropped (B,) int32, rows (B, M, 6) f32 (the bits
+    of all_relativeR[b, cand]; a padded slot: the first valid seed's row), status (1,) int32 (C2F_OVERFLOW | C2F_BAD_SEED), left on the device."""
+    cand: torch.Tensor
+    n_cand: torch.Tensor
+    n_dropped: torch.Tensor
+    rows: torch.Tensor
+    status: torch.Tensor
+
+
+def op_c2f_expand(template_poses: torch.Tensor, stage_of: torch.Tensor, max_stage: int, state: torch.Tensor, seeds: Optional[torch.Tensor],
+                  all_relativeR: torch.Tensor, *, radius_rad: float = 0.0, dist_kind: int = C2F_VIEWPOINT, capacity: int) -> C2FExpand:
+    """This stage's candidates of a coarse-to-fine search and their pose rows (include/nope_hip.h: nope_op_c2f_expand).  template_poses
+    (B|1, N, 3, 3) of any float dtype, stage_of (N,), state (B, N) uint8 contiguous -- UPDATED IN PLACE --, seeds (B, n_seeds) int64 as
+    hip.topk returns them or None (stage 0: every eligible pose), all_relativeR (B, N, 6).  Everything follows the state's device.
+    Nothing is read by the host."""
+    require_device(state)
+    if state.dim() != 2 or state.dtype != torch.uint8 or not state.is_contiguous():
+        raise NopeError(f"state {tuple(state.shape)} {state.dtype}: expected a contiguous (B, N) uint8 tensor (it is updated in place)")
+    B, N = state.shape
+    dev = state.device
+    poses = template_poses.to(device=dev, dtype=torch.float64).contiguous()
+    if poses.dim() != 4 or tuple(poses.shape[2:]) != (3, 3) or poses.shape[0] not in (1, B) or poses.shape[1] != N:
+        raise NopeError(f"template_poses {tuple(poses.shape)}: expected (B|1, N, 3, 3) for state {(B, N)}")
+    stage_of = stage_of.to(device=dev, dtype=torch.int32).contiguous()
+    rel = all_relativeR.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(stage_of.shape) != (N,) or tuple(rel.shape) != (B, N, 6):
+        raise NopeError(f"stage_of {tuple(stage_of.shape)} / all_relativeR {tuple(rel.shape)}: expected ({N},) and ({B}, {N}, 6)")
+    if seeds is not None:
+        if seeds.dim() != 2 or seeds.shape[0] != B:
+            raise NopeError(f"seeds {tuple(seeds.shape)}: expected ({B}, n_seeds)")
+        seeds = seeds.to(device=dev, dtype=torch.int64).contiguous()
+    M = max(int(capacity), 1)
+    out = C2FExpand(torch.empty((B, M), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                    torch.empty(B, dtype=torch.int32, device=dev), torch.empty((B, M, 6), dtype=torch.float32, device=dev),
+                    torch.empty(1, dtype=torch.int32, device=dev))
+    if B == 0:
+        return out
+    stride_b = 0 if (poses.shape[0] == 1 and B > 1) else N * 9
+    return _c2f_expand_call(poses, stride_b, N, stage_of, max_stage, state, seeds, 0 if seeds is None else seeds.shape[1], radius_rad,
+                            dist_kind, rel, capacity, out)
+
+
+def _c2f_expand_call(poses, stride_b, N, stage_of, max_stage, state, seeds, n_seeds, radius_rad, dist_kind, rel, capacity, out: C2FExpand) -> C2FExpand:
+    """The launch of op_c2f_expand into given outputs (the argument tests pre-fill them)."""
+    l = lib()
+    l.check(l.dll.nope_op_c2f_expand(_ptr(poses), stride_b, N, _ptr(stage_of), int(max_stage), _ptr(state), _ptr(seeds), int(n_seeds),
+                                     float(radius_rad), int(dist_kind), _ptr(rel), int(capacity), _ptr(out.cand), _ptr(out.n_cand),
+                                     _ptr(out.n_dropped), _ptr(out.rows), _ptr(out.status), state.shape[0], _stream(state)), "nope_op_c2f_expand")
+    return out
+
+
+def op_c2f_commit(scores: torch.Tensor, cand: torch.Tensor, similarity: torch.Tensor) -> torch.Tensor:
+    """similarity[b, cand[b, j]] = scores[b, j] for every cand >= 0, bit for bit, IN PLACE (nope_op_c2f_commit).  scores (B, M) f32, cand
+    (B, M) int32, similarity (B, N) f32 with inner stride 1 (a view is written through its row stride: columns >= N stay untouched)."""
+    require_device(similarity)
+    if similarity.dim() != 2 or similarity.dtype != torch.float32 or (similarity.shape[1] > 1 and similarity.stride(1) != 1) or \
+            (similarity.shape[0] > 1 and similarity.stride(0) < similarity.shape[1]):
+        raise NopeError(f"similarity {tuple(similarity.shape)} {similarity.dtype} strides {similarity.stride()}: expected (B, N) f32 rows (it is written in place)")
+    B, N = similarity.shape
+    if scores.dim() != 2 or scores.shape[0] != B or tuple(cand.shape) != tuple(scores.shape):
+        raise NopeError(f"scores {tuple(scores.shape)} / cand {tuple(cand.shape)}: expected two ({B}, M) tensors")
+    scores = scores.to(device=similarity.device, dtype=torch.float32).contiguous()
+    cand = cand.to(device=similarity.device, dtype=torch.int32).contiguous()
+    if B == 0 or scores.shape[1] == 0:
+        return similarity
+    ld = similarity.stride(0) if B > 1 else max(N, 1)
+    l = lib()
+    l.check(l.dll.nope_op_c2f_commit(_ptr(scores), _ptr(cand), scores.shape[1], N, _ptr(similarity), ld, B, _stream(similarity)), "nope_op_c2f_commit")
+    return similarity
 
 
 # --------------------------------------------------------------------------------------------

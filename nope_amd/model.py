@@ -378,17 +378,62 @@ class PoseConditional(nn.Module):
         from the grid: above its vertex spacing): there are no trained weights to tune them on."""
         return hip.op_pose_modes(similarity, template_poses, symmetry, temperature=temperature, radius_deg=radius_deg, max_modes=max_modes)
 
+    # ---- coarse-to-fine retrieval (no reference counterpart: DESIGN.md section 4.11) ----------------------------------------------------
+    @torch.no_grad()
+    def retrieve_coarse_to_fine_from_feat(self, query_feat, reference_feat, all_relativeR, template_poses, stage_of=None, **kw):
+        """The retrieval in stages over a nested grid (nope_amd.search.coarse_to_fine_search, whose keyword arguments pass through): only
+        the poses the search admits get a U-Net pass and a score.  Returns its C2FResult: a sparse similarity (B,N) with -inf where nothing
+        was evaluated -- an ordinary input to pose_distribution and refine_from_feat -- and nearest_idx (B,k).  query_feat, reference_feat
+        (B,C,h,w) f32; all_relativeR (B,N,6); template_poses (B|1,N,3,3); stage_of (N,) on the host (nope_amd.poses.grid_stages; None: the
+        synthesised icosphere grid of this size, poses.grid_stages_for_size).  As with the refinement, the f16x2 range check of a stage's
+        forward is not deferred: the next stage's candidates depend on its scores.  With synthetic weights the score landscape is not
+        smooth: nothing is claimed about how often the search meets the exhaustive answer on real data."""
+        from .search import coarse_to_fine_search
+        if self.similarity_metric != "l2":
+            return None
+        if self.template_parallel and ndist.world()[1] > 1:
+            raise NotImplementedError("coarse-to-fine retrieval under template_parallel with more than one rank: the stages are too small to shard")
+        if stage_of is None:
+            from .poses import grid_stages_for_size
+            stage_of = grid_stages_for_size(all_relativeR.shape[1])
+        query_feat, reference_feat = query_feat.float().contiguous(), reference_feat.float().contiguous()
+        C, h, w = query_feat.shape[1:]
+
+        def evaluate(rows, cand):
+            maps = torch.empty((rows.shape[0], rows.shape[1], C, h, w), dtype=torch.float32, device=rows.device)
+            return hip.similarity(query_feat, self._forward_poses(reference_feat, rows, maps))
+        return coarse_to_fine_search(evaluate, all_relativeR, template_poses, stage_of, **kw)
+
+    @torch.no_grad()
+    def retrieve_coarse_to_fine(self, query, reference, all_relativeR, template_poses, stage_of=None, **kw):
+        """Encode both images, then retrieve_coarse_to_fine_from_feat (same keyword arguments)."""
+        return self._encode_retrieve_coarse_to_fine(query, reference, all_relativeR, template_poses, stage_of, **kw)[0]
+
+    def _encode_retrieve_coarse_to_fine(self, query, reference, all_relativeR, template_poses, stage_of=None, **kw):
+        enc = self.u_net.encoder
+        query_feat = enc.encode_image(query, mode="mode")
+        reference_feat = enc.encode_image(reference, mode="mode")
+        return self.retrieve_coarse_to_fine_from_feat(query_feat, reference_feat, all_relativeR, template_poses, stage_of, **kw), query_feat, reference_feat
+
     @torch.no_grad()
     def predict_pose(self, query, reference, all_relativeR, template_poses, refine_iters=0, distinct_deg=None, symmetry=None, temperature=1.0,
-                     **kw):
+                     coarse_to_fine=None, **kw):
         """(pred_R (B,k,3,3) f64, score (B,k) f32): the k best poses of the query.  refine_iters = 0: template_poses[nearest_idx]
         (model.py:352-354) and the retrieval scores; above 0: those candidates refined below the grid spacing (refine_from_feat, whose
         keyword arguments pass through), in ITS order.  template_poses (B|1,N,3,3).  None for a metric the reference does not implement.
         distinct_deg (None: the plain top-k, every output as without the argument): the k = 5 candidates are the seeds of the distinct
-        modes within that radius under `symmetry` (op_pose_modes with fill: always k valid candidates), not a vertex and its neighbours."""
+        modes within that radius under `symmetry` (op_pose_modes with fill: always k valid candidates), not a vertex and its neighbours.
+        coarse_to_fine (None: the exhaustive retrieval, every output as without the argument; True, or a dict of
+        retrieve_coarse_to_fine_from_feat's keyword arguments): the scores come from the search in stages over the nested grid instead --
+        a sparse row, -inf where nothing was evaluated, on which distinct_deg and refine_iters work unchanged."""
         if self.similarity_metric != "l2":
             return None
-        similarity, nearest_idx, _, query_feat, reference_feat = self._encode_generate_retrieve(query, reference, all_relativeR)
+        if coarse_to_fine is not None and coarse_to_fine is not False:
+            c2f, query_feat, reference_feat = self._encode_retrieve_coarse_to_fine(query, reference, all_relativeR, template_poses,
+                                                                                   **({} if coarse_to_fine is True else dict(coarse_to_fine)))
+            similarity, nearest_idx = c2f.similarity, c2f.nearest_idx
+        else:
+            similarity, nearest_idx, _, query_feat, reference_feat = self._encode_generate_retrieve(query, reference, all_relativeR)
         if distinct_deg is not None:
             nearest_idx = hip.op_pose_modes(similarity, template_poses, symmetry, temperature=temperature, radius_deg=distinct_deg,
                                             max_modes=nearest_idx.shape[1], fill=True, want_prob=False).idx

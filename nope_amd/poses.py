@@ -129,6 +129,70 @@ def load_index_level0_in_level2(pose_distribution: str, root: Optional[str] = No
     return idx
 
 
+# ---- coarse-to-fine retrieval (no reference counterpart: DESIGN.md section 4.11) ---------------------------------------------------
+def grid_stages(level: int, pose_distribution: str, root: Optional[str] = None) -> np.ndarray:
+    """(N,) int32: the icosphere level at which each pose of the selected grid first appears (0 .. level) -- `stage_of` of
+    nope_amd.search.coarse_to_fine_search.  Synthesised grids: coarser grids are prefixes of finer ones (icosphere_vertices), so the level of
+    a pose follows from its index in the full grid.  With `root` (the reference's files, whose order is their own): every coarser grid's
+    camera positions are matched against this one's, as load_index_level0_in_level2 does, and the match is asserted."""
+    if root is None:
+        index, _ = get_obj_poses_from_template_level(level, pose_distribution, return_index=True)
+        sizes = [10 * 4 ** (l + 1) + 2 for l in range(level)]      # 42, 162, 642: the vertex counts of the coarser levels
+        return np.searchsorted(np.asarray(sizes, dtype=np.int64), index, side="right").astype(np.int32)
+    fine = get_obj_poses_from_template_level(level, pose_distribution, return_cam=True, root=root)[:, :3, 3]
+    stage = np.full(len(fine), level, dtype=np.int32)
+    for l in range(level - 1, -1, -1):
+        coarse = get_obj_poses_from_template_level(l, pose_distribution, return_cam=True, root=root)[:, :3, 3]
+        d = np.linalg.norm(coarse[:, None] - fine[None], axis=-1)
+        idx = d.argmin(axis=1)
+        assert float(d[np.arange(len(coarse)), idx].max()) < 1e-6 and len(set(idx.tolist())) == len(idx)      # coarse vertices are vertices of the finer grid
+        stage[idx] = l
+    return stage
+
+
+def grid_stages_for_size(n: int) -> np.ndarray:
+    """grid_stages of the synthesised icosphere grid with `n` poses (26 / 91 / 341 / 1321: "upper"; 42 / 162 / 642 / 2562: "all").  A grid
+    read from the reference's files has an order of its own: pass its grid_stages(level, distribution, root) instead."""
+    for level in range(4):
+        for dist in ("upper", "all"):
+            if len(get_obj_poses_from_template_level(level, dist, return_index=True)[0]) == n:
+                return grid_stages(level, dist)
+    raise ValueError(f"no synthesised icosphere grid has {n} poses: pass stage_of (nope_amd.poses.grid_stages)")
+
+
+def pose_distance(A: np.ndarray, B: np.ndarray, dist_kind: int) -> np.ndarray:
+    """(m, n) f64 radians between the rotations A (m, 3, 3) and B (n, 3, 3), as nope_op_c2f_expand defines them: 0 = the rotation angle
+    acos(clamp((tr(A B^T) - 1) / 2)), 1 = the angle between the third rows (the camera's optical axis in the object frame), norms floored at 1e-8."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if dist_kind == 0:
+        return np.arccos(np.clip((np.einsum("aij,bij->ab", A, B) - 1.0) / 2.0, -1.0, 1.0))
+    if dist_kind != 1:
+        raise ValueError(f"dist_kind {dist_kind!r}: 0 (rotation) or 1 (viewpoint)")
+    a, b = A[:, 2, :], B[:, 2, :]
+    na, nb = np.maximum(np.linalg.norm(a, axis=1), 1e-8), np.maximum(np.linalg.norm(b, axis=1), 1e-8)
+    return np.arccos(np.clip((a @ b.T) / (na[:, None] * nb[None, :]), -1.0, 1.0))
+
+
+def stage_radii(template_poses, stage_of, dist_kind: int = 1, factor: float = 1.25) -> np.ndarray:
+    """(n_stages,) f64 radians, host NumPy: entry s >= 1 is `factor` x the largest nearest-neighbour distance among the poses with
+    stage_of <= s -- the search radius of stage s (entry 0 is 0: stage 0 takes every pose of its level).  On the synthesised upper grids
+    under the viewpoint distance: 22.50, 11.36 and 5.86 degrees, each inside a wide gap of the pairwise-distance spectrum."""
+    P = np.asarray(template_poses, dtype=np.float64).reshape(-1, *np.shape(template_poses)[-2:])[:, :3, :3]
+    stage_of = np.asarray(stage_of)
+    if stage_of.shape != (len(P),):
+        raise ValueError(f"stage_of {stage_of.shape} for {len(P)} poses")
+    radii = np.zeros(int(stage_of.max()) + 1, dtype=np.float64)
+    for s in range(1, len(radii)):
+        Q = P[stage_of <= s]
+        nn = np.zeros(len(Q))
+        for i0 in range(0, len(Q), 1024):
+            d = pose_distance(Q[i0:i0 + 1024], Q, dist_kind)
+            d[np.arange(d.shape[0]), i0 + np.arange(d.shape[0])] = np.inf
+            nn[i0:i0 + 1024] = d.min(axis=1)
+        radii[s] = factor * nn.max()
+    return radii
+
+
 def load_mapping_id_templates_to_idx_pose_distribution(level: int, pose_distribution: str, root: Optional[str] = None):
     """utils.py:113-125."""
     index_range, _ = get_obj_poses_from_template_level(level, pose_distribution, return_index=True, root=root)
