@@ -93,9 +93,10 @@ typedef void* nope_stream_t;
  *     nope_op_group_norm_ex and nope_op_group_norm_shared);
  * 18: nope_op_pose_modes;
  * 19: nope_conv_op gains gn_emb, gn_emb_stride, gn_self, gn_resid_rep (the conv's own GroupNorm);
- * 20: nope_op_c2f_expand, nope_op_c2f_commit.  Callers compare nope_abi_version() against the header they were
- * built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 20
+ * 20: nope_op_c2f_expand, nope_op_c2f_commit;
+ * 21: nope_op_multiref_prepare, nope_multiref_similarity, nope_op_multiref_fuse_scores.  Callers compare nope_abi_version() against the
+ * header they were built with before passing any struct (nope_amd/hip.py does at load time). */
+#define NOPE_ABI_VERSION 21
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -223,6 +224,59 @@ int nope_op_c2f_expand(const double* template_poses, int64_t pose_stride_b, int 
                        int* n_cand, int* n_dropped, float* rows, int* status, int B, nope_stream_t stream);
 int nope_op_c2f_commit(const float* scores, const int* cand, int capacity, int N, float* similarity, int64_t similarity_ld, int B,
                        nope_stream_t stream);
+
+/* (ABI 21) Multi-reference pose retrieval: several posed reference views of one object fused into one score row.
+ * No reference counterpart: the reference has one reference image per object (src/model/model.py:313,323).  Per sample b: one query, R
+ * references (1 <= R <= 8) with their object-to-camera rotations P[b, r] in the object frame of the template grid T[n], and optionally
+ * n_refs[b] <= R: references r >= n_refs[b] are padding.  The caller's sequence:
+ *     nope_op_multiref_prepare;  nope_unet_forward on the B R sources with all_relativeR viewed as (B R, N, 6) -> bank (B, R, N, C, H, W);
+ *     feature fusion: nope_multiref_similarity      or  score fusion: nope_similarity of the bank viewed as (B, R N, C, H, W), then
+ *     nope_op_multiref_fuse_scores;  nope_topk
+ * The fused (B, N) row is an ordinary input to nope_topk, nope_op_pose_modes and nope_op_refine_select.
+ *
+ * nope_op_multiref_prepare: the relative poses and the blend weights.  One launch, f64 arithmetic, nothing read by the host, no atomics
+ * (the status word has one writer), plain vector stores only, byte-identical from run to run.
+ *   template_poses  (B|1, N, 3, 3) f64, sample stride pose_stride_b elements (0 = one grid for every query, as nope_op_pose_modes)
+ *   ref_poses       (B, R, 3, 3) f64
+ *   n_refs          (B) int32 or NULL (all R)
+ * The distance d[b, r, n] between T[n] and P[b, r] is nope_op_c2f_expand's: dist_kind 0, rotation: acos(clamp((tr(T P^T) - 1) / 2, -1, 1));
+ * dist_kind 1, viewpoint: the clamped acos of the cosine between the third rows, norms floored at 1e-8.
+ *   all_relativeR   (B, R, N, 6) f32 or NULL: the first two rows of T[n] P[b, r]^T, computed in f64 and rounded once to f32 -- the
+ *                   reference's R_q R_ref^-1 (src/dataloader/shapeNet.py:243-245) for an orthonormal P; orthonormality is not checked.
+ *                   A padded reference carries the rows of reference 0: the U-Net sees a finite pose.
+ *   weights         (B, R, N) f32.  weighting 0, uniform: 1 / n_refs[b].  1, softmax: exp(-(d_r - d_min) / tau_rad) / sum_r exp(-(d_r -
+ *                   d_min) / tau_rad), the sum over the valid references in ascending r, f64, rounded once to f32.  2, nearest: 1 at the
+ *                   valid reference with the smallest d (ties -> the lowest r), 0 elsewhere.  Padded references get 0.
+ *   dist            (B, R, N) f64 or NULL: d; +inf at a padded reference.
+ *   status          one device int, written by the call: bit 0 = a valid reference pose has a non-finite entry, bit 1 = n_refs[b] outside
+ *                   [1, R].  In either case EVERY weight of that sample is NaN, so its fused row is NaN and ranks first in nope_topk:
+ *                   visible, never silently wrong.  The other samples are not affected.
+ * NOPE_ERR_ARG, before anything is launched or written: R outside [1, 8]; N < 1; tau_rad not finite or not > 0 under softmax; an unknown
+ * weighting or dist_kind; a missing pointer (template_poses, ref_poses, weights, status).
+ *
+ * nope_multiref_similarity: the score against the blend of the R banks, in one streaming pass; the blend is never materialised.
+ *   q (B, C, H, W) f32;  bank (B, R, N, C, H, W) of bank_dtype (NOPE_F32 | NOPE_BF16 | NOPE_F16), contiguous;  weights (B, R, N) f32;
+ *   scores f32, row b at scores + b * score_ld (score_ld >= N).
+ * Per element: tbar = 0.0f; for r = 0 .. R - 1 in that order: if (w[b, r, n] != 0) tbar = fma(w[b, r, n], float(t[b, r, n, c, p]), tbar), in
+ * f32 -- one fused multiply-add per term on the device.  (The host interpreter build of the test suite has no fused multiply-add and
+ * rounds the product and the sum separately.)  Then score[b, n] = - sum_p sqrt(sum_c (q - tbar)^4) with nope_similarity's arithmetic per
+ * bank type: the correctly rounded sqrtf for f32 banks, the hardware square root for the 16-bit ones.  A term whose weight is exactly 0
+ * contributes nothing whatever its bank entries hold, NaN and inf included: it is discarded by a select, never multiplied.  NaN is not 0:
+ * a NaN weight gives a NaN score.  R = 1 with weight 1 is nope_similarity's definition (another kernel: the two agree to the last bits of
+ * the sums, not bit for bit).  Shape limits are nope_similarity's: H W a multiple of 4 (f32)
+ * or 8 (16-bit); the generic form (taken when H W / (4 | 8) does not divide 256, or C > 16) needs C H W <= 16384; NOPE_ERR_UNSUPPORTED
+ * beyond.  NOPE_ERR_ARG: R outside [1, 8], a missing pointer, a size < 1, score_ld < N.
+ *
+ * nope_op_multiref_fuse_scores: late fusion.  per_ref, weights (B, R, N) f32 -> scores[b, n] = f32(sum_r f64(w) f64(s)), ascending r,
+ * terms with w == 0 skipped (a -inf or NaN score under a zero weight does not poison the row), row stride score_ld >= N; columns >= N
+ * are not touched.  The per-reference scores need no entry of their own: nope_similarity of the bank viewed as (B, R N, C, H, W). */
+int nope_op_multiref_prepare(const double* template_poses, int64_t pose_stride_b, int N, const double* ref_poses, int R, const int* n_refs,
+                             int weighting, double tau_rad, int dist_kind, float* all_relativeR, float* weights, double* dist, int* status, int B,
+                             nope_stream_t stream);
+int nope_multiref_similarity(const float* q, const void* bank, int bank_dtype, const float* weights, float* scores, int B, int R, int N, int C,
+                             int H, int W, int score_ld, nope_stream_t stream);
+int nope_op_multiref_fuse_scores(const float* per_ref, const float* weights, float* scores, int B, int R, int N, int64_t score_ld,
+                                 nope_stream_t stream);
 
 /* (ABI 15) Sub-grid pose refinement: Gauss-Newton on SO(3) through the U-Net.  No reference counterpart: the reference's prediction is
  * template_poses[nearest_idx] (src/model/model.py:352-354), a vertex of the template grid (26 templates: ~32 degrees apart).  The U-Net is a

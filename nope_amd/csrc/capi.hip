@@ -146,6 +146,24 @@ int nope_op_c2f_commit(const float* scores, const int* cand, int capacity, int N
     return launch_c2f_commit(scores, cand, capacity, N, similarity, (long long)similarity_ld, B, (hipStream_t)stream);
 }
 
+int nope_op_multiref_prepare(const double* template_poses, int64_t pose_stride_b, int N, const double* ref_poses, int R, const int* n_refs,
+                             int weighting, double tau_rad, int dist_kind, float* all_relativeR, float* weights, double* dist, int* status, int B,
+                             nope_stream_t stream) {
+    return launch_multiref_prepare(template_poses, (long long)pose_stride_b, N, ref_poses, R, n_refs, weighting, tau_rad, dist_kind, all_relativeR,
+                                   weights, dist, status, B, (hipStream_t)stream);
+}
+
+int nope_multiref_similarity(const float* q, const void* bank, int bank_dtype, const float* weights, float* scores, int B, int R, int N, int C,
+                             int H, int W, int score_ld, nope_stream_t stream) {
+    if (H <= 0 || W <= 0) return NOPE_ERR_ARG;
+    return launch_multiref_similarity(q, bank, bank_dtype, weights, scores, B, R, N, C, H * W, score_ld, (hipStream_t)stream);
+}
+
+int nope_op_multiref_fuse_scores(const float* per_ref, const float* weights, float* scores, int B, int R, int N, int64_t score_ld,
+                                 nope_stream_t stream) {
+    return launch_multiref_fuse_scores(per_ref, weights, scores, B, R, N, (long long)score_ld, (hipStream_t)stream);
+}
+
 int nope_op_refine_init(const float* all_relativeR, int64_t N, const int64_t* idx, double* dR, double* dR_init, float* poses, int* status,
                         int B, int k, double fd_step, nope_stream_t stream) {
     return launch_refine_init(all_relativeR, (long long)N, (const long long*)idx, dR, dR_init, poses, status, B, k, fd_step, (hipStream_t)stream);

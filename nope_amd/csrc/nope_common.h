@@ -579,6 +579,13 @@ int launch_c2f_expand(const double* poses, long long stride_b, int N, const int*
                       const long long* seeds, int n_seeds, double radius_rad, int dist_kind, const float* all_rel, int capacity, int* cand,
                       int* n_cand, int* n_dropped, float* rows, int* status, int B, hipStream_t s);
 int launch_c2f_commit(const float* scores, const int* cand, int capacity, int N, float* sim, long long sim_ld, int B, hipStream_t s);
+// multi-reference retrieval (kernels_multiref.hip)
+int launch_multiref_prepare(const double* template_poses, long long stride_b, int N, const double* ref_poses, int R, const int* n_refs,
+                            int weighting, double tau_rad, int dist_kind, float* all_rel, float* weights, double* dist, int* status, int B,
+                            hipStream_t s);
+int launch_multiref_similarity(const float* q, const void* bank, int bank_dt, const float* weights, float* scores, int B, int R, int N, int C, int HW,
+                               int score_ld, hipStream_t s);
+int launch_multiref_fuse_scores(const float* per_ref, const float* weights, float* scores, int B, int R, int N, long long score_ld, hipStream_t s);
 // sub-grid pose refinement (kernels_refine.hip)
 int launch_refine_init(const float* all_rel, long long N, const long long* idx, double* dR, double* dR0, float* poses, int* status, int B, int k,
                        double h, hipStream_t s);

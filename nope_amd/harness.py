@@ -72,12 +72,15 @@ def rotation_6d(m: torch.Tensor) -> torch.Tensor:
 
 
 def synthetic_batch(batch: int, n_templates: int, size: int, seed: int = 2022, device="cpu",
-                    pose_level: Optional[int] = None, pose_root: Optional[str] = None, gt_templates: bool = False) -> Dict[str, torch.Tensor]:
+                    pose_level: Optional[int] = None, pose_root: Optional[str] = None, gt_templates: bool = False,
+                    n_references: int = 1) -> Dict[str, torch.Tensor]:
     """A test-split batch shaped like ShapeNet.__getitem__ (dataloader/shapeNet.py:348-357).  Template poses are
     Haar-random rotations, or -- `pose_level` 0..3 -- the upper-hemisphere icosphere grid the reference evaluates on
     (nope_amd.poses: 26 / 91 / 341 / 1321 viewpoints; `pose_root` = the reference's predefined_poses directory to
     read its own files); `n_templates` is ignored then.  gt_templates: add the (B, N, 3, size, size) ground-truth template images that the
-    visualisation shows (shapeNet.py:352; drawn last, the other tensors do not change)."""
+    visualisation shows (shapeNet.py:352; drawn last, the other tensors do not change).  n_references R (no reference counterpart: the
+    reference's test split has one reference per object): `references` (B, R, 3, size, size) and `reference_poses` (B, R, 3, 3) for the
+    multi-reference path; index 0 is `reference` and its pose, the extras are drawn after everything else."""
     g = torch.Generator().manual_seed(seed)
     query = torch.rand(batch, 3, size, size, generator=g) * 2 - 1
     reference = torch.rand(batch, 3, size, size, generator=g) * 2 - 1
@@ -98,6 +101,13 @@ def synthetic_batch(batch: int, n_templates: int, size: int, seed: int = 2022, d
                template_poses=R_tpl[None].expand(batch, -1, -1, -1).contiguous())
     if gt_templates:
         out["gt_templates"] = torch.rand(batch, n_templates, 3, size, size, generator=g) * 2 - 1
+    n_extra = max(int(n_references), 1) - 1
+    out["references"], out["reference_poses"] = reference[:, None], R_ref[:, None]
+    if n_extra > 0:
+        extra_img = torch.rand(batch, n_extra, 3, size, size, generator=g) * 2 - 1
+        extra_R = random_rotations(batch * n_extra, g).reshape(batch, n_extra, 3, 3)
+        out["references"] = torch.cat([out["references"], extra_img], dim=1)
+        out["reference_poses"] = torch.cat([out["reference_poses"], extra_R], dim=1)
     return {k: v.to(device) for k, v in out.items()}
 
 
@@ -145,7 +155,7 @@ def geodesic_deg(predR: torch.Tensor, gtR: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False,
                   errors_out: Optional[list] = None, refine_iters: int = 0, distinct_deg: Optional[float] = None, temperature: float = 1.0,
-                  coarse_to_fine=None):
+                  coarse_to_fine=None, multi_ref=None):
     """The body of PoseConditional.eval_geodesic (model.py:268-376).  visualize (effective with a decoding encoder and model.save_dir only,
     model.py:269-274; needs batch["gt_templates"] (B, N, 3, S, S)): the three kinds of pictures and the video under save_dir/media
     (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions.  errors_out: a list that
@@ -159,7 +169,10 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     changes; True or a dict of PoseConditional.retrieve_coarse_to_fine's keyword arguments): the exhaustive path runs as always and the search
     in stages over the nested grid (nope_amd/search.py) runs next to it -- the same metric keys under "c2f/", computed on the search's
     nearest_idx, "c2f/evaluated_frac" (the share of the grid that got a U-Net pass, batch mean) and "c2f/top1_agree" (the share of queries
-    whose top-1 is the exhaustive one); the saved predictions gain `c2f_similarity` and `c2f_idx`."""
+    whose top-1 is the exhaustive one); the saved predictions gain `c2f_similarity` and `c2f_idx`.  multi_ref (no reference counterpart; None:
+    nothing changes; a dict of PoseConditional.retrieve_multi's keyword arguments, may be empty): the retrieval from ALL of
+    batch["references"] (B, R, 3, S, S) with batch["reference_poses"] (B, R, 3, 3) runs next to the single-reference one -- the same
+    metric keys under "multi/" and "multi/top1_agree"; the saved predictions gain `multi_similarity`."""
     visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
     if visualize and "gt_templates" not in batch:
         raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
@@ -217,6 +230,16 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
         res["c2f/top1_agree"] = float((c2f.nearest_idx[:, 0] == nearest_idx[:, 0]).float().mean())
         if save_path:
             extra.update(c2f_similarity=c2f.similarity.cpu().numpy(), c2f_idx=c2f.nearest_idx.cpu().numpy())
+    if multi_ref is not None and multi_ref is not False:
+        if "references" not in batch or "reference_poses" not in batch:
+            raise ValueError('eval_geodesic(multi_ref=...) needs batch["references"] (B, R, 3, S, S) and batch["reference_poses"] (B, R, 3, 3)')
+        mr = model.retrieve_multi(query, batch["references"], batch["reference_poses"], batch["template_poses"][:1],
+                                  **({} if multi_ref is True else dict(multi_ref)))
+        _, r_metric = GeodesicError(list(thresholds)).from_indices(batch["template_poses"][:1], mr.nearest_idx, batch["query_pose"], sym)
+        res.update({f"multi/{k}": float(v) for k, v in r_metric.items()})
+        res["multi/top1_agree"] = float((mr.nearest_idx[:, 0] == nearest_idx[:, 0]).float().mean())
+        if save_path:
+            extra.update(multi_similarity=mr.similarity.cpu().numpy())
     if save_path:
         if visualize:       # model.py:334-339,367-375: the un-resized grid of the last picture
             extra["vis_imgs"] = hip.op_vis_grid(retrieved)[0].cpu().numpy()
@@ -295,10 +318,17 @@ def main(argv=None):
     ap.add_argument("--coarse-to-fine", action="store_true",
                     help="with --pose-level: also retrieve in stages over the nested grid and print its scores (c2f/...: the metrics, the evaluated share, the agreement with the exhaustive top-1)")
     ap.add_argument("--c2f-seeds", type=int, default=3, metavar="M", help="with --coarse-to-fine: the best M poses of a stage seed the next")
+    ap.add_argument("--references", type=int, default=1, metavar="R",
+                    help="also retrieve from R posed reference views per object, fused (multi/...: the metrics, the agreement with the single-reference top-1)")
+    ap.add_argument("--fusion", default="feature", choices=["feature", "score"], help="with --references: blend the predicted embeddings and score once, or average the score rows")
+    ap.add_argument("--weighting", default="softmax", choices=["uniform", "softmax", "nearest"], help="with --references: the blend weights over the references")
+    ap.add_argument("--tau-deg", type=float, default=30.0, metavar="D", help="with --weighting softmax: the temperature, degrees of pose distance")
     a = ap.parse_args(argv)
+    if not 1 <= a.references <= hip.MULTIREF_MAX_REFS:
+        ap.error(f"--references: 1 .. {hip.MULTIREF_MAX_REFS}")
     if a.data_root:
-        if a.refine or a.distinct_deg is not None or a.coarse_to_fine:
-            ap.error("--refine / --distinct-deg / --coarse-to-fine apply to the synthetic batch (a split's pooled scores carry none of them)")
+        if a.refine or a.distinct_deg is not None or a.coarse_to_fine or a.references > 1:
+            ap.error("--refine / --distinct-deg / --coarse-to-fine / --references apply to the synthetic batch (a split's pooled scores carry none of them)")
         return main_dataset(a, ap)
     a.size = a.size or 128
     if a.coarse_to_fine and a.pose_level is None:
@@ -309,7 +339,8 @@ def main(argv=None):
         raise SystemExit("nope_amd.harness needs an MI355X (no CPU fallback)")
     model = build_model(a.seed, a.dtype, a.bank_dtype, "cuda", save_dir=a.save_dir, encoder=a.encoder)
     batches = {f"shapeNet_{a.category}": synthetic_batch(a.batch, a.templates, a.size, a.seed, "cuda", pose_level=a.pose_level,
-                                                                  pose_root=a.pose_root, gt_templates=a.visualize)}
+                                                                  pose_root=a.pose_root, gt_templates=a.visualize,
+                                                                  n_references=a.references)}
     c2f = None
     if a.coarse_to_fine:
         from .poses import grid_stages
@@ -318,7 +349,8 @@ def main(argv=None):
         t0 = time.time()
         save = os.path.join(a.save_dir, "predictions", f"pred_step0_rank{model.global_rank}") if a.save_dir else None
         sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize, refine_iters=a.refine, distinct_deg=a.distinct_deg,
-                                      temperature=a.temperature, coarse_to_fine=c2f)
+                                      temperature=a.temperature, coarse_to_fine=c2f,
+                                      multi_ref=dict(fusion=a.fusion, weighting=a.weighting, tau_deg=a.tau_deg) if a.references > 1 else None)
         torch.cuda.synchronize()
         res.update(dataloader=name, seconds=time.time() - t0, nearest_idx=idx.tolist())
         print(json.dumps(res))

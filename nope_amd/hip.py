@@ -16,7 +16,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 20                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 21                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -115,6 +115,9 @@ _PROTOS = {
     "nope_op_pose_modes": (_i, [_vp, _i64, _vp, _i64, _i, _vp, C.c_double, C.c_double, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "nope_op_c2f_expand": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, C.c_double, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "nope_op_c2f_commit": (_i, [_vp, _vp, _i, _i, _vp, _i64, _i, _vp]),
+    "nope_op_multiref_prepare": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "nope_multiref_similarity": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "nope_op_multiref_fuse_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
     "nope_op_refine_init": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp]),
     "nope_op_refine_normal_eq_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nope_op_refine_normal_eq": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _sz, _vp]),
@@ -572,6 +575,113 @@ def op_c2f_commit(scores: torch.Tensor, cand: torch.Tensor, similarity: torch.Te
     l = lib()
     l.check(l.dll.nope_op_c2f_commit(_ptr(scores), _ptr(cand), scores.shape[1], N, _ptr(similarity), ld, B, _stream(similarity)), "nope_op_c2f_commit")
     return similarity
+
+
+# --------------------------------------------------------------------------------------------
+# multi-reference retrieval (csrc/kernels_multiref.hip; the drivers are PoseConditional.retrieve_multi*)
+# --------------------------------------------------------------------------------------------
+MULTIREF_BAD_POSE, MULTIREF_BAD_COUNT = 1, 2            # bits of op_multiref_prepare's status
+MULTIREF_MAX_REFS = 8
+MULTIREF_WEIGHTINGS = {"uniform": 0, "softmax": 1, "nearest": 2}
+
+
+class MultiRefPrep(NamedTuple):
+    """op_multiref_prepare: all_relativeR (B, R, N, 6) f32 or None, weights (B, R, N) f32, dist (B, R, N) f64 radians or None (+inf at a
+    padded reference), status (1,) int32 (MULTIREF_BAD_POSE | MULTIREF_BAD_COUNT; every weight of such a sample is NaN), left on the device."""
+    all_relativeR: Optional[torch.Tensor]
+    weights: torch.Tensor
+    dist: Optional[torch.Tensor]
+    status: torch.Tensor
+
+
+def op_multiref_prepare(template_poses: torch.Tensor, ref_poses: torch.Tensor, n_refs: Optional[torch.Tensor] = None, *, weighting="softmax",
+                        tau_deg: float = 30.0, dist_kind: int = C2F_ROTATION, want_rel: bool = True, want_dist: bool = False) -> MultiRefPrep:
+    """The relative poses T[n] P[b, r]^T (6-D rows for the U-Net) and the blend weights of R posed reference views per sample
+    (include/nope_hip.h: nope_op_multiref_prepare).  template_poses (B|1, N, 3, 3) and ref_poses (B, R, 3, 3) of any float dtype, n_refs (B,)
+    or None (all R valid; references r >= n_refs[b] are padding: weight 0, the pose rows of reference 0).  weighting "uniform" | "softmax"
+    (over -d / tau_deg, d the distance of `dist_kind` between grid pose and reference pose) | "nearest".  Everything follows the reference
+    poses' device.  Nothing is read by the host."""
+    require_device(ref_poses)
+    if ref_poses.dim() != 4 or tuple(ref_poses.shape[2:]) != (3, 3):
+        raise NopeError(f"ref_poses {tuple(ref_poses.shape)}: expected (B, R, 3, 3)")
+    B, R = ref_poses.shape[:2]
+    dev = ref_poses.device
+    refs = ref_poses.to(torch.float64).contiguous()
+    poses = template_poses.to(device=dev, dtype=torch.float64).contiguous()
+    if poses.dim() != 4 or tuple(poses.shape[2:]) != (3, 3) or poses.shape[0] not in (1, B):
+        raise NopeError(f"template_poses {tuple(poses.shape)}: expected (B|1, N, 3, 3) for ref_poses {tuple(ref_poses.shape)}")
+    N = poses.shape[1]
+    nr = None if n_refs is None else n_refs.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    if nr is not None and nr.numel() != B:
+        raise NopeError(f"n_refs has {nr.numel()} entries for {B} samples")
+    if not isinstance(weighting, int):
+        if weighting not in MULTIREF_WEIGHTINGS:
+            raise NopeError(f"weighting {weighting!r}: one of {sorted(MULTIREF_WEIGHTINGS)}")
+        weighting = MULTIREF_WEIGHTINGS[weighting]
+    out = MultiRefPrep(torch.empty((B, R, N, 6), dtype=torch.float32, device=dev) if want_rel else None,
+                       torch.empty((B, R, N), dtype=torch.float32, device=dev),
+                       torch.empty((B, R, N), dtype=torch.float64, device=dev) if want_dist else None,
+                       torch.empty(1, dtype=torch.int32, device=dev))
+    if B == 0:
+        return out
+    stride_b = 0 if (poses.shape[0] == 1 and B > 1) else N * 9
+    return _multiref_prepare_call(poses, stride_b, N, refs, R, nr, weighting, math.radians(tau_deg), dist_kind, out)
+
+
+def _multiref_prepare_call(poses, stride_b, N, refs, R, n_refs, weighting, tau_rad, dist_kind, out: MultiRefPrep) -> MultiRefPrep:
+    """The launch of op_multiref_prepare into given outputs (the argument tests pre-fill them)."""
+    l = lib()
+    l.check(l.dll.nope_op_multiref_prepare(_ptr(poses), stride_b, int(N), _ptr(refs), int(R), _ptr(n_refs), int(weighting), float(tau_rad),
+                                           int(dist_kind), _ptr(out.all_relativeR), _ptr(out.weights), _ptr(out.dist), _ptr(out.status),
+                                           refs.shape[0], _stream(refs)), "nope_op_multiref_prepare")
+    return out
+
+
+def multiref_similarity(q: torch.Tensor, bank: torch.Tensor, weights: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """score[b, n] of model.py:257-262 against the blend sum_r weights[b, r, n] bank[b, r, n] of R banks, in one pass that never writes the
+    blend (include/nope_hip.h: nope_multiref_similarity).  q (B,C,H,W) f32; bank (B,R,N,C,H,W) f32|bf16|fp16; weights (B,R,N) f32.  With
+    `out` (B, ld >= N) given, writes its columns [0, N)."""
+    require_device(q)
+    q = _f32c(q)
+    B, Cc, H, W = q.shape
+    if bank.dim() != 6 or bank.shape[0] != B or tuple(bank.shape[3:]) != (Cc, H, W):
+        raise NopeError(f"bank shape {tuple(bank.shape)} does not match query {tuple(q.shape)}: expected (B, R, N, C, H, W)")
+    R, N = bank.shape[1:3]
+    if tuple(weights.shape) != (B, R, N):
+        raise NopeError(f"weights {tuple(weights.shape)}: expected {(B, R, N)} for bank {tuple(bank.shape)}")
+    if bank.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        bank = bank.float()
+    bank = bank.contiguous()
+    weights = weights.to(device=q.device, dtype=torch.float32).contiguous()
+    if N == 0:
+        return torch.empty((B, 0), dtype=torch.float32, device=q.device) if out is None else out
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.float32, device=q.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] == B and out.shape[1] >= N
+    l = lib()
+    l.check(l.dll.nope_multiref_similarity(_ptr(q), _ptr(bank), dtype_code(bank.dtype), _ptr(weights), _ptr(out), B, R, N, Cc, H, W, out.shape[1],
+                                           _stream(q)), "nope_multiref_similarity")
+    return out
+
+
+def op_multiref_fuse_scores(per_ref: torch.Tensor, weights: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Late fusion: scores[b, n] = f32(sum_r f64(weights[b, r, n]) f64(per_ref[b, r, n])), terms with a zero weight skipped
+    (nope_op_multiref_fuse_scores).  per_ref, weights (B, R, N) f32.  With `out` (B, ld >= N) given, writes its columns [0, N)."""
+    require_device(per_ref)
+    if per_ref.dim() != 3 or tuple(weights.shape) != tuple(per_ref.shape):
+        raise NopeError(f"per_ref {tuple(per_ref.shape)} / weights {tuple(weights.shape)}: expected two (B, R, N) tensors")
+    per_ref = _f32c(per_ref)
+    weights = weights.to(device=per_ref.device, dtype=torch.float32).contiguous()
+    B, R, N = per_ref.shape
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.float32, device=per_ref.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] == B and out.shape[1] >= N
+    if B == 0 or N == 0:
+        return out
+    l = lib()
+    l.check(l.dll.nope_op_multiref_fuse_scores(_ptr(per_ref), _ptr(weights), _ptr(out), B, R, N, out.shape[1], _stream(per_ref)),
+            "nope_op_multiref_fuse_scores")
+    return out
 
 
 # --------------------------------------------------------------------------------------------

@@ -43,6 +43,17 @@ class RefineResult(NamedTuple):
     pred_R: Optional[torch.Tensor]
 
 
+class MultiRefResult(NamedTuple):
+    """What PoseConditional.retrieve_multi_from_feat returns: similarity (B,N) f32, the fused row; nearest_idx (B,k) int64; weights (B,R,N)
+    f32, the blend weights (NaN for a sample whose reference poses or count were invalid: its fused row is NaN too); per_reference (B,R,N)
+    f32, the single-reference scores, or None; bank (B,R,N,C,h,w)."""
+    similarity: torch.Tensor
+    nearest_idx: torch.Tensor
+    weights: torch.Tensor
+    per_reference: Optional[torch.Tensor]
+    bank: torch.Tensor
+
+
 def _cfg_get(cfg, key, default=None):
     if cfg is None:
         return default
@@ -414,6 +425,86 @@ class PoseConditional(nn.Module):
         query_feat = enc.encode_image(query, mode="mode")
         reference_feat = enc.encode_image(reference, mode="mode")
         return self.retrieve_coarse_to_fine_from_feat(query_feat, reference_feat, all_relativeR, template_poses, stage_of, **kw), query_feat, reference_feat
+
+    # ---- multi-reference retrieval (no reference counterpart: DESIGN.md section 4.12) ---------------------------------------------------
+    def _no_multi_ref_shards(self):
+        if self.template_parallel and ndist.world()[1] > 1:
+            raise NotImplementedError("multi-reference retrieval under template_parallel with more than one rank: sharded banks are not fused")
+
+    @torch.no_grad()
+    def generate_templates_multi_from_feat(self, reference_feats, all_relativeR):
+        """reference_feats (B,R,C,h,w), all_relativeR (B,R,N,6) -> the bank (B,R,N,C,h,w): every (sample, reference) pair is one source of
+        generate_templates_from_feat -- same chunking, and the f16x2 range check is finished there."""
+        self._no_multi_ref_shards()
+        B, R, N = all_relativeR.shape[:3]
+        if tuple(reference_feats.shape[:2]) != (B, R):
+            raise hip.NopeError(f"reference_feats {tuple(reference_feats.shape)} / all_relativeR {tuple(all_relativeR.shape)}: expected (B, R, C, h, w) and (B, R, N, 6)")
+        bank = self.generate_templates_from_feat(reference_feats.reshape(B * R, *reference_feats.shape[2:]).contiguous(),
+                                                 all_relativeR.reshape(B * R, N, 6))
+        return bank.view(B, R, N, *bank.shape[2:])
+
+    @torch.no_grad()
+    def retrieve_multi_from_feat(self, query_feat, reference_feats, ref_poses, template_poses, n_refs=None, fusion="feature", weighting="softmax",
+                                 tau_deg=30.0, dist_kind=hip.C2F_ROTATION, k=5, return_per_reference=False):
+        """Retrieval from R posed reference views per sample (include/nope_hip.h: nope_op_multiref_prepare, nope_multiref_similarity,
+        nope_op_multiref_fuse_scores).  query_feat (B,C,h,w); reference_feats (B,R,C,h,w); ref_poses (B,R,3,3), the references' object-to-camera
+        rotations in the frame of the grid; template_poses (B|1,N,3,3); n_refs (B,) or None: references r >= n_refs[b] are padding.
+        fusion "feature": the U-Net's predictions from the R references are blended per grid pose and the query is scored once against the
+        blend; "score": the R single-reference score rows are averaged under the same weights.  weighting "uniform" | "softmax" (over
+        -distance / tau_deg between grid pose and reference pose: a reference predicts best near its own view -- a design choice, not a
+        measured gain: there are no trained weights) | "nearest".  Returns a MultiRefResult; its similarity is an ordinary input to
+        pose_distribution.  None for a metric the reference does not implement."""
+        if self.similarity_metric != "l2":
+            return None
+        self._no_multi_ref_shards()
+        if fusion not in ("feature", "score"):
+            raise ValueError(f"fusion {fusion!r}: 'feature' or 'score'")
+        query_feat = query_feat.float().contiguous()
+        prep = hip.op_multiref_prepare(template_poses, ref_poses.to(query_feat.device), n_refs, weighting=weighting, tau_deg=tau_deg,
+                                       dist_kind=dist_kind)
+        bank = self.generate_templates_multi_from_feat(reference_feats, prep.all_relativeR)
+        B, R, N = bank.shape[:3]
+        per_ref = None
+        if fusion == "score" or return_per_reference:
+            per_ref = hip.similarity(query_feat, bank.view(B, R * N, *bank.shape[3:])).view(B, R, N)
+        if fusion == "feature":
+            similarity = hip.multiref_similarity(query_feat, bank, prep.weights)
+        else:
+            similarity = hip.op_multiref_fuse_scores(per_ref, prep.weights)
+        _, nearest_idx = hip.topk(similarity, k)
+        return MultiRefResult(similarity, nearest_idx, prep.weights, per_ref if return_per_reference else None, bank)
+
+    @torch.no_grad()
+    def retrieve_multi(self, query, references, reference_poses, template_poses, **kw):
+        """Encode, then retrieve_multi_from_feat (same keyword arguments).  query (B,3,S,S); references (B,R,3,S,S), encoded as one batch of
+        B R images; the query's encoder pass runs on the side stream underneath them, as in generate_and_retrieve."""
+        if self.similarity_metric != "l2":
+            return None
+        self._no_multi_ref_shards()
+        B, R = references.shape[:2]
+        enc = self.u_net.encoder
+        with hip.overlap_stream(query) as side:
+            query_feat = enc.encode_image(query, mode="mode")
+        reference_feats = enc.encode_image(references.reshape(B * R, *references.shape[2:]), mode="mode")
+        side.join(query_feat)
+        return self.retrieve_multi_from_feat(query_feat, reference_feats.reshape(B, R, *reference_feats.shape[1:]), reference_poses, template_poses, **kw)
+
+    @torch.no_grad()
+    def predict_pose_multi(self, query, references, reference_poses, template_poses, distinct_deg=None, symmetry=None, temperature=1.0, **kw):
+        """predict_pose from R posed references: (pred_R (B,k,3,3) f64, score (B,k) f32) = template_poses[nearest_idx] and the fused scores of
+        retrieve_multi (whose keyword arguments pass through); pred_R[:, 0] is the answer.  distinct_deg (None: the plain top-k): the k
+        candidates are the seeds of the distinct modes of the fused row within that radius under `symmetry` (op_pose_modes with fill, as
+        predict_pose)."""
+        r = self.retrieve_multi(query, references, reference_poses, template_poses, **kw)
+        if r is None:
+            return None
+        similarity, nearest_idx = r.similarity, r.nearest_idx
+        if distinct_deg is not None:
+            nearest_idx = hip.op_pose_modes(similarity, template_poses, symmetry, temperature=temperature, radius_deg=distinct_deg,
+                                            max_modes=nearest_idx.shape[1], fill=True, want_prob=False).idx
+        tp = template_poses.to(device=nearest_idx.device, dtype=torch.float64)
+        rows = torch.arange(nearest_idx.shape[0], device=nearest_idx.device)[:, None] if tp.shape[0] != 1 else 0
+        return tp[rows, nearest_idx], torch.gather(similarity, 1, nearest_idx)
 
     @torch.no_grad()
     def predict_pose(self, query, reference, all_relativeR, template_poses, refine_iters=0, distinct_deg=None, symmetry=None, temperature=1.0,
