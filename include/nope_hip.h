@@ -94,9 +94,10 @@ typedef void* nope_stream_t;
  * 18: nope_op_pose_modes;
  * 19: nope_conv_op gains gn_emb, gn_emb_stride, gn_self, gn_resid_rep (the conv's own GroupNorm);
  * 20: nope_op_c2f_expand, nope_op_c2f_commit;
- * 21: nope_op_multiref_prepare, nope_multiref_similarity, nope_op_multiref_fuse_scores.  Callers compare nope_abi_version() against the
+ * 21: nope_op_multiref_prepare, nope_multiref_similarity, nope_op_multiref_fuse_scores;
+ * 22: nope_op_multiref_select, nope_op_multiref_gather.  Callers compare nope_abi_version() against the
  * header they were built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 21
+#define NOPE_ABI_VERSION 22
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -277,6 +278,42 @@ int nope_multiref_similarity(const float* q, const void* bank, int bank_dtype, c
                              int H, int W, int score_ld, nope_stream_t stream);
 int nope_op_multiref_fuse_scores(const float* per_ref, const float* weights, float* scores, int B, int R, int N, int64_t score_ld,
                                  nope_stream_t stream);
+
+/* (ABI 22) Multi-reference retrieval from the M nearest references per pose.  No reference counterpart.  The ABI 21
+ * sequence runs the U-Net on every (reference, pose) pair, B R N hypotheses; here the caller decides per (sample, pose), before the U-Net
+ * runs, which M <= R references that pose is generated from, and the U-Net runs on B M S hypotheses whatever R is.  The caller's sequence:
+ *     nope_op_multiref_select;  nope_op_multiref_gather -> sources (B M S, C, H, W);  nope_unet_forward on those sources, one pose each
+ *     (x_rep = 1), with all_relativeR viewed as (B M S, 6) -> bank (B, M, S, C, H, W);
+ *     M > 1: nope_multiref_similarity or nope_similarity + nope_op_multiref_fuse_scores with R := M;  M = 1: nope_similarity;  nope_topk
+ * With a candidate list the S slots are the candidates of a coarse-to-fine stage (nope_op_c2f_expand's cand; scores back through
+ * nope_op_c2f_commit) or the k candidates of a refinement (nope_topk's indices as int32).
+ *
+ * nope_op_multiref_select: the M nearest references of every slot.  One launch, f64 arithmetic, one thread per (b, slot), nothing read by
+ * the host, no atomics (the status word has one writer), plain vector stores only, byte-identical from run to run.
+ *   template_poses, pose_stride_b, ref_poses, n_refs, weighting, tau_rad, dist_kind: as nope_op_multiref_prepare
+ *   cand            (B, S) int32 or NULL.  NULL: S = N (the argument S is ignored) and slot s is pose s.  Otherwise slot s is pose
+ *                   cand[b, s], laid out as nope_op_c2f_expand writes it: candidates, then -1.
+ *   M               in [1, R]
+ * Per valid slot: d[r], nope_op_multiref_prepare's distance (the same bits), of the valid references; ordered by (d, r) ascending, a NaN
+ * after every number; the first Mv = min(M, n_refs[b]) are kept.
+ *   src             (B, M, S) int32: the kept reference of slot m
+ *   all_relativeR   (B, M, S, 6) f32 or NULL: the first two rows of T[p] P[b, src]^T, f64 rounded once (nope_op_multiref_prepare's bits)
+ *   weights         (B, M, S) f32.  uniform: 1 / Mv.  softmax, over the KEPT references only: exp(-(d_m - d_0) / tau_rad) / sum_m exp(-(d_m -
+ *                   d_0) / tau_rad), the sum in ascending m, f64 rounded once.  nearest: 1 at m = 0, 0 elsewhere.
+ *   dist            (B, M, S) f64 or NULL
+ * Slots m >= Mv: weight exactly 0, src and pose rows of slot 0, dist +inf.  A padded candidate (cand == -1): all M weights 0, src 0, the rows
+ * of pose 0 against reference 0, dist +inf.  A cand entry below -1 or >= N: as padding, and status bit 2.  Status bits 0 and 1 are
+ * nope_op_multiref_prepare's, and so is their rule: EVERY weight of such a sample is NaN (padded slots included), src stays inside [0, R).
+ * NOPE_ERR_ARG, before anything is launched or written: nope_op_multiref_prepare's cases; M outside [1, R]; S < 1 with cand given; a
+ * missing src, weights or status.
+ *
+ * nope_op_multiref_gather: out[b, j, :] = reference_feats[b, src[b, j], :], j in [0, J) (J = M S), both f32, rows of L = C H W elements, L a
+ * multiple of 4: 16-byte copies, bit for bit (NaN payloads survive).  reference_feats (B, R, L), src (B, J) int32, out (B, J, L).  A src
+ * entry outside [0, R) fills its row with NaN: visible, never a wild read.  NOPE_ERR_ARG: L % 4, a missing pointer, a size < 1. */
+int nope_op_multiref_select(const double* template_poses, int64_t pose_stride_b, int N, const double* ref_poses, int R, const int* n_refs,
+                            const int* cand, int S, int M, int weighting, double tau_rad, int dist_kind, int* src, float* all_relativeR, float* weights,
+                            double* dist, int* status, int B, nope_stream_t stream);
+int nope_op_multiref_gather(const float* reference_feats, const int* src, float* out, int B, int R, int J, int64_t L, nope_stream_t stream);
 
 /* (ABI 15) Sub-grid pose refinement: Gauss-Newton on SO(3) through the U-Net.  No reference counterpart: the reference's prediction is
  * template_poses[nearest_idx] (src/model/model.py:352-354), a vertex of the template grid (26 templates: ~32 degrees apart).  The U-Net is a

@@ -164,6 +164,17 @@ int nope_op_multiref_fuse_scores(const float* per_ref, const float* weights, flo
     return launch_multiref_fuse_scores(per_ref, weights, scores, B, R, N, (long long)score_ld, (hipStream_t)stream);
 }
 
+int nope_op_multiref_select(const double* template_poses, int64_t pose_stride_b, int N, const double* ref_poses, int R, const int* n_refs,
+                            const int* cand, int S, int M, int weighting, double tau_rad, int dist_kind, int* src, float* all_relativeR, float* weights,
+                            double* dist, int* status, int B, nope_stream_t stream) {
+    return launch_multiref_select(template_poses, (long long)pose_stride_b, N, ref_poses, R, n_refs, cand, S, M, weighting, tau_rad, dist_kind, src,
+                                  all_relativeR, weights, dist, status, B, (hipStream_t)stream);
+}
+
+int nope_op_multiref_gather(const float* reference_feats, const int* src, float* out, int B, int R, int J, int64_t L, nope_stream_t stream) {
+    return launch_multiref_gather(reference_feats, src, out, B, R, J, (long long)L, (hipStream_t)stream);
+}
+
 int nope_op_refine_init(const float* all_relativeR, int64_t N, const int64_t* idx, double* dR, double* dR_init, float* poses, int* status,
                         int B, int k, double fd_step, nope_stream_t stream) {
     return launch_refine_init(all_relativeR, (long long)N, (const long long*)idx, dR, dR_init, poses, status, B, k, fd_step, (hipStream_t)stream);

@@ -1,5 +1,5 @@
 // Multi-reference pose retrieval (no reference counterpart: the reference has one reference image per object,
-// src/model/model.py:313,323).  Three entries:
+// src/model/model.py:313,323).  Five entries:
 //
 //   multiref_prepare      per (query b, reference r, grid pose n): the relative pose the U-Net is asked for (first two rows of T[n] P[b, r]^T),
 //                         the distance d[b, r, n] between T[n] and P[b, r] (kernels_search.hip's two kinds) and the blend weight w[b, r, n]
@@ -9,6 +9,10 @@
 //   multiref_similarity   the hot path: score[b, n] = - sum_p sqrt( sum_c (q - tbar)^4 ) against the blend of R banks,
 //                         tbar = sum_r w[b, r, n] t[b, r, n, c, p], in ONE streaming pass -- the blend is never written anywhere.
 //   multiref_fuse_scores  late fusion: score[b, n] = f32( sum_r f64(w) f64(s[b, r, n]) ).
+//
+//   multiref_select        per (query b, slot s): the M nearest references of grid pose s -- or of pose cand[b, s] --, their
+//                         relative poses and blend weights; multiref_prepare's distance and row arithmetic, so the bits agree.
+//   multiref_gather       out[b, j, :] = reference_feats[b, src[b, j], :]: the source embedding of every hypothesis, 16-byte copies.
 //
 // The scoring kernels follow kernels_retrieval.hip's sim_reg_kernel / sim_lds_kernel (same lane -> pixel-vector mapping, same reductions,
 // same per-type square root), whose small load / unpack helpers are restated here: that file does not change, and neither do its kernels'
@@ -363,7 +367,159 @@ __global__ __launch_bounds__(NT) void multiref_fuse_kernel(const float* __restri
     scores[(size_t)b * score_ld + n] = (float)acc;
 }
 
+// ---- select: the M nearest references per (sample, slot) -----------------------------------------------------------------------------------
+// (a, i) before (b, j) in the order "distance ascending, then index ascending, a NaN after every number"; i != j
+__device__ __forceinline__ bool mr_before(double a, int i, double b, int j) {
+    const bool an = a != a, bn = b != b;
+    if (an || bn) return an == bn ? i < j : bn;
+    return a < b || (a == b && i < j);
+}
+
+// first two rows of T P^T, f64 rounded once: multiref_prepare_kernel's expression, so the bits agree
+__device__ __forceinline__ void mr_store_rows(const double* T, const double* Pr, float* __restrict__ rel) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            rel[i * 3 + j] = (float)(T[i * 3] * Pr[j * 3] + T[i * 3 + 1] * Pr[j * 3 + 1] + T[i * 3 + 2] * Pr[j * 3 + 2]);
+}
+
+// grid (chunks of 256 slots, B); thread -> one (b, slot): M rounds of "the smallest (d, r) not taken yet" over the references, every loop
+// unrolled to MR_MAX_REFS and the taken references a bit mask, so d[] stays in registers
+__global__ __launch_bounds__(NT) void multiref_select_kernel(const double* __restrict__ tpl, long long stride_b, int N, const double* __restrict__ ref_poses,
+                                                             int R, const int* __restrict__ n_refs, const int* __restrict__ cand, int S, int M,
+                                                             int weighting, double tau, int kind, int* __restrict__ src, float* __restrict__ rel,
+                                                             float* __restrict__ weights, double* __restrict__ dist, int* __restrict__ status, int B) {
+    __shared__ int s_bits[NT / 64];
+    const int b = blockIdx.y, t = threadIdx.x, s = blockIdx.x * NT + t;
+    if (blockIdx.x == 0 && blockIdx.y == 0) {         // the status word: one writer, a plain store
+        int bits = 0;
+        for (int i = t; i < B; i += NT) bits |= mr_sample_status(ref_poses, n_refs, R, i);
+        if (cand)
+            for (long long i = t; i < (long long)B * S; i += NT) {
+                const int c = cand[i];
+                if (c < -1 || c >= N) bits |= 4;
+            }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) bits |= __shfl_xor(bits, o, 64);
+        if ((t & 63) == 0) s_bits[t >> 6] = bits;
+        __syncthreads();
+        if (t == 0) {
+            int all = 0;
+#pragma unroll
+            for (int w = 0; w < NT / 64; ++w) all |= s_bits[w];
+            *status = all;
+        }
+    }
+    if (s >= S) return;
+    const bool bad = mr_sample_status(ref_poses, n_refs, R, b) != 0;
+    int nr = n_refs ? n_refs[b] : R;
+    nr = nr < 0 ? 0 : (nr > R ? R : nr);
+    int p = cand ? cand[(size_t)b * S + s] : s;
+    const bool pad = p < 0 || p >= N;                 // -1, or an entry out of range (status bit 2)
+    if (pad) p = 0;
+    const int Mv = pad ? 0 : (M < nr ? M : nr);
+    const double* Pb = ref_poses + (size_t)b * R * 9;
+    double T[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) T[e] = tpl[(size_t)b * stride_b + (size_t)p * 9 + e];
+    const double inf = (double)__builtin_huge_valf();
+    const float qnan = __builtin_nanf("");
+
+    double d[MR_MAX_REFS];
+#pragma unroll
+    for (int r = 0; r < MR_MAX_REFS; ++r) {
+        d[r] = inf;
+        if (r < nr) {
+            double Pr[9];
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Pr[e] = Pb[r * 9 + e];
+            d[r] = mr_distance(T, Pr, kind);
+        }
+    }
+    unsigned taken = 0;
+    int first = 0;                                    // slot 0's reference: what the slots m >= Mv repeat
+    double d0 = 0.0, e[MR_MAX_REFS], Z = 0.0;
+#pragma unroll
+    for (int m = 0; m < MR_MAX_REFS; ++m) {
+        e[m] = 0.0;
+        if (m < M) {
+            int best = -1;
+            double dbest = inf;
+            if (m < Mv) {
+#pragma unroll
+                for (int r = 0; r < MR_MAX_REFS; ++r)
+                    if (r < nr && !((taken >> r) & 1u) && (best < 0 || mr_before(d[r], r, dbest, best))) { best = r; dbest = d[r]; }
+                taken |= 1u << best;
+                if (m == 0) { first = best; d0 = dbest; }
+                e[m] = weighting == 1 ? exp(-(dbest - d0) / tau) : 0.0;
+                Z += e[m];
+            } else {
+                best = first;
+            }
+            const size_t o = ((size_t)b * M + m) * S + s;
+            src[o] = best;
+            if (dist) dist[o] = dbest;
+            if (rel) {
+                double Pr[9];
+#pragma unroll
+                for (int q = 0; q < 9; ++q) Pr[q] = Pb[best * 9 + q];
+                mr_store_rows(T, Pr, rel + o * 6);
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MR_MAX_REFS; ++m)
+        if (m < M) {
+            float w = 0.f;
+            if (bad) w = qnan;
+            else if (m < Mv) w = weighting == 0 ? (float)(1.0 / (double)Mv) : weighting == 1 ? (float)(e[m] / Z) : (m == 0 ? 1.f : 0.f);
+            weights[((size_t)b * M + m) * S + s] = w;
+        }
+}
+
+// gather: one workgroup per output row (b, j); 16-byte copies, bit for bit; a source outside [0, R) fills the row with NaN
+__global__ __launch_bounds__(NT) void multiref_gather_kernel(const float* __restrict__ feats, const int* __restrict__ src, float* __restrict__ out, int R, int J,
+                                                             int L4) {
+    const size_t row = blockIdx.x;
+    const int b = (int)(row / (size_t)J);
+    const int r = src[row];
+    u32x4* o = reinterpret_cast<u32x4*>(out) + row * (size_t)L4;
+    if (r < 0 || r >= R) {
+        const unsigned q = 0x7fc00000u;
+        const u32x4 v = {q, q, q, q};
+        for (int i = threadIdx.x; i < L4; i += NT) o[i] = v;
+        return;
+    }
+    const u32x4* in = reinterpret_cast<const u32x4*>(feats) + ((size_t)b * R + r) * (size_t)L4;
+    for (int i = threadIdx.x; i < L4; i += NT) o[i] = in[i];
+}
+
 }  // namespace
+
+int launch_multiref_select(const double* template_poses, long long stride_b, int N, const double* ref_poses, int R, const int* n_refs, const int* cand,
+                           int S, int M, int weighting, double tau_rad, int dist_kind, int* src, float* all_rel, float* weights, double* dist, int* status,
+                           int B, hipStream_t s) {
+    if (!template_poses || !ref_poses || !src || !weights || !status || B <= 0 || N < 1 || stride_b < 0) return NOPE_ERR_ARG;
+    if (R < 1 || R > MR_MAX_REFS || M < 1 || M > R) return NOPE_ERR_ARG;
+    if (weighting < 0 || weighting > 2 || (dist_kind != 0 && dist_kind != 1)) return NOPE_ERR_ARG;
+    if (weighting == 1 && (!(tau_rad > 0.0) || !std::isfinite(tau_rad))) return NOPE_ERR_ARG;
+    if (cand && S < 1) return NOPE_ERR_ARG;
+    if (!cand) S = N;
+    if (B > 65535) return NOPE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(multiref_select_kernel, dim3((unsigned)cdiv(S, NT), (unsigned)B), dim3(NT), 0, s, template_poses, stride_b, N, ref_poses, R, n_refs,
+                       cand, S, M, weighting, tau_rad, dist_kind, src, all_rel, weights, dist, status, B);
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
+
+int launch_multiref_gather(const float* reference_feats, const int* src, float* out, int B, int R, int J, long long L, hipStream_t s) {
+    if (!reference_feats || !src || !out || B < 1 || R < 1 || J < 1 || L < 1 || (L & 3)) return NOPE_ERR_ARG;
+    if ((long long)B * J > 0x7fffffffLL || L / 4 > 0x7fffffffLL) return NOPE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(multiref_gather_kernel, dim3((unsigned)((long long)B * J)), dim3(NT), 0, s, reference_feats, src, out, R, J, (int)(L / 4));
+    NOPE_CHECK_LAUNCH();
+    return NOPE_OK;
+}
 
 int launch_multiref_prepare(const double* template_poses, long long stride_b, int N, const double* ref_poses, int R, const int* n_refs,
                             int weighting, double tau_rad, int dist_kind, float* all_rel, float* weights, double* dist, int* status, int B,

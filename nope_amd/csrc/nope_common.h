@@ -586,6 +586,10 @@ int launch_multiref_prepare(const double* template_poses, long long stride_b, in
 int launch_multiref_similarity(const float* q, const void* bank, int bank_dt, const float* weights, float* scores, int B, int R, int N, int C, int HW,
                                int score_ld, hipStream_t s);
 int launch_multiref_fuse_scores(const float* per_ref, const float* weights, float* scores, int B, int R, int N, long long score_ld, hipStream_t s);
+int launch_multiref_select(const double* template_poses, long long stride_b, int N, const double* ref_poses, int R, const int* n_refs, const int* cand,
+                           int S, int M, int weighting, double tau_rad, int dist_kind, int* src, float* all_rel, float* weights, double* dist, int* status,
+                           int B, hipStream_t s);
+int launch_multiref_gather(const float* reference_feats, const int* src, float* out, int B, int R, int J, long long L, hipStream_t s);
 // sub-grid pose refinement (kernels_refine.hip)
 int launch_refine_init(const float* all_rel, long long N, const long long* idx, double* dR, double* dR0, float* poses, int* status, int B, int k,
                        double h, hipStream_t s);

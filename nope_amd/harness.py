@@ -25,6 +25,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import sys
 import time
 from typing import Dict, Optional
 
@@ -172,7 +173,10 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     whose top-1 is the exhaustive one); the saved predictions gain `c2f_similarity` and `c2f_idx`.  multi_ref (no reference counterpart; None:
     nothing changes; a dict of PoseConditional.retrieve_multi's keyword arguments, may be empty): the retrieval from ALL of
     batch["references"] (B, R, 3, S, S) with batch["reference_poses"] (B, R, 3, 3) runs next to the single-reference one -- the same
-    metric keys under "multi/" and "multi/top1_agree"; the saved predictions gain `multi_similarity`."""
+    metric keys under "multi/" and "multi/top1_agree"; the saved predictions gain `multi_similarity`.  Two keys of the dict are taken out here:
+    "coarse_to_fine" (True or a dict of the search's keyword arguments): the multi-reference retrieval itself runs in stages
+    (PoseConditional.retrieve_multi_coarse_to_fine, max_refs 1 unless given) and "multi/evaluated_frac" is added; "refine_iters" > 0: its
+    candidates are refined, each through its nearest reference (refine_multi_from_feat), and scored under "multi_refined/"."""
     visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
     if visualize and "gt_templates" not in batch:
         raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
@@ -233,11 +237,28 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     if multi_ref is not None and multi_ref is not False:
         if "references" not in batch or "reference_poses" not in batch:
             raise ValueError('eval_geodesic(multi_ref=...) needs batch["references"] (B, R, 3, S, S) and batch["reference_poses"] (B, R, 3, 3)')
-        mr = model.retrieve_multi(query, batch["references"], batch["reference_poses"], batch["template_poses"][:1],
-                                  **({} if multi_ref is True else dict(multi_ref)))
-        _, r_metric = GeodesicError(list(thresholds)).from_indices(batch["template_poses"][:1], mr.nearest_idx, batch["query_pose"], sym)
+        mkw = {} if multi_ref is True else dict(multi_ref)
+        m_c2f, m_refine = mkw.pop("coarse_to_fine", None), int(mkw.pop("refine_iters", 0))
+        tpl = batch["template_poses"][:1]
+        model._no_multi_ref_shards()
+        q_feat, ref_feats = model._encode_multi(query, batch["references"])      # once: retrieval and refinement both start from the embeddings
+        if m_c2f is not None and m_c2f is not False:       # the search in stages, every admitted pose from its max_refs nearest references
+            mkw.pop("return_per_reference", None)
+            if "dist_kind" in mkw:
+                mkw["ref_dist_kind"] = mkw.pop("dist_kind")
+            if mkw.get("max_refs") is None:
+                mkw["max_refs"] = 1
+            mr = model.retrieve_multi_coarse_to_fine_from_feat(q_feat, ref_feats, batch["reference_poses"], tpl, **mkw, **({} if m_c2f is True else dict(m_c2f)))
+            res["multi/evaluated_frac"] = float(mr.n_evaluated.float().mean()) / similarity.shape[1]
+        else:
+            mr = model.retrieve_multi_from_feat(q_feat, ref_feats, batch["reference_poses"], tpl, **mkw)
+        _, r_metric = GeodesicError(list(thresholds)).from_indices(tpl, mr.nearest_idx, batch["query_pose"], sym)
         res.update({f"multi/{k}": float(v) for k, v in r_metric.items()})
         res["multi/top1_agree"] = float((mr.nearest_idx[:, 0] == nearest_idx[:, 0]).float().mean())
+        if m_refine > 0:                                   # each candidate refined through its nearest reference
+            ref = model.refine_multi_from_feat(q_feat, ref_feats, batch["reference_poses"], tpl, mr.nearest_idx, n_refs=mkw.get("n_refs"), iters=m_refine)
+            _, refined = GeodesicError(list(thresholds))._topk_result(hip.op_geodesic(ref.pred_R, batch["query_pose"], sym))
+            res.update({f"multi_refined/{k}": float(v) for k, v in refined.items()})
         if save_path:
             extra.update(multi_similarity=mr.similarity.cpu().numpy())
     if save_path:
@@ -322,10 +343,15 @@ def main(argv=None):
                     help="also retrieve from R posed reference views per object, fused (multi/...: the metrics, the agreement with the single-reference top-1)")
     ap.add_argument("--fusion", default="feature", choices=["feature", "score"], help="with --references: blend the predicted embeddings and score once, or average the score rows")
     ap.add_argument("--weighting", default="softmax", choices=["uniform", "softmax", "nearest"], help="with --references: the blend weights over the references")
+    ap.add_argument("--max-refs", type=int, default=None, metavar="M",
+                    help="with --references: generate every pose from its M nearest references only (M U-Net passes per pose whatever R is); "
+                         "with --coarse-to-fine / --refine as well, the multi-reference retrieval runs in stages / its candidates are refined")
     ap.add_argument("--tau-deg", type=float, default=30.0, metavar="D", help="with --weighting softmax: the temperature, degrees of pose distance")
     a = ap.parse_args(argv)
     if not 1 <= a.references <= hip.MULTIREF_MAX_REFS:
         ap.error(f"--references: 1 .. {hip.MULTIREF_MAX_REFS}")
+    if a.max_refs is not None and not 1 <= a.max_refs <= a.references:
+        ap.error("--max-refs: 1 .. --references")
     if a.data_root:
         if a.refine or a.distinct_deg is not None or a.coarse_to_fine or a.references > 1:
             ap.error("--refine / --distinct-deg / --coarse-to-fine / --references apply to the synthetic batch (a split's pooled scores carry none of them)")
@@ -345,12 +371,20 @@ def main(argv=None):
     if a.coarse_to_fine:
         from .poses import grid_stages
         c2f = dict(seeds=a.c2f_seeds, stage_of=grid_stages(a.pose_level, "upper", root=a.pose_root))
+    multi = None
+    if a.references > 1 and a.max_refs is None and (a.coarse_to_fine or a.refine):
+        print("note: --coarse-to-fine / --refine apply to the single-reference retrieval only; add --max-refs M to run them through the "
+              "references as well (multi/evaluated_frac, multi_refined/...)", file=sys.stderr)
+    if a.references > 1:
+        multi = dict(fusion=a.fusion, weighting=a.weighting, tau_deg=a.tau_deg)
+        if a.max_refs is not None:          # the sparse path and, through it, the stages and the refinement from several references
+            multi.update(max_refs=a.max_refs, coarse_to_fine=c2f, refine_iters=a.refine)
     for name, batch in batches.items():                         # test_step, model.py:550-565
         t0 = time.time()
         save = os.path.join(a.save_dir, "predictions", f"pred_step0_rank{model.global_rank}") if a.save_dir else None
         sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize, refine_iters=a.refine, distinct_deg=a.distinct_deg,
                                       temperature=a.temperature, coarse_to_fine=c2f,
-                                      multi_ref=dict(fusion=a.fusion, weighting=a.weighting, tau_deg=a.tau_deg) if a.references > 1 else None)
+                                      multi_ref=multi)
         torch.cuda.synchronize()
         res.update(dataloader=name, seconds=time.time() - t0, nearest_idx=idx.tolist())
         print(json.dumps(res))

@@ -16,7 +16,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 21                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 22                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -118,6 +118,8 @@ _PROTOS = {
     "nope_op_multiref_prepare": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "nope_multiref_similarity": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nope_op_multiref_fuse_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
+    "nope_op_multiref_select": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "nope_op_multiref_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
     "nope_op_refine_init": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp]),
     "nope_op_refine_normal_eq_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nope_op_refine_normal_eq": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _sz, _vp]),
@@ -681,6 +683,93 @@ def op_multiref_fuse_scores(per_ref: torch.Tensor, weights: torch.Tensor, out: O
     l = lib()
     l.check(l.dll.nope_op_multiref_fuse_scores(_ptr(per_ref), _ptr(weights), _ptr(out), B, R, N, out.shape[1], _stream(per_ref)),
             "nope_op_multiref_fuse_scores")
+    return out
+
+
+MULTIREF_BAD_CAND = 4                                   # bit 2 of op_multiref_select's status: a cand entry below -1 or >= N
+
+
+class MultiRefSelect(NamedTuple):
+    """op_multiref_select: all_relativeR (B, M, S, 6) f32 or None, weights (B, M, S) f32, dist (B, M, S) f64 radians or None (+inf at a slot
+    m >= min(M, n_refs[b]) and at a padded candidate), status (1,) int32 (MULTIREF_BAD_POSE | MULTIREF_BAD_COUNT | MULTIREF_BAD_CAND), src
+    (B, M, S) int32: the reference each slot is generated from.  Left on the device."""
+    all_relativeR: Optional[torch.Tensor]
+    weights: torch.Tensor
+    dist: Optional[torch.Tensor]
+    status: torch.Tensor
+    src: torch.Tensor
+
+
+def op_multiref_select(template_poses: torch.Tensor, ref_poses: torch.Tensor, n_refs: Optional[torch.Tensor] = None, *, max_refs: int,
+                       cand: Optional[torch.Tensor] = None, weighting="softmax", tau_deg: float = 30.0, dist_kind: int = C2F_ROTATION,
+                       want_rel: bool = True, want_dist: bool = False) -> MultiRefSelect:
+    """The max_refs = M nearest of R posed references per (sample, slot), their relative poses and their blend weights (include/nope_hip.h:
+    nope_op_multiref_select).  Arguments as op_multiref_prepare; cand (B, S) integers or None: the grid poses the slots stand for (-1:
+    padding, as op_c2f_expand writes them; hip.topk's indices do as well); None: slot s is pose s, S = N.  Nothing is read by the host."""
+    require_device(ref_poses)
+    if ref_poses.dim() != 4 or tuple(ref_poses.shape[2:]) != (3, 3):
+        raise NopeError(f"ref_poses {tuple(ref_poses.shape)}: expected (B, R, 3, 3)")
+    B, R = ref_poses.shape[:2]
+    dev = ref_poses.device
+    refs = ref_poses.to(torch.float64).contiguous()
+    poses = template_poses.to(device=dev, dtype=torch.float64).contiguous()
+    if poses.dim() != 4 or tuple(poses.shape[2:]) != (3, 3) or poses.shape[0] not in (1, B):
+        raise NopeError(f"template_poses {tuple(poses.shape)}: expected (B|1, N, 3, 3) for ref_poses {tuple(ref_poses.shape)}")
+    N = poses.shape[1]
+    nr = None if n_refs is None else n_refs.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    if nr is not None and nr.numel() != B:
+        raise NopeError(f"n_refs has {nr.numel()} entries for {B} samples")
+    if not isinstance(weighting, int):
+        if weighting not in MULTIREF_WEIGHTINGS:
+            raise NopeError(f"weighting {weighting!r}: one of {sorted(MULTIREF_WEIGHTINGS)}")
+        weighting = MULTIREF_WEIGHTINGS[weighting]
+    S = N
+    if cand is not None:
+        if cand.dim() != 2 or cand.shape[0] != B:
+            raise NopeError(f"cand {tuple(cand.shape)}: expected ({B}, S)")
+        cand = cand.to(device=dev, dtype=torch.int32).contiguous()
+        S = cand.shape[1]
+    M = int(max_refs)
+    Mo = max(M, 0)
+    out = MultiRefSelect(torch.empty((B, Mo, S, 6), dtype=torch.float32, device=dev) if want_rel else None,
+                         torch.empty((B, Mo, S), dtype=torch.float32, device=dev),
+                         torch.empty((B, Mo, S), dtype=torch.float64, device=dev) if want_dist else None,
+                         torch.empty(1, dtype=torch.int32, device=dev), torch.empty((B, Mo, S), dtype=torch.int32, device=dev))
+    if B == 0:
+        return out
+    stride_b = 0 if (poses.shape[0] == 1 and B > 1) else N * 9
+    return _multiref_select_call(poses, stride_b, N, refs, R, nr, cand, S, M, weighting, math.radians(tau_deg), dist_kind, out)
+
+
+def _multiref_select_call(poses, stride_b, N, refs, R, n_refs, cand, S, M, weighting, tau_rad, dist_kind, out: MultiRefSelect) -> MultiRefSelect:
+    """The launch of op_multiref_select into given outputs (the argument tests pre-fill them)."""
+    l = lib()
+    l.check(l.dll.nope_op_multiref_select(_ptr(poses), stride_b, int(N), _ptr(refs), int(R), _ptr(n_refs), _ptr(cand), int(S), int(M), int(weighting),
+                                          float(tau_rad), int(dist_kind), _ptr(out.src), _ptr(out.all_relativeR), _ptr(out.weights), _ptr(out.dist),
+                                          _ptr(out.status), refs.shape[0], _stream(refs)), "nope_op_multiref_select")
+    return out
+
+
+def op_multiref_gather(reference_feats: torch.Tensor, src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[b, j] = reference_feats[b, src[b, j]], bit for bit (nope_op_multiref_gather).  reference_feats (B, R, ...) f32 with rows of a
+    multiple of 4 elements; src (B, ...) int32, J entries per sample (op_multiref_select's (B, M, S)); -> (B, J, ...) f32.  A src entry outside
+    [0, R) gives a NaN row."""
+    require_device(reference_feats)
+    if reference_feats.dim() < 3 or src.dim() < 2 or src.shape[0] != reference_feats.shape[0]:
+        raise NopeError(f"reference_feats {tuple(reference_feats.shape)} / src {tuple(src.shape)}: expected (B, R, ...) and (B, ...)")
+    feats = _f32c(reference_feats)
+    B, R = feats.shape[:2]
+    src = src.to(device=feats.device, dtype=torch.int32).contiguous()
+    J = src.numel() // B if B else 0
+    L = feats[0, 0].numel() if B and R else 0
+    if out is None:
+        out = torch.empty((B, J, *feats.shape[2:]), dtype=torch.float32, device=feats.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.device != feats.device or out.numel() != B * J * L:
+        raise NopeError(f"out {tuple(out.shape)} {out.dtype}: expected a contiguous f32 tensor of {B * J * L} elements ({B}, {J}, ...) on {feats.device}")
+    if B == 0 or J == 0:
+        return out
+    l = lib()
+    l.check(l.dll.nope_op_multiref_gather(_ptr(feats), _ptr(src), _ptr(out), B, R, J, L, _stream(feats)), "nope_op_multiref_gather")
     return out
 
 

@@ -46,12 +46,14 @@ class RefineResult(NamedTuple):
 class MultiRefResult(NamedTuple):
     """What PoseConditional.retrieve_multi_from_feat returns: similarity (B,N) f32, the fused row; nearest_idx (B,k) int64; weights (B,R,N)
     f32, the blend weights (NaN for a sample whose reference poses or count were invalid: its fused row is NaN too); per_reference (B,R,N)
-    f32, the single-reference scores, or None; bank (B,R,N,C,h,w)."""
+    f32, the single-reference scores, or None; bank (B,R,N,C,h,w).  With max_refs = M (the sparse path): weights, per_reference (the per-slot
+    rows) and bank have M in place of R, and src (B,M,N) int32 names the reference each slot was generated from (None on the dense path)."""
     similarity: torch.Tensor
     nearest_idx: torch.Tensor
     weights: torch.Tensor
     per_reference: Optional[torch.Tensor]
     bank: torch.Tensor
+    src: Optional[torch.Tensor] = None
 
 
 def _cfg_get(cfg, key, default=None):
@@ -344,13 +346,21 @@ class PoseConditional(nn.Module):
         entry), costs (iters,B,k) f64 (r^T r at the START of each iteration, in retrieval order), status (iters,B,k) int32 (hip.REFINE_*),
         trajectory (iters+1,B,k,3,3) f64 (dR before the first and after every step, retrieval order) and, with template_poses (B|1,N,3,3),
         pred_R (B,k,3,3) f64 = (dR dR_init^T) template_poses[nearest_idx]."""
+        query_feat, reference_feat = query_feat.float().contiguous(), reference_feat.float().contiguous()
+        return self._refine(query_feat, lambda poses, out: self._forward_poses(reference_feat, poses, out), all_relativeR, nearest_idx, nearest_idx,
+                            similarity, iters, fd_step, max_step_deg, damping, template_poses)
+
+    def _refine(self, query_feat, forward, rows, row_idx, nearest_idx, similarity, iters, fd_step, max_step_deg, damping, template_poses):
+        """The loop of refine_from_feat / refine_multi_from_feat.  forward(poses (B,n,6), out (B,n,C,h,w)) fills `out` with the U-Net's maps of
+        `poses`, n = 7k (candidate-major: the pose and its six neighbours) or k; rows[b, row_idx[b, j]] is candidate j's starting pose;
+        similarity (B,N) holds the baseline score at nearest_idx -- or is None: the baseline is then the score of slot 0 of each group of
+        seven in the FIRST iteration's forward, the starting pose through the same source as every later pass."""
         import math
         if iters < 1:
             raise ValueError("refine_from_feat: iters >= 1 (predict_pose(refine_iters=0) is the unrefined answer)")
-        query_feat, reference_feat = query_feat.float().contiguous(), reference_feat.float().contiguous()
         B, k = nearest_idx.shape
         C, h, w = query_feat.shape[1:]
-        dR, dR0, poses, _ = hip.op_refine_init(all_relativeR, nearest_idx, fd_step)
+        dR, dR0, poses, _ = hip.op_refine_init(rows, row_idx, fd_step)
         dev = dR.device
         maps = torch.empty((B, 7 * k, C, h, w), dtype=torch.float32, device=dev)
         ne = torch.empty((iters, B, k, 10), dtype=torch.float64, device=dev)
@@ -359,12 +369,16 @@ class PoseConditional(nn.Module):
         ws = torch.empty(max(8, int(hip.lib().dll.nope_op_refine_normal_eq_workspace_bytes(B, k, h, w))) // 8, dtype=torch.float64, device=dev)
         traj[0].copy_(dR)
         for it in range(iters):
-            self._forward_poses(reference_feat, poses, maps)
+            forward(poses, maps)
+            if similarity is None:
+                base_score = hip.similarity(query_feat, maps.view(B, k, 7, C, h, w)[:, :, 0].contiguous())
+                similarity = torch.full((B, template_poses.shape[1]), float("-inf"), dtype=torch.float32, device=dev)
+                hip.op_c2f_commit(base_score, nearest_idx.to(torch.int32), similarity)
             hip.op_refine_normal_eq(query_feat, maps, fd_step, out=ne[it], workspace=ws)
             hip.op_refine_step(ne[it], dR, poses, fd_step, math.radians(max_step_deg), damping, status=status[it])
             traj[it + 1].copy_(dR)
         base = poses.view(B, k, 7, 6)[:, :, 0].contiguous()
-        final_maps = self._forward_poses(reference_feat, base, torch.empty((B, k, C, h, w), dtype=torch.float32, device=dev))
+        final_maps = forward(base, torch.empty((B, k, C, h, w), dtype=torch.float32, device=dev))
         score = hip.similarity(query_feat, final_maps)
         r = hip.op_refine_select(dR, dR0, score, similarity, nearest_idx, template_poses)
         return RefineResult(relR=r.dR, rot6d=r.rot6d, score=r.score, score_init=r.score_init, accepted=r.accepted, order=r.order,
@@ -445,7 +459,7 @@ class PoseConditional(nn.Module):
 
     @torch.no_grad()
     def retrieve_multi_from_feat(self, query_feat, reference_feats, ref_poses, template_poses, n_refs=None, fusion="feature", weighting="softmax",
-                                 tau_deg=30.0, dist_kind=hip.C2F_ROTATION, k=5, return_per_reference=False):
+                                 tau_deg=30.0, dist_kind=hip.C2F_ROTATION, k=5, return_per_reference=False, max_refs=None):
         """Retrieval from R posed reference views per sample (include/nope_hip.h: nope_op_multiref_prepare, nope_multiref_similarity,
         nope_op_multiref_fuse_scores).  query_feat (B,C,h,w); reference_feats (B,R,C,h,w); ref_poses (B,R,3,3), the references' object-to-camera
         rotations in the frame of the grid; template_poses (B|1,N,3,3); n_refs (B,) or None: references r >= n_refs[b] are padding.
@@ -453,13 +467,24 @@ class PoseConditional(nn.Module):
         blend; "score": the R single-reference score rows are averaged under the same weights.  weighting "uniform" | "softmax" (over
         -distance / tau_deg between grid pose and reference pose: a reference predicts best near its own view -- a design choice, not a
         measured gain: there are no trained weights) | "nearest".  Returns a MultiRefResult; its similarity is an ordinary input to
-        pose_distribution.  None for a metric the reference does not implement."""
+        pose_distribution.  None for a metric the reference does not implement.
+        max_refs (None: every pose is generated from all R references, B R N U-Net hypotheses): every pose is generated from its M =
+        max_refs nearest references only (nope_op_multiref_select), B M N hypotheses whatever R is, and the weights -- softmax over the
+        kept references -- , per_reference and the bank carry M slots in place of the R references.  M = 1 is
+        "nearest" at the cost of one reference: its row is nope_similarity's, which reads no weights."""
         if self.similarity_metric != "l2":
             return None
         self._no_multi_ref_shards()
         if fusion not in ("feature", "score"):
             raise ValueError(f"fusion {fusion!r}: 'feature' or 'score'")
         query_feat = query_feat.float().contiguous()
+        if max_refs is not None:
+            M = self._check_max_refs(max_refs, reference_feats.shape[1])
+            sel = hip.op_multiref_select(template_poses, ref_poses.to(query_feat.device), n_refs, max_refs=M, weighting=weighting, tau_deg=tau_deg,
+                                         dist_kind=dist_kind)
+            similarity, per_ref, bank = self._score_selected(query_feat, reference_feats, sel, fusion, return_per_reference, self.bank_dtype)
+            _, nearest_idx = hip.topk(similarity, k)
+            return MultiRefResult(similarity, nearest_idx, sel.weights, per_ref, bank, sel.src)
         prep = hip.op_multiref_prepare(template_poses, ref_poses.to(query_feat.device), n_refs, weighting=weighting, tau_deg=tau_deg,
                                        dist_kind=dist_kind)
         bank = self.generate_templates_multi_from_feat(reference_feats, prep.all_relativeR)
@@ -474,6 +499,107 @@ class PoseConditional(nn.Module):
         _, nearest_idx = hip.topk(similarity, k)
         return MultiRefResult(similarity, nearest_idx, prep.weights, per_ref if return_per_reference else None, bank)
 
+    # ---- the M nearest references per pose ----
+    @staticmethod
+    def _check_max_refs(max_refs, R):
+        M = int(max_refs)
+        if not 1 <= M <= R:
+            raise ValueError(f"max_refs {max_refs}: 1 .. R = {R}")
+        return M
+
+    def _generate_selected(self, reference_feats, sel, out_dtype="f32"):
+        """The bank (B,M,S,C,h,w) of a selection (hip.op_multiref_select): hypothesis (b, m, s) is the U-Net's map of sel.all_relativeR[b, m, s]
+        from reference sel.src[b, m, s].  Every hypothesis brings its own gathered source (forward_hypotheses with one pose per source), in
+        chunks of max_hypotheses_per_launch; the f16x2 range check is not deferred."""
+        B, M, S = sel.src.shape
+        feat = reference_feats.shape[2:]
+        x = hip.op_multiref_gather(reference_feats, sel.src).view(B * M * S, *feat)
+        poses = sel.all_relativeR.view(B * M * S, 1, 6)
+        bank = torch.empty((B * M * S, 1, self.u_net.channels, *feat[1:]), dtype=hip.torch_dtype(hip.dtype_code(out_dtype)), device=x.device)
+        for i in range(0, B * M * S, self.max_hyp):
+            j = min(B * M * S, i + self.max_hyp)
+            self.u_net.forward_hypotheses(x[i:j], poses[i:j], out=bank[i:j], out_dtype=out_dtype, defer_range_check=False)
+        return bank.view(B, M, S, *bank.shape[2:])
+
+    def _score_selected(self, query_feat, reference_feats, sel, fusion, want_per_ref=False, out_dtype="f32"):
+        """(scores (B,S), the per-slot rows (B,M,S) or None, the bank) of a selection: the ABI 21 scoring with R := M; M = 1: nope_similarity."""
+        bank = self._generate_selected(reference_feats, sel, out_dtype)
+        B, M, S = bank.shape[:3]
+        per_ref = None
+        if M == 1:
+            scores = hip.similarity(query_feat, bank.view(B, S, *bank.shape[3:]))
+            return scores, (scores.view(B, 1, S) if want_per_ref else None), bank
+        if fusion == "score" or want_per_ref:
+            per_ref = hip.similarity(query_feat, bank.view(B, M * S, *bank.shape[3:])).view(B, M, S)
+        if fusion == "feature":
+            scores = hip.multiref_similarity(query_feat, bank, sel.weights)
+        else:
+            scores = hip.op_multiref_fuse_scores(per_ref, sel.weights)
+        return scores, (per_ref if want_per_ref else None), bank
+
+    @torch.no_grad()
+    def retrieve_multi_coarse_to_fine_from_feat(self, query_feat, reference_feats, ref_poses, template_poses, n_refs=None, max_refs=1,
+                                                fusion="feature", weighting="softmax", tau_deg=30.0, ref_dist_kind=hip.C2F_ROTATION,
+                                                stage_of=None, **kw):
+        """retrieve_coarse_to_fine_from_feat from R posed references: every pose the search admits is generated from its max_refs nearest
+        references and scored as retrieve_multi_from_feat(max_refs=...) scores it.  ref_dist_kind is the distance between grid pose and
+        reference pose (retrieve_multi_from_feat's dist_kind); the search's own keyword arguments -- its dist_kind between grid poses among
+        them -- pass through.  Returns the search's C2FResult."""
+        from .search import coarse_to_fine_search
+        if self.similarity_metric != "l2":
+            return None
+        self._no_multi_ref_shards()
+        if fusion not in ("feature", "score"):
+            raise ValueError(f"fusion {fusion!r}: 'feature' or 'score'")
+        M = self._check_max_refs(max_refs, reference_feats.shape[1])
+        query_feat = query_feat.float().contiguous()
+        ref_poses = ref_poses.to(query_feat.device)
+        if stage_of is None:
+            from .poses import grid_stages_for_size
+            stage_of = grid_stages_for_size(template_poses.shape[1])
+        B, N = query_feat.shape[0], template_poses.shape[1]
+        # the search only gathers pose rows from its all_relativeR and hands them to `evaluate`, which makes its own: any finite rows do
+        rows = hip.op_multiref_select(template_poses, ref_poses, n_refs, max_refs=1, weighting="nearest", dist_kind=ref_dist_kind).all_relativeR
+
+        def evaluate(_, cand):
+            sel = hip.op_multiref_select(template_poses, ref_poses, n_refs, max_refs=M, cand=cand, weighting=weighting, tau_deg=tau_deg,
+                                         dist_kind=ref_dist_kind)
+            return self._score_selected(query_feat, reference_feats, sel, fusion)[0]
+        return coarse_to_fine_search(evaluate, rows.view(B, N, 6), template_poses, stage_of, **kw)
+
+    @torch.no_grad()
+    def refine_multi_from_feat(self, query_feat, reference_feats, ref_poses, template_poses, nearest_idx, n_refs=None, dist_kind=hip.C2F_ROTATION,
+                               iters=3, fd_step=1e-2, max_step_deg=10.0, damping=1e-6):
+        """refine_from_feat from R posed references: each of the k candidates nearest_idx (B,k) is refined through ITS nearest reference
+        (nope_op_multiref_select with the candidates and M = 1).  The accept / revert baseline, score_init, is the score of the grid pose
+        predicted from that same reference -- slot 0 of the first iteration's forward --, not the fused row's.  template_poses (B|1,N,3,3)
+        is needed; pred_R does not depend on the reference.  Returns a RefineResult."""
+        self._no_multi_ref_shards()
+        query_feat = query_feat.float().contiguous()
+        B, k = nearest_idx.shape
+        sel = hip.op_multiref_select(template_poses, ref_poses.to(query_feat.device), n_refs, max_refs=1, cand=nearest_idx, weighting="nearest",
+                                     dist_kind=dist_kind)
+        x = hip.op_multiref_gather(reference_feats, sel.src).view(B * k, *reference_feats.shape[2:])
+
+        def forward(poses, out):                    # candidate-major: (B, n k, 6) is (B k, n, 6), n = 7 or 1
+            n = poses.shape[1] // k
+            self._forward_poses(x, poses.view(B * k, n, 6), out.view(B * k, n, *out.shape[2:]))
+            return out
+        slot = torch.arange(k, device=query_feat.device).expand(B, k).contiguous()
+        return self._refine(query_feat, forward, sel.all_relativeR.view(B, k, 6), slot, nearest_idx, None, iters, fd_step, max_step_deg, damping,
+                            template_poses)
+
+    def _encode_multi(self, query, references):
+        """(query_feat, reference_feats (B,R,C,h,w)): the references encoded as one batch of B R images; the query's encoder pass runs on the
+        side stream underneath them, as in generate_and_retrieve."""
+        B, R = references.shape[:2]
+        enc = self.u_net.encoder
+        with hip.overlap_stream(query) as side:
+            query_feat = enc.encode_image(query, mode="mode")
+        reference_feats = enc.encode_image(references.reshape(B * R, *references.shape[2:]), mode="mode")
+        side.join(query_feat)
+        return query_feat, reference_feats.reshape(B, R, *reference_feats.shape[1:])
+
     @torch.no_grad()
     def retrieve_multi(self, query, references, reference_poses, template_poses, **kw):
         """Encode, then retrieve_multi_from_feat (same keyword arguments).  query (B,3,S,S); references (B,R,3,S,S), encoded as one batch of
@@ -481,27 +607,52 @@ class PoseConditional(nn.Module):
         if self.similarity_metric != "l2":
             return None
         self._no_multi_ref_shards()
-        B, R = references.shape[:2]
-        enc = self.u_net.encoder
-        with hip.overlap_stream(query) as side:
-            query_feat = enc.encode_image(query, mode="mode")
-        reference_feats = enc.encode_image(references.reshape(B * R, *references.shape[2:]), mode="mode")
-        side.join(query_feat)
-        return self.retrieve_multi_from_feat(query_feat, reference_feats.reshape(B, R, *reference_feats.shape[1:]), reference_poses, template_poses, **kw)
+        query_feat, reference_feats = self._encode_multi(query, references)
+        return self.retrieve_multi_from_feat(query_feat, reference_feats, reference_poses, template_poses, **kw)
 
     @torch.no_grad()
-    def predict_pose_multi(self, query, references, reference_poses, template_poses, distinct_deg=None, symmetry=None, temperature=1.0, **kw):
+    def retrieve_multi_coarse_to_fine(self, query, references, reference_poses, template_poses, **kw):
+        """Encode, then retrieve_multi_coarse_to_fine_from_feat (same keyword arguments)."""
+        if self.similarity_metric != "l2":
+            return None
+        self._no_multi_ref_shards()
+        query_feat, reference_feats = self._encode_multi(query, references)
+        return self.retrieve_multi_coarse_to_fine_from_feat(query_feat, reference_feats, reference_poses, template_poses, **kw)
+
+    _REFINE_KEYS = ("fd_step", "max_step_deg", "damping")
+
+    @torch.no_grad()
+    def predict_pose_multi(self, query, references, reference_poses, template_poses, distinct_deg=None, symmetry=None, temperature=1.0,
+                           max_refs=None, coarse_to_fine=None, refine_iters=0, **kw):
         """predict_pose from R posed references: (pred_R (B,k,3,3) f64, score (B,k) f32) = template_poses[nearest_idx] and the fused scores of
         retrieve_multi (whose keyword arguments pass through); pred_R[:, 0] is the answer.  distinct_deg (None: the plain top-k): the k
         candidates are the seeds of the distinct modes of the fused row within that radius under `symmetry` (op_pose_modes with fill, as
-        predict_pose)."""
-        r = self.retrieve_multi(query, references, reference_poses, template_poses, **kw)
-        if r is None:
+        predict_pose).  max_refs (None: all R references per pose): retrieve_multi_from_feat's.  coarse_to_fine (None: the exhaustive
+        retrieval; True, or a dict of the search's keyword arguments): retrieve_multi_coarse_to_fine_from_feat with max_refs (None: 1).
+        refine_iters above 0: the candidates refined by refine_multi_from_feat (fd_step, max_step_deg, damping pass to it), in ITS order."""
+        if self.similarity_metric != "l2":
             return None
+        self._no_multi_ref_shards()
+        refine_kw = {key: kw.pop(key) for key in self._REFINE_KEYS if key in kw}
+        query_feat, reference_feats = self._encode_multi(query, references)
+        if coarse_to_fine is not None and coarse_to_fine is not False:
+            c2f_kw = {} if coarse_to_fine is True else dict(coarse_to_fine)
+            unknown = sorted(set(kw) - {"n_refs", "fusion", "weighting", "tau_deg", "k", "dist_kind"})
+            if unknown:          # (the exhaustive branch raises for them as well: nothing is dropped silently)
+                raise TypeError(f"predict_pose_multi(coarse_to_fine=...) got unexpected keyword arguments {unknown}")
+            c2f_kw.update({("ref_dist_kind" if key == "dist_kind" else key): v for key, v in kw.items()})
+            r = self.retrieve_multi_coarse_to_fine_from_feat(query_feat, reference_feats, reference_poses, template_poses,
+                                                             max_refs=1 if max_refs is None else max_refs, **c2f_kw)
+        else:
+            r = self.retrieve_multi_from_feat(query_feat, reference_feats, reference_poses, template_poses, max_refs=max_refs, **kw)
         similarity, nearest_idx = r.similarity, r.nearest_idx
         if distinct_deg is not None:
             nearest_idx = hip.op_pose_modes(similarity, template_poses, symmetry, temperature=temperature, radius_deg=distinct_deg,
                                             max_modes=nearest_idx.shape[1], fill=True, want_prob=False).idx
+        if refine_iters > 0:
+            rr = self.refine_multi_from_feat(query_feat, reference_feats, reference_poses, template_poses, nearest_idx, n_refs=kw.get("n_refs"),
+                                             dist_kind=kw.get("dist_kind", hip.C2F_ROTATION), iters=refine_iters, **refine_kw)
+            return rr.pred_R, rr.score
         tp = template_poses.to(device=nearest_idx.device, dtype=torch.float64)
         rows = torch.arange(nearest_idx.shape[0], device=nearest_idx.device)[:, None] if tp.shape[0] != 1 else 0
         return tp[rows, nearest_idx], torch.gather(similarity, 1, nearest_idx)
