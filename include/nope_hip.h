@@ -95,9 +95,10 @@ typedef void* nope_stream_t;
  * 19: nope_conv_op gains gn_emb, gn_emb_stride, gn_self, gn_resid_rep (the conv's own GroupNorm);
  * 20: nope_op_c2f_expand, nope_op_c2f_commit;
  * 21: nope_op_multiref_prepare, nope_multiref_similarity, nope_op_multiref_fuse_scores;
- * 22: nope_op_multiref_select, nope_op_multiref_gather.  Callers compare nope_abi_version() against the
+ * 22: nope_op_multiref_select, nope_op_multiref_gather;
+ * 23: nope_robust_similarity, nope_op_residual_maps, nope_op_pool_mask.  Callers compare nope_abi_version() against the
  * header they were built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 22
+#define NOPE_ABI_VERSION 23
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -314,6 +315,47 @@ int nope_op_multiref_select(const double* template_poses, int64_t pose_stride_b,
                             const int* cand, int S, int M, int weighting, double tau_rad, int dist_kind, int* src, float* all_relativeR, float* weights,
                             double* dist, int* status, int B, nope_stream_t stream);
 int nope_op_multiref_gather(const float* reference_feats, const int* src, float* out, int B, int R, int J, int64_t L, nope_stream_t stream);
+
+/* (ABI 23) Occlusion-robust scoring: masked and trimmed template scores.  No reference counterpart: the reference
+ * scores every pixel of the latent map (src/model/model.py:257-262), so one covered region of a query crop adds a large term to the score
+ * of the CORRECT template.  Two mechanisms, usable together: a mask (the caller knows which latent pixels show the object: only those are
+ * scored) and a trim (nobody knows where the occluder is: per hypothesis the largest per-pixel terms are dropped, as a fraction of the
+ * scored pixels -- a least-trimmed sum, which is scale-free).  Off by default everywhere; an addition next to the "l2" metric.
+ *
+ * With d[b,n,p] = sqrt( sum_c (q[b,c,p] - t[b,n,c,p])^4 ) in nope_similarity's arithmetic per bank type (f32 accumulation; sqrtf for f32
+ * banks, the hardware square root for the 16-bit banks):
+ *     A[b]  = { p : mask[b,p] != 0 }   (mask NULL: all H W pixels),  a = |A[b]|
+ *     t     = min(a - 1, (int)floorf(trim * (float)a))               trim f32 in [0, 1): one f32 product, then floor
+ *     m     = a - t                                                  (m >= 1 whenever a >= 1)
+ *     score[b,n] = - ( sum of the m smallest values of { d[b,n,p] : p in A[b] } )
+ * The sum of the m smallest is a multiset quantity: ties need no rule.  It is formed as s_less + (m - c_less) v, v the m-th smallest value
+ * (an exact bitwise selection on the f32 patterns, which are ordered because d >= 0), s_less and c_less the sum and the count of the values
+ * strictly below v; the second term is added only when m - c_less > 0 (an infinite v never meets a factor 0).
+ *   - a pixel outside A[b] is a select: its bank and query values do not enter, NaN or inf there does not leak;
+ *   - any NaN among the d of A[b] makes the score NaN (NaNs are never trimmed away as "the largest"); +inf is an ordinary largest value:
+ *     trimmed it leaves a finite score, kept it gives -inf;
+ *   - a == 0: the whole row is NaN;  all kept terms zero: the score is -0.0, as a planted match scores in nope_similarity;
+ *   - trim == 0 with mask == NULL is nope_similarity's definition from another kernel: the two agree to the last bits of the sums, not bit
+ *     for bit (the statement made for nope_multiref_similarity);  trim == 0 skips the selection: a plain masked sum;
+ *   - fixed-shape reductions, no floating-point atomics: bit-identical from run to run.
+ *   q, bank, bank_dtype, bank_stride_b (0 = one shared bank), scores, score_ld and the shape limits: as nope_similarity
+ *   mask    (B, H, W) uint8 or NULL
+ * NOPE_ERR_ARG: trim outside [0, 1) or NaN, and nope_similarity's cases.
+ *
+ * nope_op_residual_maps: the d planes of chosen hypotheses -- where a match disagrees.  out[b, j, p] = d[b, idx[b, j], p], (B, k, H, W) f32;
+ * idx (B, k) int64 or NULL (templates 0..k, k <= N).  An index outside [0, N) gives a NaN plane, never a wild read.  Any H, W >= 1.
+ *
+ * nope_op_pool_mask: an image-resolution coverage plane (B, S_h, S_w) -> the latent mask (B, H, W) uint8 in {0, 1}; S_h % H == 0 and
+ * S_w % W == 0 (else NOPE_ERR_ARG); a cell is (S_h / H) x (S_w / W) pixels.
+ *   is_u8 != 0: cover is uint8 alpha; mask = 1 where the cell's integer byte sum is >= min_sum_u8 (exact).
+ *   is_u8 == 0: cover is an f32 visibility in [0, 1]; mask = 1 where the cell's f32 sum, taken in row-major order within the cell, divided
+ *               by the f32 area is >= min_mean_f32 (a NaN never is). */
+int nope_robust_similarity(const float* q, const void* bank, int bank_dtype, const uint8_t* mask, float trim, float* scores, int B, int N, int C,
+                           int H, int W, int64_t bank_stride_b, int score_ld, nope_stream_t stream);
+int nope_op_residual_maps(const float* q, const void* bank, int bank_dtype, const int64_t* idx, float* out, int B, int N, int k, int C, int H,
+                          int W, int64_t bank_stride_b, nope_stream_t stream);
+int nope_op_pool_mask(const void* cover, int is_u8, int B, int S_h, int S_w, int H, int W, int64_t min_sum_u8, float min_mean_f32, uint8_t* mask,
+                      nope_stream_t stream);
 
 /* (ABI 15) Sub-grid pose refinement: Gauss-Newton on SO(3) through the U-Net.  No reference counterpart: the reference's prediction is
  * template_poses[nearest_idx] (src/model/model.py:352-354), a vertex of the template grid (26 templates: ~32 degrees apart).  The U-Net is a

@@ -175,6 +175,23 @@ int nope_op_multiref_gather(const float* reference_feats, const int* src, float*
     return launch_multiref_gather(reference_feats, src, out, B, R, J, (long long)L, (hipStream_t)stream);
 }
 
+int nope_robust_similarity(const float* q, const void* bank, int bank_dtype, const uint8_t* mask, float trim, float* scores, int B, int N, int C,
+                           int H, int W, int64_t bank_stride_b, int score_ld, nope_stream_t stream) {
+    if (H <= 0 || W <= 0) return NOPE_ERR_ARG;
+    return launch_robust_similarity(q, bank, bank_dtype, mask, trim, scores, B, N, C, H * W, (long long)bank_stride_b, score_ld, (hipStream_t)stream);
+}
+
+int nope_op_residual_maps(const float* q, const void* bank, int bank_dtype, const int64_t* idx, float* out, int B, int N, int k, int C, int H,
+                          int W, int64_t bank_stride_b, nope_stream_t stream) {
+    if (H <= 0 || W <= 0) return NOPE_ERR_ARG;
+    return launch_residual_maps(q, bank, bank_dtype, (const long long*)idx, out, B, N, k, C, H * W, (long long)bank_stride_b, (hipStream_t)stream);
+}
+
+int nope_op_pool_mask(const void* cover, int is_u8, int B, int S_h, int S_w, int H, int W, int64_t min_sum_u8, float min_mean_f32, uint8_t* mask,
+                      nope_stream_t stream) {
+    return launch_pool_mask(cover, is_u8, B, S_h, S_w, H, W, (long long)min_sum_u8, min_mean_f32, mask, (hipStream_t)stream);
+}
+
 int nope_op_refine_init(const float* all_relativeR, int64_t N, const int64_t* idx, double* dR, double* dR_init, float* poses, int* status,
                         int B, int k, double fd_step, nope_stream_t stream) {
     return launch_refine_init(all_relativeR, (long long)N, (const long long*)idx, dR, dR_init, poses, status, B, k, fd_step, (hipStream_t)stream);

@@ -566,6 +566,13 @@ int launch_nearest2(int dt, const void* x, void* y, long long n, int H, int W, i
 int launch_similarity(const float* q, const void* bank, int bank_dt, float* scores, int B, int N, int C, int HW,
                       long long bank_stride_b, int score_ld, hipStream_t s);
 int launch_topk(const float* scores, long long* idx, float* vals, int B, int N, int k, int ld, hipStream_t s, const long long* map = nullptr);
+// kernels_robust.hip
+int launch_robust_similarity(const float* q, const void* bank, int bank_dt, const unsigned char* mask, float trim, float* scores, int B, int N, int C,
+                             int HW, long long bank_stride_b, int score_ld, hipStream_t s);
+int launch_residual_maps(const float* q, const void* bank, int bank_dt, const long long* idx, float* out, int B, int N, int k, int C, int HW,
+                         long long bank_stride_b, hipStream_t s);
+int launch_pool_mask(const void* cover, int is_u8, int B, int Sh, int Sw, int H, int W, long long min_sum_u8, float min_mean_f32, unsigned char* mask,
+                     hipStream_t s);
 int launch_gather_topk(const float* gathered, int G, int B, int N, float* scores, long long* idx, float* vals, int k, hipStream_t s);
 int launch_geodesic(const double* poses, long long stride_b, int N, const long long* idx, const double* gt, const int* symmetry,
                     double* err, int* status, int B, int k, hipStream_t s);

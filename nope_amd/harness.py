@@ -112,6 +112,32 @@ def synthetic_batch(batch: int, n_templates: int, size: int, seed: int = 2022, d
     return {k: v.to(device) for k, v in out.items()}
 
 
+def occlude_queries(batch: Dict[str, torch.Tensor], frac: float, seed: int = 2022):
+    """Paste ONE axis-aligned rectangle of seeded uniform noise covering `frac` of the area over each query image (no reference counterpart:
+    a stand-in for another object in front of the crop).  Returns (a new batch -- the same tensors, `query` replaced and `visibility` added --,
+    visibility (B, S, S) f32: 0 inside the rectangle, 1 elsewhere; hip.op_pool_mask turns it into the latent mask).  The rectangle is as square
+    as the size allows, its place drawn per sample; everything is drawn on the host from `seed`, whatever the batch's device."""
+    if not (0.0 <= frac < 1.0):
+        raise ValueError(f"occlude_queries: frac {frac!r} outside [0, 1)")
+    query = batch["query"]
+    B, Cq, Sh, Sw = query.shape
+    g = torch.Generator().manual_seed(seed)
+    rh = min(Sh, max(1, int(round((frac ** 0.5) * Sh)))) if frac > 0 else 0
+    rw = min(Sw, max(1, int(round(frac * Sh * Sw / rh)))) if frac > 0 else 0
+    occluded = query.detach().cpu().clone()
+    visibility = torch.ones(B, Sh, Sw, dtype=torch.float32)
+    for b in range(B):
+        y0 = int(torch.randint(0, Sh - rh + 1, (1,), generator=g))
+        x0 = int(torch.randint(0, Sw - rw + 1, (1,), generator=g))
+        noise = torch.rand(Cq, rh, rw, generator=g) * 2 - 1
+        occluded[b, :, y0:y0 + rh, x0:x0 + rw] = noise.to(occluded.dtype)
+        visibility[b, y0:y0 + rh, x0:x0 + rw] = 0.0
+    out = dict(batch)
+    out["query"] = occluded.to(query.device)
+    out["visibility"] = visibility.to(query.device)
+    return out, out["visibility"]
+
+
 def build_model(seed: int = 2022, compute_dtype="f32", bank_dtype="f32", device="cuda", u_net_dim: Optional[int] = None,
                 save_dir: Optional[str] = None, template_parallel: bool = False, max_hypotheses_per_launch: int = 512, encoder: str = "template"):
     """encoder: "template" (template_base.yaml's FeatureExtractor), "vae" (vae_base.yaml's VAE_StableDiffusion at the SD-1.5 shapes,
@@ -156,7 +182,7 @@ def geodesic_deg(predR: torch.Tensor, gtR: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), save_path: Optional[str] = None, visualize: bool = False,
                   errors_out: Optional[list] = None, refine_iters: int = 0, distinct_deg: Optional[float] = None, temperature: float = 1.0,
-                  coarse_to_fine=None, multi_ref=None):
+                  coarse_to_fine=None, multi_ref=None, robust=None):
     """The body of PoseConditional.eval_geodesic (model.py:268-376).  visualize (effective with a decoding encoder and model.save_dir only,
     model.py:269-274; needs batch["gt_templates"] (B, N, 3, S, S)): the three kinds of pictures and the video under save_dir/media
     (nope_amd/vis.py), and `vis_imgs` -- the full-size f16 grid of the retrieved picture -- in the saved predictions.  errors_out: a list that
@@ -176,7 +202,12 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     metric keys under "multi/" and "multi/top1_agree"; the saved predictions gain `multi_similarity`.  Two keys of the dict are taken out here:
     "coarse_to_fine" (True or a dict of the search's keyword arguments): the multi-reference retrieval itself runs in stages
     (PoseConditional.retrieve_multi_coarse_to_fine, max_refs 1 unless given) and "multi/evaluated_frac" is added; "refine_iters" > 0: its
-    candidates are refined, each through its nearest reference (refine_multi_from_feat), and scored under "multi_refined/"."""
+    candidates are refined, each through its nearest reference (refine_multi_from_feat), and scored under "multi_refined/".  robust (no
+    reference counterpart; None: nothing changes; {"trim": t, "use_mask": bool}): the SAME bank is scored once more with the occlusion-robust
+    score (hip.robust_similarity: the largest terms of a fraction t of the scored pixels dropped per hypothesis; with use_mask only the latent
+    pixels whose cell of batch["visibility"] (B, S, S) f32 -- occlude_queries' plane -- is at least half visible are scored) -- the same metric
+    keys under "robust/" and "robust/top1_agree"; the saved predictions gain `robust_similarity`.  No accuracy is claimed for it: the weights
+    are synthetic."""
     visualize = bool(visualize) and model._decoder() is not None and model.save_dir is not None
     if visualize and "gt_templates" not in batch:
         raise ValueError('eval_geodesic(visualize=True) with a decoding encoder and save_dir needs batch["gt_templates"] (B, N, 3, S, S): '
@@ -184,7 +215,7 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
     query, reference = batch["query"], batch["reference"]
     loss = model.forward(query, reference, batch["gt_relativeR"])
     if not visualize:
-        similarity, nearest_idx, _ = model.generate_and_retrieve(query, reference, batch["all_relativeR"])
+        similarity, nearest_idx, bank = model.generate_and_retrieve(query, reference, batch["all_relativeR"])
     else:
         from . import vis
         media, tag = os.path.join(model.save_dir, "media"), f"step{model.global_step}_rank{model.global_rank}"
@@ -261,6 +292,23 @@ def eval_geodesic(model, batch: Dict[str, torch.Tensor], thresholds=(15, 30), sa
             res.update({f"multi_refined/{k}": float(v) for k, v in refined.items()})
         if save_path:
             extra.update(multi_similarity=mr.similarity.cpu().numpy())
+    if robust is not None and robust is not False:
+        rkw = dict(robust)
+        use_mask, trim = bool(rkw.pop("use_mask", False)), float(rkw.pop("trim", 0.0))
+        if rkw:
+            raise TypeError(f"eval_geodesic(robust=...) got unexpected keys {sorted(rkw)}")
+        q_feat = model.u_net.encoder.encode_image(query, mode="mode")
+        mask = None
+        if use_mask:
+            if "visibility" not in batch:
+                raise ValueError('eval_geodesic(robust={"use_mask": True}) needs batch["visibility"] (B, S, S) f32 (occlude_queries makes it)')
+            mask = hip.op_pool_mask(batch["visibility"].float(), q_feat.shape[2:], 0.5)
+        r_sim, r_idx = model.retrieval_from_feat(q_feat, bank, k=nearest_idx.shape[1], robust={"mask": mask, "trim": trim})
+        _, r_metric = GeodesicError(list(thresholds)).from_indices(batch["template_poses"][:1], r_idx, batch["query_pose"], sym)
+        res.update({f"robust/{k}": float(v) for k, v in r_metric.items()})
+        res["robust/top1_agree"] = float((r_idx[:, 0] == nearest_idx[:, 0]).float().mean())
+        if save_path:
+            extra.update(robust_similarity=r_sim.cpu().numpy())
     if save_path:
         if visualize:       # model.py:334-339,367-375: the un-resized grid of the last picture
             extra["vis_imgs"] = hip.op_vis_grid(retrieved)[0].cpu().numpy()
@@ -346,15 +394,23 @@ def main(argv=None):
     ap.add_argument("--max-refs", type=int, default=None, metavar="M",
                     help="with --references: generate every pose from its M nearest references only (M U-Net passes per pose whatever R is); "
                          "with --coarse-to-fine / --refine as well, the multi-reference retrieval runs in stages / its candidates are refined")
+    ap.add_argument("--occlude", type=float, default=0.0, metavar="FRAC", help="paste a rectangle of seeded noise covering FRAC of each query image (occlude_queries)")
+    ap.add_argument("--trim", type=float, default=0.0, metavar="FRAC",
+                    help="also score the bank with the occlusion-robust score, the largest terms of FRAC of the scored pixels dropped per hypothesis (robust/...)")
+    ap.add_argument("--use-mask", action="store_true", help="with --occlude: the robust score reads only the latent pixels the rectangle leaves at least half visible")
     ap.add_argument("--tau-deg", type=float, default=30.0, metavar="D", help="with --weighting softmax: the temperature, degrees of pose distance")
     a = ap.parse_args(argv)
     if not 1 <= a.references <= hip.MULTIREF_MAX_REFS:
         ap.error(f"--references: 1 .. {hip.MULTIREF_MAX_REFS}")
     if a.max_refs is not None and not 1 <= a.max_refs <= a.references:
         ap.error("--max-refs: 1 .. --references")
+    if not 0.0 <= a.occlude < 1.0 or not 0.0 <= a.trim < 1.0:
+        ap.error("--occlude / --trim: a fraction in [0, 1)")
+    if a.use_mask and a.occlude <= 0.0:
+        ap.error("--use-mask needs --occlude (the mask is the rectangle's complement)")
     if a.data_root:
-        if a.refine or a.distinct_deg is not None or a.coarse_to_fine or a.references > 1:
-            ap.error("--refine / --distinct-deg / --coarse-to-fine / --references apply to the synthetic batch (a split's pooled scores carry none of them)")
+        if a.refine or a.distinct_deg is not None or a.coarse_to_fine or a.references > 1 or a.occlude or a.trim:
+            ap.error("--refine / --distinct-deg / --coarse-to-fine / --references / --occlude / --trim apply to the synthetic batch (a split's pooled scores carry none of them)")
         return main_dataset(a, ap)
     a.size = a.size or 128
     if a.coarse_to_fine and a.pose_level is None:
@@ -379,12 +435,15 @@ def main(argv=None):
         multi = dict(fusion=a.fusion, weighting=a.weighting, tau_deg=a.tau_deg)
         if a.max_refs is not None:          # the sparse path and, through it, the stages and the refinement from several references
             multi.update(max_refs=a.max_refs, coarse_to_fine=c2f, refine_iters=a.refine)
+    robust = {"trim": a.trim, "use_mask": a.use_mask} if (a.trim > 0.0 or a.use_mask) else None
     for name, batch in batches.items():                         # test_step, model.py:550-565
+        if a.occlude > 0.0:
+            batch, _ = occlude_queries(batch, a.occlude, a.seed)
         t0 = time.time()
         save = os.path.join(a.save_dir, "predictions", f"pred_step0_rank{model.global_rank}") if a.save_dir else None
         sim, idx, res = eval_geodesic(model, batch, save_path=save, visualize=a.visualize, refine_iters=a.refine, distinct_deg=a.distinct_deg,
                                       temperature=a.temperature, coarse_to_fine=c2f,
-                                      multi_ref=multi)
+                                      multi_ref=multi, robust=robust)
         torch.cuda.synchronize()
         res.update(dataloader=name, seconds=time.time() - t0, nearest_idx=idx.tolist())
         print(json.dumps(res))

@@ -16,7 +16,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 22                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 23                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -120,6 +120,9 @@ _PROTOS = {
     "nope_op_multiref_fuse_scores": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
     "nope_op_multiref_select": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "nope_op_multiref_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
+    "nope_robust_similarity": (_i, [_vp, _vp, _i, _vp, C.c_float, _vp, _i, _i, _i, _i, _i, _i64, _i, _vp]),
+    "nope_op_residual_maps": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp]),
+    "nope_op_pool_mask": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i64, C.c_float, _vp, _vp]),
     "nope_op_refine_init": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp]),
     "nope_op_refine_normal_eq_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "nope_op_refine_normal_eq": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, _vp, _sz, _vp]),
@@ -684,6 +687,121 @@ def op_multiref_fuse_scores(per_ref: torch.Tensor, weights: torch.Tensor, out: O
     l.check(l.dll.nope_op_multiref_fuse_scores(_ptr(per_ref), _ptr(weights), _ptr(out), B, R, N, out.shape[1], _stream(per_ref)),
             "nope_op_multiref_fuse_scores")
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# occlusion-robust scoring (csrc/kernels_robust.hip; the drivers are PoseConditional.retrieval*(robust=...) / retrieve_robust)
+# --------------------------------------------------------------------------------------------
+def _robust_mask(mask: Optional[torch.Tensor], B: int, H: int, W: int, device) -> Optional[torch.Tensor]:
+    """mask (B, H, W) uint8 | bool -> contiguous uint8 on `device` (bool is reinterpreted, not converted: True is the byte 1)."""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+        raise NopeError(f"mask must be a uint8 or bool tensor, got {getattr(mask, 'dtype', type(mask))}")
+    if tuple(mask.shape) != (B, H, W):
+        raise NopeError(f"mask {tuple(mask.shape)}: expected {(B, H, W)}")
+    require_device(mask)
+    mask = mask.to(device).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def check_trim(trim) -> float:
+    trim = float(trim)
+    if not (0.0 <= trim < 1.0):         # (a NaN fails both comparisons)
+        raise NopeError(f"trim {trim!r}: a fraction in [0, 1)")
+    return trim
+
+
+def robust_similarity(q: torch.Tensor, bank: torch.Tensor, mask: Optional[torch.Tensor] = None, trim: float = 0.0,
+                      out: Optional[torch.Tensor] = None, col_offset: int = 0) -> torch.Tensor:
+    """Masked, trimmed template scores (include/nope_hip.h: nope_robust_similarity): minus the sum of the m smallest per-pixel terms of
+    `similarity` over the pixels of `mask`, m = a - min(a - 1, floor(trim a)).  q (B,C,H,W) f32; bank (B|1,N,C,H,W) f32|bf16|fp16; mask
+    (B,H,W) uint8|bool or None (every pixel); trim in [0, 1).  With `out` (B, Ntotal) given, writes columns [col_offset, col_offset+N)."""
+    require_device(q)
+    trim = check_trim(trim)
+    q = _f32c(q)
+    B, Cc, H, W = q.shape
+    if bank.dim() != 5 or tuple(bank.shape[2:]) != (Cc, H, W) or bank.shape[0] not in (1, B):
+        raise NopeError(f"bank shape {tuple(bank.shape)} does not match query {tuple(q.shape)}")
+    require_device(bank)
+    mask = _robust_mask(mask, B, H, W, q.device)
+    if bank.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        bank = bank.float()
+    bank = bank.contiguous()
+    N = bank.shape[1]
+    if N == 0:
+        return torch.empty((B, 0), dtype=torch.float32, device=q.device) if out is None else out
+    stride_b = 0 if (bank.shape[0] == 1 and B > 1) else N * Cc * H * W
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.float32, device=q.device)
+        col_offset = 0
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape[0] == B
+    ld = out.shape[1]
+    assert 0 <= col_offset and col_offset + N <= ld
+    l = lib()
+    l.check(l.dll.nope_robust_similarity(_ptr(q), _ptr(bank), dtype_code(bank.dtype), _ptr(mask), trim, out.data_ptr() + 4 * col_offset, B, N, Cc,
+                                         H, W, stride_b, ld, _stream(q)), "nope_robust_similarity")
+    return out
+
+
+def op_residual_maps(q: torch.Tensor, bank: torch.Tensor, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The per-pixel terms d[b, idx[b, j], p] = sqrt(sum_c (q - t)^4) of chosen hypotheses -- where a match disagrees -- (B, k, H, W) f32
+    (nope_op_residual_maps).  q (B,C,H,W) f32; bank (B|1,N,C,H,W) f32|bf16|fp16; idx (B, k) int64 as hip.topk returns it, or None: every
+    template.  An index outside [0, N) gives a NaN plane."""
+    require_device(q)
+    q = _f32c(q)
+    B, Cc, H, W = q.shape
+    if bank.dim() != 5 or tuple(bank.shape[2:]) != (Cc, H, W) or bank.shape[0] not in (1, B):
+        raise NopeError(f"bank shape {tuple(bank.shape)} does not match query {tuple(q.shape)}")
+    require_device(bank)
+    if bank.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        bank = bank.float()
+    bank = bank.contiguous()
+    N = bank.shape[1]
+    if idx is not None:
+        if idx.dim() != 2 or idx.shape[0] != B:
+            raise NopeError(f"idx {tuple(idx.shape)}: expected ({B}, k)")
+        idx = idx.to(device=q.device, dtype=torch.int64).contiguous()
+        k = idx.shape[1]
+    else:
+        k = N
+    out = torch.empty((B, k, H, W), dtype=torch.float32, device=q.device)
+    if B == 0 or k == 0:
+        return out
+    if N == 0:
+        return out.fill_(float("nan"))
+    stride_b = 0 if (bank.shape[0] == 1 and B > 1) else N * Cc * H * W
+    l = lib()
+    l.check(l.dll.nope_op_residual_maps(_ptr(q), _ptr(bank), dtype_code(bank.dtype), _ptr(idx), _ptr(out), B, N, k, Cc, H, W, stride_b, _stream(q)),
+            "nope_op_residual_maps")
+    return out
+
+
+def op_pool_mask(cover: torch.Tensor, hw, threshold: float = 0.5) -> torch.Tensor:
+    """An image-resolution coverage plane -> the latent mask robust_similarity takes (nope_op_pool_mask).  cover (B, S_h, S_w) uint8 alpha
+    or f32 visibility in [0, 1]; hw = (H, W) with S_h % H == 0 and S_w % W == 0.  A latent pixel is scored where the mean coverage of its
+    cell reaches `threshold`: uint8, exactly, byte sum >= ceil(threshold 255 area); f32, f32 sum / area >= f32(threshold).  -> (B, H, W) uint8."""
+    from fractions import Fraction
+    require_device(cover)
+    H, W = int(hw[0]), int(hw[1])
+    if cover.dim() != 3 or cover.dtype not in (torch.uint8, torch.float32):
+        raise NopeError(f"cover {tuple(cover.shape)} {cover.dtype}: expected a (B, S_h, S_w) uint8 or float32 tensor")
+    B, Sh, Sw = cover.shape
+    if H < 1 or W < 1 or Sh % H or Sw % W:
+        raise NopeError(f"cover {tuple(cover.shape)}: its size must be a multiple of the latent size {(H, W)}")
+    threshold = float(threshold)
+    if not (0.0 <= threshold <= 1.0):
+        raise NopeError(f"threshold {threshold!r}: a coverage in [0, 1]")
+    cover = cover.contiguous()
+    area = (Sh // H) * (Sw // W)
+    min_sum = math.ceil(Fraction(threshold) * 255 * area)          # exact: Fraction(float) is the float's value
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=cover.device)
+    if B == 0:
+        return mask
+    l = lib()
+    l.check(l.dll.nope_op_pool_mask(_ptr(cover), int(cover.dtype == torch.uint8), B, Sh, Sw, H, W, int(min_sum), threshold, _ptr(mask),
+                                    _stream(cover)), "nope_op_pool_mask")
+    return mask
 
 
 MULTIREF_BAD_CAND = 4                                   # bit 2 of op_multiref_select's status: a cand entry below -1 or >= N

@@ -230,6 +230,37 @@ class PoseConditional(nn.Module):
         query_feat = self.u_net.encoder.encode_image(query, mode="mode")
         return self.retrieval_from_feat(query_feat, template_feat, shard=shard)
 
+    # ---- occlusion-robust scoring (no reference counterpart: DESIGN.md section 4.14) -----------------------------------------------------
+    def _score(self, query_feat, bank, robust, **kw):
+        """The score row of every retrieval: hip.similarity -- or, with robust = {"mask": (B,h,w) uint8|bool tensor or None, "trim": float},
+        hip.robust_similarity.  robust=None is today's call, unchanged."""
+        if robust is None:
+            return hip.similarity(query_feat, bank, **kw)
+        unknown = sorted(set(robust) - {"mask", "trim"})
+        if unknown:
+            raise TypeError(f"robust: unexpected keys {unknown} (expected 'mask' and / or 'trim')")
+        return hip.robust_similarity(query_feat, bank, robust.get("mask"), robust.get("trim", 0.0), **kw)
+
+    def _no_robust_shards(self, robust):
+        if robust is not None and self.template_parallel and ndist.world()[1] > 1:
+            raise NotImplementedError("robust scoring under template_parallel with more than one rank: sharded robust banks are not built")
+
+    @staticmethod
+    def _no_robust_multi(robust):
+        if robust is not None:
+            raise NotImplementedError("robust scoring with the multi-reference methods: the fused scoring kernel has no masked / trimmed form")
+
+    @torch.no_grad()
+    def retrieve_robust(self, query, reference, all_relativeR, mask=None, trim=0.0):
+        """generate_and_retrieve with the occlusion-robust score (hip.robust_similarity; include/nope_hip.h: nope_robust_similarity):
+        (similarity, nearest_idx, bank).  mask (B,h,w) uint8|bool at the latent size or None -- the pixels of the query that show the object
+        (hip.op_pool_mask makes it from an alpha or visibility plane) --, trim in [0, 1): the fraction of the scored pixels whose largest
+        terms are dropped per hypothesis.  The f16x2 range-check re-score is the robust score as well.  No default is tuned and no accuracy
+        is claimed: there are no trained weights."""
+        if self.similarity_metric != "l2":
+            return None
+        return self._encode_generate_retrieve(query, reference, all_relativeR, robust={"mask": mask, "trim": trim})[:3]
+
     # ---- model.py:313,323 (the two calls eval_geodesic makes back to back) --------------------------------
     @torch.no_grad()
     def generate_and_retrieve(self, query, reference, all_relativeR):
@@ -242,8 +273,9 @@ class PoseConditional(nn.Module):
             return None
         return self._encode_generate_retrieve(query, reference, all_relativeR)[:3]
 
-    def _encode_generate_retrieve(self, query, reference, all_relativeR):
+    def _encode_generate_retrieve(self, query, reference, all_relativeR, robust=None):
         """The body of generate_and_retrieve; also hands out the two embeddings (predict_pose refines on them)."""
+        self._no_robust_shards(robust)
         if self.pipeline_encoders and query.is_cuda:
             with hip.overlap_stream(query, wait_current=False) as side:
                 reference_feat = self.u_net.encoder.encode_image(reference, mode="mode")
@@ -260,28 +292,30 @@ class PoseConditional(nn.Module):
         defer = not (self.template_parallel and ndist.world()[1] > 1)
         bank = self.generate_templates_from_feat(reference_feat, all_relativeR, defer_range_check=defer)
         side.join(query_feat)
-        similarity, nearest_idx = self.retrieval_from_feat(query_feat, bank)
+        similarity, nearest_idx = self.retrieval_from_feat(query_feat, bank, robust=robust)
         # f16x2: the U-Net's activation-range check, at the END of the step -- one stream synchronisation where the results are read anyway.
         # When a layer had left its accurate window the forwards were just repeated into the same bank: score and rank again.
         if defer and self.u_net.finish_range_check():
-            similarity, nearest_idx = self.retrieval_from_feat(query_feat, bank)
+            similarity, nearest_idx = self.retrieval_from_feat(query_feat, bank, robust=robust)
         return similarity, nearest_idx, bank, query_feat, reference_feat
 
     @torch.no_grad()
-    def retrieval_topk_from_feat(self, query_feat, template_feat, k=5, shard=None):
+    def retrieval_topk_from_feat(self, query_feat, template_feat, k=5, shard=None, robust=None):
         """The top-k only -- (values (B,k), nearest_idx (B,k)) -- for callers that do not keep the full similarity: under `template_parallel` every
         rank ranks its own slice and only the (B, k) (score, global index) pairs are all-gathered and merged (north_star's "all-gather of
-        per-shard top-k"; tie rule of model.py:265 as everywhere: lowest global index).  Same indices as `retrieval_from_feat`."""
+        per-shard top-k"; tie rule of model.py:265 as everywhere: lowest global index).  Same indices as `retrieval_from_feat`.
+        robust: as retrieval_from_feat."""
+        self._no_robust_shards(robust)
         sl = (template_feat.shard if isinstance(template_feat, ndist.ShardedBank) else None) if shard is None else (shard or None)
         if not (self.template_parallel and sl is not None):
             if self.template_parallel and shard is None and ndist.world()[1] > 1:
                 raise hip.NopeError("template_parallel: this bank is a plain tensor without a shard placement: pass shard=(lo, hi, n_total) or shard=False")
-            sim = hip.similarity(query_feat, template_feat)
+            sim = self._score(query_feat, template_feat, robust)
             return hip.topk(sim, k)
         B, n_local = query_feat.shape[0], template_feat.shape[1]
         kl = min(k, n_local)
         if kl > 0:
-            vals, idx = hip.topk(hip.similarity(query_feat, template_feat), kl)
+            vals, idx = hip.topk(self._score(query_feat, template_feat, robust), kl)
             idx = idx + sl[0]
         else:
             vals = torch.empty((B, 0), dtype=torch.float32, device=query_feat.device)
@@ -289,12 +323,16 @@ class PoseConditional(nn.Module):
         return ndist.all_gather_topk_pairs(vals, idx, k)
 
     @torch.no_grad()
-    def retrieval_from_feat(self, query_feat, template_feat, k=5, shard=None):
+    def retrieval_from_feat(self, query_feat, template_feat, k=5, shard=None, robust=None):
         """`shard` = (lo, hi, N): this rank's slice [lo, hi) of the N templates; `shard=False`: the bank is COMPLETE on this rank
         (e.g. loaded from disk on every rank) and is scored locally without a collective.  Banks made by `generate_templates`
         are `nope_amd.dist.ShardedBank`s and carry their placement themselves; a bank that went through another op since (`.to()`,
         a slice, `torch.cat`, save / load) is a plain tensor again: under `template_parallel` with more than one rank that raises --
-        scoring only a local slice while the other ranks wait in the collective would return rank-local indices without an error."""
+        scoring only a local slice while the other ranks wait in the collective would return rank-local indices without an error.
+        robust (None: the reference's score, every output as without the argument): {"mask": (B,h,w) uint8|bool tensor or None, "trim":
+        float in [0, 1)} scores with hip.robust_similarity instead; the row feeds hip.topk, pose_distribution and
+        the coarse-to-fine commit unchanged.  NotImplementedError under template_parallel with more than one rank."""
+        self._no_robust_shards(robust)
         sl = (template_feat.shard if isinstance(template_feat, ndist.ShardedBank) else None) if shard is None else (shard or None)
         if self.template_parallel and sl is None and shard is None and ndist.world()[1] > 1:
             raise hip.NopeError("template_parallel: this bank is a plain tensor, not a ShardedBank with a shard placement (it was not made by generate_templates, or was "
@@ -305,13 +343,13 @@ class PoseConditional(nn.Module):
             B, n_local = query_feat.shape[0], template_feat.shape[1]
             send, _ = ndist.gather_buffers(B, sl[2], query_feat.device)
             if n_local > 0:          # this rank's columns go straight into the collective's send buffer
-                hip.similarity(query_feat, template_feat, out=send, col_offset=0)
+                self._score(query_feat, template_feat, robust, out=send, col_offset=0)
             if ndist.world()[1] > 1 and k <= sl[2]:
                 # scoring -> ONE collective -> ONE kernel (un-pad into an owned (B, N) similarity + top-k): nope_gather_topk
                 return ndist.all_gather_scores_topk(n_local, sl[2], B, query_feat.device, k)
             similarity = ndist.all_gather_scores(send[:, :n_local], sl[2])
         else:
-            similarity = hip.similarity(query_feat, template_feat)
+            similarity = self._score(query_feat, template_feat, robust)
         _, nearest_idx = hip.topk(similarity, k)
         return similarity, nearest_idx
 
@@ -405,14 +443,15 @@ class PoseConditional(nn.Module):
 
     # ---- coarse-to-fine retrieval (no reference counterpart: DESIGN.md section 4.11) ----------------------------------------------------
     @torch.no_grad()
-    def retrieve_coarse_to_fine_from_feat(self, query_feat, reference_feat, all_relativeR, template_poses, stage_of=None, **kw):
+    def retrieve_coarse_to_fine_from_feat(self, query_feat, reference_feat, all_relativeR, template_poses, stage_of=None, robust=None, **kw):
         """The retrieval in stages over a nested grid (nope_amd.search.coarse_to_fine_search, whose keyword arguments pass through): only
         the poses the search admits get a U-Net pass and a score.  Returns its C2FResult: a sparse similarity (B,N) with -inf where nothing
         was evaluated -- an ordinary input to pose_distribution and refine_from_feat -- and nearest_idx (B,k).  query_feat, reference_feat
         (B,C,h,w) f32; all_relativeR (B,N,6); template_poses (B|1,N,3,3); stage_of (N,) on the host (nope_amd.poses.grid_stages; None: the
         synthesised icosphere grid of this size, poses.grid_stages_for_size).  As with the refinement, the f16x2 range check of a stage's
         forward is not deferred: the next stage's candidates depend on its scores.  With synthetic weights the score landscape is not
-        smooth: nothing is claimed about how often the search meets the exhaustive answer on real data."""
+        smooth: nothing is claimed about how often the search meets the exhaustive answer on real data.
+        robust: as retrieval_from_feat -- every stage is scored with hip.robust_similarity, the same bits the exhaustive robust row holds."""
         from .search import coarse_to_fine_search
         if self.similarity_metric != "l2":
             return None
@@ -426,13 +465,13 @@ class PoseConditional(nn.Module):
 
         def evaluate(rows, cand):
             maps = torch.empty((rows.shape[0], rows.shape[1], C, h, w), dtype=torch.float32, device=rows.device)
-            return hip.similarity(query_feat, self._forward_poses(reference_feat, rows, maps))
+            return self._score(query_feat, self._forward_poses(reference_feat, rows, maps), robust)
         return coarse_to_fine_search(evaluate, all_relativeR, template_poses, stage_of, **kw)
 
     @torch.no_grad()
-    def retrieve_coarse_to_fine(self, query, reference, all_relativeR, template_poses, stage_of=None, **kw):
+    def retrieve_coarse_to_fine(self, query, reference, all_relativeR, template_poses, stage_of=None, robust=None, **kw):
         """Encode both images, then retrieve_coarse_to_fine_from_feat (same keyword arguments)."""
-        return self._encode_retrieve_coarse_to_fine(query, reference, all_relativeR, template_poses, stage_of, **kw)[0]
+        return self._encode_retrieve_coarse_to_fine(query, reference, all_relativeR, template_poses, stage_of, robust=robust, **kw)[0]
 
     def _encode_retrieve_coarse_to_fine(self, query, reference, all_relativeR, template_poses, stage_of=None, **kw):
         enc = self.u_net.encoder
@@ -459,7 +498,7 @@ class PoseConditional(nn.Module):
 
     @torch.no_grad()
     def retrieve_multi_from_feat(self, query_feat, reference_feats, ref_poses, template_poses, n_refs=None, fusion="feature", weighting="softmax",
-                                 tau_deg=30.0, dist_kind=hip.C2F_ROTATION, k=5, return_per_reference=False, max_refs=None):
+                                 tau_deg=30.0, dist_kind=hip.C2F_ROTATION, k=5, return_per_reference=False, max_refs=None, robust=None):
         """Retrieval from R posed reference views per sample (include/nope_hip.h: nope_op_multiref_prepare, nope_multiref_similarity,
         nope_op_multiref_fuse_scores).  query_feat (B,C,h,w); reference_feats (B,R,C,h,w); ref_poses (B,R,3,3), the references' object-to-camera
         rotations in the frame of the grid; template_poses (B|1,N,3,3); n_refs (B,) or None: references r >= n_refs[b] are padding.
@@ -472,6 +511,7 @@ class PoseConditional(nn.Module):
         max_refs nearest references only (nope_op_multiref_select), B M N hypotheses whatever R is, and the weights -- softmax over the
         kept references -- , per_reference and the bank carry M slots in place of the R references.  M = 1 is
         "nearest" at the cost of one reference: its row is nope_similarity's, which reads no weights."""
+        self._no_robust_multi(robust)
         if self.similarity_metric != "l2":
             return None
         self._no_multi_ref_shards()
@@ -540,12 +580,13 @@ class PoseConditional(nn.Module):
     @torch.no_grad()
     def retrieve_multi_coarse_to_fine_from_feat(self, query_feat, reference_feats, ref_poses, template_poses, n_refs=None, max_refs=1,
                                                 fusion="feature", weighting="softmax", tau_deg=30.0, ref_dist_kind=hip.C2F_ROTATION,
-                                                stage_of=None, **kw):
+                                                stage_of=None, robust=None, **kw):
         """retrieve_coarse_to_fine_from_feat from R posed references: every pose the search admits is generated from its max_refs nearest
         references and scored as retrieve_multi_from_feat(max_refs=...) scores it.  ref_dist_kind is the distance between grid pose and
         reference pose (retrieve_multi_from_feat's dist_kind); the search's own keyword arguments -- its dist_kind between grid poses among
         them -- pass through.  Returns the search's C2FResult."""
         from .search import coarse_to_fine_search
+        self._no_robust_multi(robust)
         if self.similarity_metric != "l2":
             return None
         self._no_multi_ref_shards()
@@ -623,13 +664,15 @@ class PoseConditional(nn.Module):
 
     @torch.no_grad()
     def predict_pose_multi(self, query, references, reference_poses, template_poses, distinct_deg=None, symmetry=None, temperature=1.0,
-                           max_refs=None, coarse_to_fine=None, refine_iters=0, **kw):
+                           max_refs=None, coarse_to_fine=None, refine_iters=0, robust=None, **kw):
         """predict_pose from R posed references: (pred_R (B,k,3,3) f64, score (B,k) f32) = template_poses[nearest_idx] and the fused scores of
         retrieve_multi (whose keyword arguments pass through); pred_R[:, 0] is the answer.  distinct_deg (None: the plain top-k): the k
         candidates are the seeds of the distinct modes of the fused row within that radius under `symmetry` (op_pose_modes with fill, as
         predict_pose).  max_refs (None: all R references per pose): retrieve_multi_from_feat's.  coarse_to_fine (None: the exhaustive
         retrieval; True, or a dict of the search's keyword arguments): retrieve_multi_coarse_to_fine_from_feat with max_refs (None: 1).
-        refine_iters above 0: the candidates refined by refine_multi_from_feat (fd_step, max_step_deg, damping pass to it), in ITS order."""
+        refine_iters above 0: the candidates refined by refine_multi_from_feat (fd_step, max_step_deg, damping pass to it), in ITS order.
+        robust: NotImplementedError unless None, as on every multi-reference method."""
+        self._no_robust_multi(robust)
         if self.similarity_metric != "l2":
             return None
         self._no_multi_ref_shards()
@@ -659,7 +702,7 @@ class PoseConditional(nn.Module):
 
     @torch.no_grad()
     def predict_pose(self, query, reference, all_relativeR, template_poses, refine_iters=0, distinct_deg=None, symmetry=None, temperature=1.0,
-                     coarse_to_fine=None, **kw):
+                     coarse_to_fine=None, robust=None, **kw):
         """(pred_R (B,k,3,3) f64, score (B,k) f32): the k best poses of the query.  refine_iters = 0: template_poses[nearest_idx]
         (model.py:352-354) and the retrieval scores; above 0: those candidates refined below the grid spacing (refine_from_feat, whose
         keyword arguments pass through), in ITS order.  template_poses (B|1,N,3,3).  None for a metric the reference does not implement.
@@ -667,15 +710,22 @@ class PoseConditional(nn.Module):
         modes within that radius under `symmetry` (op_pose_modes with fill: always k valid candidates), not a vertex and its neighbours.
         coarse_to_fine (None: the exhaustive retrieval, every output as without the argument; True, or a dict of
         retrieve_coarse_to_fine_from_feat's keyword arguments): the scores come from the search in stages over the nested grid instead --
-        a sparse row, -inf where nothing was evaluated, on which distinct_deg and refine_iters work unchanged."""
+        a sparse row, -inf where nothing was evaluated, on which distinct_deg and refine_iters work unchanged.
+        robust (None: every output as without the argument): as retrieval_from_feat; the exhaustive row or every stage of the search is
+        the robust score.  With refine_iters > 0 it raises NotImplementedError: the refinement's cost and its accept / revert are defined
+        on the plain metric."""
+        if robust is not None and refine_iters > 0:
+            raise NotImplementedError("robust scoring with refine_iters > 0: the refinement's cost and its accept / revert are defined on the plain metric")
         if self.similarity_metric != "l2":
             return None
         if coarse_to_fine is not None and coarse_to_fine is not False:
-            c2f, query_feat, reference_feat = self._encode_retrieve_coarse_to_fine(query, reference, all_relativeR, template_poses,
-                                                                                   **({} if coarse_to_fine is True else dict(coarse_to_fine)))
+            c2f_kw = {} if coarse_to_fine is True else dict(coarse_to_fine)
+            if robust is not None:
+                c2f_kw["robust"] = robust
+            c2f, query_feat, reference_feat = self._encode_retrieve_coarse_to_fine(query, reference, all_relativeR, template_poses, **c2f_kw)
             similarity, nearest_idx = c2f.similarity, c2f.nearest_idx
         else:
-            similarity, nearest_idx, _, query_feat, reference_feat = self._encode_generate_retrieve(query, reference, all_relativeR)
+            similarity, nearest_idx, _, query_feat, reference_feat = self._encode_generate_retrieve(query, reference, all_relativeR, robust=robust)
         if distinct_deg is not None:
             nearest_idx = hip.op_pose_modes(similarity, template_poses, symmetry, temperature=temperature, radius_deg=distinct_deg,
                                             max_modes=nearest_idx.shape[1], fill=True, want_prob=False).idx
