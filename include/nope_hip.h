@@ -96,9 +96,10 @@ typedef void* nope_stream_t;
  * 20: nope_op_c2f_expand, nope_op_c2f_commit;
  * 21: nope_op_multiref_prepare, nope_multiref_similarity, nope_op_multiref_fuse_scores;
  * 22: nope_op_multiref_select, nope_op_multiref_gather;
- * 23: nope_robust_similarity, nope_op_residual_maps, nope_op_pool_mask.  Callers compare nope_abi_version() against the
+ * 23: nope_robust_similarity, nope_op_residual_maps, nope_op_pool_mask;
+ * 24: nope_op_pose_errors, nope_op_mesh_diameter and their _workspace_bytes, NOPE_POSE_ERR_*.  Callers compare nope_abi_version() against the
  * header they were built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 23
+#define NOPE_ABI_VERSION 24
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -439,6 +440,55 @@ size_t nope_op_vsd_workspace_bytes(int B, int k, int H, int W);
 int nope_op_vsd(const float* depth_test, const float* depth_gt, const float* depth_est, const double* K, int B, int k, int H, int W,
                 double delta, double tau, int cost_type, int visib_mode, double* err, void* workspace, size_t workspace_bytes,
                 nope_stream_t stream);
+
+/* (ABI 24) The BOP pose errors besides VSD: MSSD, MSPD, ADD and ADI (ADD-S) of P pose pairs.  No reference
+ * counterpart: the reference reads models_info.json (dataloader/baseBOP.py:284) but evaluates VSD alone.  The definitions are those of
+ * the BOP toolkit (pose_error.py: mssd, mspd, add, adi), restated here; they are the contract.
+ *   verts     (V, 3) f32, all meshes concatenated (mm), as nope_op_render_depth takes them
+ *   vert_off, vert_cnt  (P) int32 on the device: pose p reads the vertices x_i, i < V_p = vert_cnt[p], at vert_off[p] + i;
+ *             max_verts (host) >= every vert_cnt[p]
+ *   syms      (S_total, 4, 4) f64 row-major rigid transforms (R_s | t_s), the symmetry sets of all objects concatenated
+ *   sym_off, sym_cnt    (P) int32 on the device: pose p uses the symmetries s < S_p = sym_cnt[p] at sym_off[p] + s (the identity is entry 0 of
+ *             every set nope_amd.bop builds; the kernels do not rely on it);  max_syms (host) >= every sym_cnt[p]
+ *   pose_est, pose_gt   (P, 4, 4) f64 object-to-camera (Re | te), (Rg | tg): OpenCV axes, mm;  K (P, 3, 3) f64
+ *   mssd, mspd, add, adi  (P) f64 each, or NULL: a NULL output's metric is not computed (ADI is the expensive one)
+ *   status    (P) int32: 0 or a sum of NOPE_POSE_ERR_* bits
+ * With Xe_i = Re x_i + te and Xg_i^s = Rg (R_s x_i + t_s) + tg:
+ *   ADD  = (1 / V_p) sum_i |Xe_i - (Rg x_i + tg)|
+ *   ADI  = (1 / V_p) sum_i min_j |Xe_i - (Rg x_j + tg)|, searched in the ground truth's object frame: y_i = Rg^T (Xe_i - tg),
+ *          min_j |y_i - x_j|  (Rg is taken to be a rotation)
+ *   MSSD = min_s max_i |Xe_i - Xg_i^s|                                        (mm)
+ *   MSPD = min_s max_i |pi(Xe_i) - pi(Xg_i^s)|, pi(X) = (K X)_{0,1} / (K X)_2 with the whole K, as the toolkit's project_pts    (pixels)
+ * Arithmetic: f64 on the f32-stored vertices, no contraction, every 3-term dot product summed left to right; min / max are taken on
+ * squared distances and sqrt once (sqrt is monotone and correctly rounded: the same bits).  The means are summed in a fixed order (per lane,
+ * butterfly, waves, then blocks of NOPE_POSE_ERR_POINT_BLOCK vertices in order); no floating-point atomics: the same bits on every run.
+ * Edge rules:
+ *   a NaN or inf anywhere in pose_est[p], pose_gt[p] or K[p]: all outputs of p are NaN, NOPE_POSE_ERR_NONFINITE.  The maxima and minima keep
+ *     a NaN of any operand (a NaN vertex gives NaN, not the maximum of the others)
+ *   a vertex with (K X)_2 <= 0 under the estimate or under any symmetric ground truth: mspd[p] is NaN, NOPE_POSE_ERR_BEHIND; mssd, add,
+ *     adi are unaffected
+ *   vert_cnt[p] <= 0, > max_verts, or a range outside [0, V): all outputs of p are NaN, NOPE_POSE_ERR_VERT_RANGE; nothing is read
+ *   sym_cnt[p] <= 0, > max_syms, or a range outside [0, S_total): the same with NOPE_POSE_ERR_SYM_RANGE
+ *   all four outputs NULL, a missing input pointer, V, S_total, P, max_verts or max_syms < 1, P > 65535: NOPE_ERR_ARG; a short workspace:
+ *     NOPE_ERR_WORKSPACE; both before anything is launched or written
+ * workspace: nope_op_pose_errors_workspace_bytes(P, max_verts, max_syms) bytes. */
+enum { NOPE_POSE_ERR_NONFINITE = 1, NOPE_POSE_ERR_BEHIND = 2, NOPE_POSE_ERR_VERT_RANGE = 4, NOPE_POSE_ERR_SYM_RANGE = 8 };
+/* the sizes at which the kernels take another path (tests name their shapes from these) */
+enum { NOPE_POSE_ERR_POINT_BLOCK = 512, /* vertices whose ADD / ADI terms one workgroup owns */
+       NOPE_POSE_ERR_TILE = 1024,       /* vertices per LDS tile of the ADI / diameter search */
+       NOPE_POSE_ERR_SYM_CHUNK = 8      /* symmetries one workgroup walks */ };
+size_t nope_op_pose_errors_workspace_bytes(int P, int max_verts, int max_syms);
+int nope_op_pose_errors(const float* verts, int V, const int* vert_off, const int* vert_cnt, int max_verts, const double* syms, int S_total,
+                        const int* sym_off, const int* sym_cnt, int max_syms, const double* pose_est, const double* pose_gt, const double* K,
+                        int P, double* mssd, double* mspd, double* add, double* adi, int* status, void* workspace, size_t workspace_bytes,
+                        nope_stream_t stream);
+
+/* (ABI 24) Diameter of n_obj objects: diameter[o] = max_{i,j} |x_i - x_j| over the vertex range of object o, f64 on the f32 vertices, the
+ * ADI tiling with a maximum over the block pairs i <= j; bit-identical from run to run.  An empty or bad range gives NaN (nothing is read),
+ * a NaN vertex gives NaN.  n_obj <= 65535.  workspace: nope_op_mesh_diameter_workspace_bytes(n_obj, max_verts) bytes. */
+size_t nope_op_mesh_diameter_workspace_bytes(int n_obj, int max_verts);
+int nope_op_mesh_diameter(const float* verts, int V, const int* vert_off, const int* vert_cnt, int n_obj, int max_verts, double* diameter,
+                          void* workspace, size_t workspace_bytes, nope_stream_t stream);
 
 /* (ABI 12) Visualisation pictures: the contact sheets PoseConditional saves as PNGs and the `vis_imgs` grid of its predictions file.
  * A picture is n_cols (1 .. NOPE_VIS_MAX_COLS) columns; a column is one stack of f32 NCHW images, read where it lies -- nothing is copied

@@ -240,6 +240,23 @@ int nope_op_vsd(const float* depth_test, const float* depth_gt, const float* dep
                       (hipStream_t)stream);
 }
 
+size_t nope_op_pose_errors_workspace_bytes(int P, int max_verts, int max_syms) { return pose_errors_workspace_bytes(P, max_verts, max_syms); }
+
+int nope_op_pose_errors(const float* verts, int V, const int* vert_off, const int* vert_cnt, int max_verts, const double* syms, int S_total,
+                        const int* sym_off, const int* sym_cnt, int max_syms, const double* pose_est, const double* pose_gt, const double* K,
+                        int P, double* mssd, double* mspd, double* add, double* adi, int* status, void* workspace, size_t workspace_bytes,
+                        nope_stream_t stream) {
+    return launch_pose_errors(verts, V, vert_off, vert_cnt, max_verts, syms, S_total, sym_off, sym_cnt, max_syms, pose_est, pose_gt, K, P, mssd,
+                              mspd, add, adi, status, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t nope_op_mesh_diameter_workspace_bytes(int n_obj, int max_verts) { return mesh_diameter_workspace_bytes(n_obj, max_verts); }
+
+int nope_op_mesh_diameter(const float* verts, int V, const int* vert_off, const int* vert_cnt, int n_obj, int max_verts, double* diameter,
+                          void* workspace, size_t workspace_bytes, nope_stream_t stream) {
+    return launch_mesh_diameter(verts, V, vert_off, vert_cnt, n_obj, max_verts, diameter, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int nope_op_vis_grid(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, void* grid_f16, nope_stream_t stream) {
     return launch_vis_grid(cols, n_cols, B, F, H, W, static_cast<f16_t*>(grid_f16), (hipStream_t)stream);
 }

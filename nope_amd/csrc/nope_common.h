@@ -615,6 +615,14 @@ int launch_render_depth(const float* verts, int V, const int* faces, int F, cons
 size_t vsd_workspace_bytes(int B, int k, int H, int W);
 int launch_vsd(const float* dtest, const float* dgt, const float* dest, const double* K, int B, int k, int H, int W, double delta, double tau,
                int cost_type, int visib_mode, double* err, void* ws, size_t ws_bytes, hipStream_t s);
+// BOP pose errors (kernels_poseerr.hip)
+size_t pose_errors_workspace_bytes(int P, int max_verts, int max_syms);
+int launch_pose_errors(const float* verts, int V, const int* vert_off, const int* vert_cnt, int max_verts, const double* syms, int S_total,
+                       const int* sym_off, const int* sym_cnt, int max_syms, const double* pose_est, const double* pose_gt, const double* K, int P,
+                       double* mssd, double* mspd, double* add, double* adi, int* status, void* ws, size_t ws_bytes, hipStream_t s);
+size_t mesh_diameter_workspace_bytes(int n_obj, int max_verts);
+int launch_mesh_diameter(const float* verts, int V, const int* vert_off, const int* vert_cnt, int n_obj, int max_verts, double* diameter, void* ws,
+                         size_t ws_bytes, hipStream_t s);
 int launch_vis_grid(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, f16_t* grid, hipStream_t s);
 int launch_vis_sheet(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, int tile, int nrow, int padding,
                      unsigned char* sheet, hipStream_t s);

@@ -14,7 +14,8 @@ Differences in *schedule*, none in arithmetic:
 Lightning-specific members (optimizers, wandb logging) are out of scope and are not provided; the visualisation outputs
 (PNG contact sheets, video, `vis_imgs`) are written by nope_amd/vis.py.
 The evaluation entry points -- `eval_geodesic`, `eval_vsd` (T-LESS, on the device: nope_amd/vsd.py), `load_mesh`,
-`validation_step`, `test_step` -- return their scores instead of logging them.
+`validation_step`, `test_step` -- return their scores instead of logging them; `eval_bop` / `load_models_info` (the BOP benchmark's other
+errors, nope_amd/bop.py; no reference counterpart) do the same.
 """
 from __future__ import annotations
 
@@ -777,6 +778,75 @@ class PoseConditional(nn.Module):
         scores.update(vsd.vsd_scores(err))
         if save_path is not None:
             np.save(save_path, err[:, 0].cpu().numpy())
+        return scores
+
+    def load_models_info(self, cad_dir_or_file, max_sym_disc_step=0.01):
+        """models_info.json of a BOP models directory (or the file itself): the objects' diameters and symmetry sets for eval_bop
+        (nope_amd.bop.load_models_info, SymmetryBank.from_models_info).  No reference counterpart: the reference reads the file
+        (dataloader/baseBOP.py:284) and does not use it."""
+        from . import bop
+        self.tless_models_info = bop.load_models_info(cad_dir_or_file)
+        self.tless_symmetries = bop.SymmetryBank.from_models_info(self.tless_models_info, device=next(self.parameters()).device,
+                                                                  max_sym_disc_step=max_sym_disc_step)
+        return self.tless_models_info
+
+    @torch.no_grad()
+    def eval_bop(self, batch, data_name, save_path=None):
+        """The T-LESS evaluation under the BOP benchmark's errors: eval_vsd's batch, forward pass and retrieval, then MSSD, MSPD, ADD and
+        ADI of the retrieved rotations (nope_amd.bop.pose_errors, ground-truth translation) and VSD over tau in 0.05 ... 0.50 times the
+        diameter (delta 15, step cost, bop19) from ONE rendering.  Returns {f"loss/val_{data_name}", and nope_amd.bop.bop_scores' recalls:
+        AR_MSSD, AR_MSPD, AR_VSD, AR, ADD / ADD-S at 0.1 d, for the top 1 / 3 / 5}.  Symmetries and diameters come from load_models_info;
+        without it the symmetry sets are the identity and the diameters are measured on the meshes (bop.mesh_diameters).  save_path:
+        np.savez of the error tables.  No reference counterpart (eval_vsd is the reference's evaluation); nothing is claimed about
+        accuracy on real data."""
+        import numpy as np
+        from . import bop, vsd
+        if getattr(self, "tless_cad", None) is None:
+            raise RuntimeError("eval_bop: no meshes: call load_mesh(cad_dir) first (model.py:378)")
+        query, reference = batch["query"], batch["reference"]
+        loss = self.forward(query=query, relativeR=batch["gt_relativeR"], reference=reference)
+        pred_feat, _, _ = self.generate_templates(reference=reference, all_relativeR=batch["all_relativeR"])
+        out = self.retrieval(query=query, template_feat=pred_feat)
+        if out is None:
+            raise NotImplementedError(f"eval_bop: similarity_metric {self.similarity_metric!r} (the reference implements 'l2' only)")
+        _, nearest_idx = out
+        B = query.shape[0]
+        template_poses = batch["template_poses"]
+        rows = torch.arange(B, device=template_poses.device)[:, None].expand(-1, nearest_idx.shape[1])
+        retrieved_R = template_poses[rows, nearest_idx.to(template_poses.device)]
+        if "depth" in batch:
+            depth_test = batch["depth"]
+        else:
+            depth_test = np.stack([vsd.load_depth(p) for p in batch["depth_path"]])
+        obj_ids = [int(o) for o in (batch["obj_id"].tolist() if hasattr(batch["obj_id"], "tolist") else batch["obj_id"])]
+        info = getattr(self, "tless_models_info", None)
+        if info is not None and all(o in info and "diameter" in info[o] for o in obj_ids):
+            diam = np.array([float(info[o]["diameter"]) for o in obj_ids])
+        else:
+            if getattr(self, "_tless_diameters", None) is None or self._tless_diameters[0] is not self.tless_cad:
+                self._tless_diameters = (self.tless_cad, bop.mesh_diameters(self.tless_cad))
+            diam = np.array([self._tless_diameters[1][o] for o in obj_ids])
+        errors = bop.pose_errors(self.tless_cad, getattr(self, "tless_symmetries", None), obj_ids, retrieved_R, batch["query_pose"],
+                                 batch["query_translation"], batch["intrinsic"])
+        _, d_gt, d_est = vsd.vsd_error(depth_test, self.tless_cad, obj_ids, retrieved_R, batch["query_pose"], batch["query_translation"],
+                                       batch["intrinsic"], return_depth=True)
+        dev = d_est.device
+        dtest = (depth_test if isinstance(depth_test, torch.Tensor) else torch.from_numpy(np.asarray(depth_test))).to(dev)
+        # tau differs per query (a fraction of its object's diameter): queries of one diameter share a launch
+        vsd_stack = torch.empty((len(bop.THRESHOLDS),) + tuple(d_est.shape[:2]), dtype=torch.float64, device=dev)
+        Kt = vsd._as_f64(batch["intrinsic"], dev)
+        if Kt.dim() == 2:
+            Kt = Kt.reshape(1, 3, 3).expand(B, 3, 3)
+        for d in sorted(set(diam.tolist())):
+            sel = torch.from_numpy(np.nonzero(diam == d)[0]).to(dev)
+            for ti, frac in enumerate(bop.THRESHOLDS):
+                vsd_stack[ti, sel] = vsd.vsd_from_depth(dtest[sel], d_gt[sel].contiguous(), d_est[sel].contiguous(), Kt[sel].contiguous(),
+                                                        delta=15, tau=frac * d)
+        width = depth_test.shape[-1]
+        scores = {f"loss/val_{data_name}": float(loss)}
+        scores.update(bop.bop_scores(errors, diam, width, vsd_errors=vsd_stack))
+        if save_path is not None:
+            np.savez(save_path, vsd=vsd_stack.cpu().numpy(), diameter=diam, **{m: errors[m].cpu().numpy() for m in bop.METRICS})
         return scores
 
     @torch.no_grad()

@@ -140,12 +140,14 @@ def load_depth(path: str, scale: float = 0.1) -> np.ndarray:
 # ---- meshes on the device -------------------------------------------------------------------------------------------------------------
 class MeshBank:
     """Meshes concatenated into one device vertex buffer (V,3) f32 and one face buffer (F,3) int32 (global vertex indices), with each
-    object's face range: one rasteriser launch serves a batch of mixed objects."""
+    object's face range and vertex range: one rasteriser launch (or one pose-error launch, nope_amd/bop.py) serves a batch of mixed
+    objects."""
 
     def __init__(self, meshes: Dict[int, tuple], device="cuda"):
         if not meshes:
             raise ValueError("MeshBank needs at least one mesh")
         vs, fs, self.face_off, self.face_cnt = [], [], {}, {}
+        self.vert_off, self.vert_cnt = {}, {}
         nv = nf = 0
         for oid in sorted(meshes):
             v, f = meshes[oid]
@@ -156,6 +158,7 @@ class MeshBank:
             vs.append(v)
             fs.append(f + nv)
             self.face_off[int(oid)], self.face_cnt[int(oid)] = nf, len(f)
+            self.vert_off[int(oid)], self.vert_cnt[int(oid)] = nv, len(v)
             nv += len(v)
             nf += len(f)
         if nv == 0 or nf == 0 or nv >= 2 ** 31 or nf >= 2 ** 31:
@@ -171,6 +174,12 @@ class MeshBank:
     def ranges(self, obj_ids: Iterable[int]):
         try:
             return [(self.face_off[int(o)], self.face_cnt[int(o)]) for o in obj_ids]
+        except KeyError as e:
+            raise KeyError(f"obj_id {e.args[0]} is not in the mesh bank (loaded: {self.obj_ids})") from None
+
+    def vert_ranges(self, obj_ids: Iterable[int]):
+        try:
+            return [(self.vert_off[int(o)], self.vert_cnt[int(o)]) for o in obj_ids]
         except KeyError as e:
             raise KeyError(f"obj_id {e.args[0]} is not in the mesh bank (loaded: {self.obj_ids})") from None
 
