@@ -97,9 +97,10 @@ typedef void* nope_stream_t;
  * 21: nope_op_multiref_prepare, nope_multiref_similarity, nope_op_multiref_fuse_scores;
  * 22: nope_op_multiref_select, nope_op_multiref_gather;
  * 23: nope_robust_similarity, nope_op_residual_maps, nope_op_pool_mask;
- * 24: nope_op_pose_errors, nope_op_mesh_diameter and their _workspace_bytes, NOPE_POSE_ERR_*.  Callers compare nope_abi_version() against the
- * header they were built with before passing any struct (nope_amd/hip.py does at load time). */
-#define NOPE_ABI_VERSION 24
+ * 24: nope_op_pose_errors, nope_op_mesh_diameter and their _workspace_bytes, NOPE_POSE_ERR_*;
+ * 25: nope_op_fit_translation, nope_op_mask_boxes, nope_op_depth_shift and its _workspace_bytes, NOPE_FIT_*.  Callers compare
+ * nope_abi_version() against the header they were built with before passing any struct (nope_amd/hip.py does at load time). */
+#define NOPE_ABI_VERSION 25
 const char* nope_strerror(int code);
 int nope_abi_version(void);
 /* The library reads its tuning / test switches (NOPE_* environment variables: launch policies, A/B switches, traces) once per call site and
@@ -489,6 +490,63 @@ int nope_op_pose_errors(const float* verts, int V, const int* vert_off, const in
 size_t nope_op_mesh_diameter_workspace_bytes(int n_obj, int max_verts);
 int nope_op_mesh_diameter(const float* verts, int V, const int* vert_off, const int* vert_cnt, int n_obj, int max_verts, double* diameter,
                           void* workspace, size_t workspace_bytes, nope_stream_t stream);
+
+/* (ABI 25) Translation of P poses from a rotation, the model and a 2D box: the t under which the projected box of the model's vertices is
+ * the given one.  No reference counterpart: the reference predicts no translation (src/poses/vsd.py:84-87 takes the
+ * ground truth's).
+ *   verts, V, vert_off, vert_cnt, max_verts   as nope_op_pose_errors takes them: pose p reads x_i, i < V_p
+ *   R         (P, 3, 3) f64 row-major;  K (P, 3, 3) f64: fx = K[0], cx = K[2], fy = K[4], cy = K[5] are read, as nope_op_render_depth reads them
+ *   box       (P, 4) f64 (u0, v0, u1, v1) in pixels, the rasteriser's image coordinates: image point u falls in pixel floor(u)
+ *   max_iters >= 0;  tol_scale, tol_px >= 0
+ *   t (P, 3) f64, residual (P) f64 (pixels), iters (P) int32, status (P) int32: 0 or a sum of NOPE_FIT_* bits
+ * The contract is this sequence of f64 operations on the f32-stored vertices, without contraction, every 3-term product summed left to
+ * right; min / max run over the V_p vertices and keep a NaN of any operand:
+ *   y_i = R x_i = ((R[3r] x + R[3r+1] y) + R[3r+2] z)_r;   bw = u1 - u0, bh = v1 - v0, cu = 0.5 (u0 + u1), cv = 0.5 (v0 + v1)
+ *   ax0 / ax1 = min / max y_i.x,  ay0 / ay1 = min / max y_i.y
+ *   z = 0.5 ((fx (ax1 - ax0)) / bw + (fy (ay1 - ay0)) / bh)
+ *   t = (((cu - cx) / fx) z - 0.5 (ax0 + ax1), ((cv - cy) / fy) z - 0.5 (ay0 + ay1), z);  n = 0
+ *   loop:
+ *     Z_i = y_i.z + t_z;  if not (min Z_i > 0): NOPE_FIT_BEHIND, t and residual NaN, iters = n, stop
+ *     u_i = fx ((y_i.x + t_x) / Z_i) + cx,  v_i = fy ((y_i.y + t_y) / Z_i) + cy;  pu0 / pu1 = min / max u_i,  pv0 / pv1 = min / max v_i
+ *     s = 0.5 ((pu1 - pu0) / bw + (pv1 - pv0) / bh);  du = cu - 0.5 (pu0 + pu1);  dv = cv - 0.5 (pv0 + pv1)
+ *     residual = max(max(max(|pu0 - u0|, |pu1 - u1|), |pv0 - v0|), |pv1 - v1|)
+ *     if |s - 1| <= tol_scale and |du| <= tol_px and |dv| <= tol_px: iters = n, stop (status 0)
+ *     if n == max_iters: NOPE_FIT_NOT_CONVERGED, t and residual as they stand, iters = n, stop
+ *     z' = t_z s;  t = (t_x s + (du z') / fx, t_y s + (dv z') / fy, z');  n = n + 1
+ * max_iters = 0 returns the initial guess and its residual.  Minima and maxima do not depend on the order they are taken in and nothing is
+ * summed over the vertices: the same bits on every run and from any reduction tree (the one freedom is the sign of an extreme that is
+ * zero, which reaches an output only where both extremes of an axis are zero).  One workgroup of NOPE_FIT_THREADS lanes per pose; the
+ * vertices are read and rotated again in every pass.
+ * Edge rules:
+ *   a NaN or inf in R[p], K[p] or box[p]: t, residual NaN, iters 0, NOPE_FIT_NONFINITE
+ *   a finite box with not (bw > 0) or not (bh > 0): the same with NOPE_FIT_BAD_BOX
+ *   vert_cnt[p] <= 0, > max_verts, or a range outside [0, V): the same with NOPE_FIT_VERT_RANGE; nothing is read
+ *   a NaN vertex: it stays in the extremes, z and Z_i are NaN, so the first pass stops at its test with NaN outputs (and NOPE_FIT_BEHIND)
+ *   a missing pointer, V, P or max_verts < 1, max_iters < 0, a negative or NaN tolerance: NOPE_ERR_ARG before anything is launched or written */
+enum { NOPE_FIT_NONFINITE = 1, NOPE_FIT_BAD_BOX = 2, NOPE_FIT_VERT_RANGE = 4, NOPE_FIT_BEHIND = 8, NOPE_FIT_NOT_CONVERGED = 16 };
+enum { NOPE_FIT_THREADS = 256 /* lanes per pose: vertex i is lane i mod NOPE_FIT_THREADS's (tests name their shapes from it) */ };
+int nope_op_fit_translation(const float* verts, int V, const int* vert_off, const int* vert_cnt, int max_verts, const double* R, const double* K,
+                            const double* box, int P, int max_iters, double tol_scale, double tol_px, double* t, double* residual, int* iters,
+                            int* status, nope_stream_t stream);
+
+/* (ABI 25) Boxes of B masks, in the coordinates nope_op_fit_translation takes: with xmin .. xmax, ymin .. ymax the extreme non-zero pixels of
+ * mask[b], box[b] = (xmin, ymin, xmax + 1, ymax + 1) and count[b] the number of non-zero pixels; an empty mask: a NaN box and count 0.
+ *   mask (B, H, W) uint8;  box (B, 4) f64;  count (B) int32.  Integer min / max and an integer count, one workgroup per image.
+ * A missing pointer, B, H or W < 1, H W > 2^30: NOPE_ERR_ARG. */
+int nope_op_mask_boxes(const unsigned char* mask, int B, int H, int W, double* box, int* count, nope_stream_t stream);
+
+/* (ABI 25) Mean depth difference between a test image and k rendered estimates over their inliers: the correction of an estimate's distance.
+ *   depth_test (B, H, W) f32, depth_est (B, k, H, W) f32 in mm (0 = no depth), mask (B, H, W) uint8 or NULL;  tau >= 0 (mm);  1 <= k <= 16
+ *   a pixel is an inlier of estimate j when test > 0, est > 0, mask != 0 (if given) and |f64(test) - f64(est)| <= tau; a NaN compares false
+ *   count (B, k) int32 inliers;  shift (B, k) f64 = (sum over the inliers of f64(test) - f64(est)) / count, NaN where count = 0
+ * The sum's order is fixed: with nblk = the workgroups per image (a function of H W alone), lane l of workgroup w adds pixels
+ * (w + j nblk) 256 + l, j = 0, 1, ..., in that order; then the butterfly over the wave (xor 32, 16, ..., 1), the four waves left to right,
+ * the workgroups in order.  No floating-point atomics: the same bits on every run.
+ * A missing pointer, B, H or W < 1, B > 65535, H W > 2^30, k outside 1 .. 16, a negative or NaN tau: NOPE_ERR_ARG; a short workspace:
+ * NOPE_ERR_WORKSPACE; both before anything is launched or written.  workspace: nope_op_depth_shift_workspace_bytes(B, k, H, W) bytes. */
+size_t nope_op_depth_shift_workspace_bytes(int B, int k, int H, int W);
+int nope_op_depth_shift(const float* depth_test, const float* depth_est, const unsigned char* mask, int B, int k, int H, int W, double tau,
+                        double* shift, int* count, void* workspace, size_t workspace_bytes, nope_stream_t stream);
 
 /* (ABI 12) Visualisation pictures: the contact sheets PoseConditional saves as PNGs and the `vis_imgs` grid of its predictions file.
  * A picture is n_cols (1 .. NOPE_VIS_MAX_COLS) columns; a column is one stack of f32 NCHW images, read where it lies -- nothing is copied

@@ -5,6 +5,10 @@ eval_calc_scores), restated in include/nope_hip.h and DESIGN.md section 4.15 bec
 
 The errors are HIP kernels (nope_op_pose_errors, nope_op_mesh_diameter: csrc/kernels_poseerr.hip); symmetry sets and score tables are
 small host arithmetic in numpy.
+
+A translation of the library's own (estimate_translation, refine_translation_depth): from the retrieved rotation, the mesh and the detected 2D
+box, corrected along the viewing ray from a depth image (nope_op_fit_translation, nope_op_mask_boxes, nope_op_depth_shift:
+csrc/kernels_posefit.hip).  It is what pose_errors(pred_t=...) and vsd.vsd_error(pred_t=...) are given.
 """
 from __future__ import annotations
 
@@ -22,6 +26,11 @@ from .vsd import MeshBank, _as_f64, compose_poses
 # NOPE_POSE_ERR_* (include/nope_hip.h)
 ST_NONFINITE, ST_BEHIND, ST_VERT_RANGE, ST_SYM_RANGE = 1, 2, 4, 8
 POINT_BLOCK, TILE, SYM_CHUNK = 512, 1024, 8
+# NOPE_FIT_* (include/nope_hip.h): status bits of op_fit_translation, and the lanes of one pose's workgroup
+FIT_NONFINITE, FIT_BAD_BOX, FIT_VERT_RANGE, FIT_BEHIND, FIT_NOT_CONVERGED = 1, 2, 4, 8, 16
+FIT_THREADS = 256
+# status bits of refine_translation_depth (host arithmetic; above the NOPE_FIT_* bits, so that one status word can carry both stages)
+ST_DEPTH_FEW, ST_DEPTH_POSE = 256, 512
 METRICS = ("mssd", "mspd", "add", "adi")
 THRESHOLDS = tuple(round(0.05 * i, 2) for i in range(1, 11))           # 0.05 ... 0.50: the BOP19 sweep of theta and of tau / diameter
 MSPD_THRESHOLDS = tuple(5.0 * i for i in range(1, 11))                 # px at an image width of 640
@@ -215,6 +224,161 @@ def pose_errors(meshes: MeshBank, symmetries: Optional[SymmetryBank], obj_ids, p
     out = op_pose_errors(meshes.verts, [r[0] for r in vr], [r[1] for r in vr], max(r[1] for r in vr), symmetries.syms,
                          [r[0] for r in sr], [r[1] for r in sr], max(r[1] for r in sr), est, gt, Kp, want)
     return {name: t.reshape(B, k) for name, t in out.items()}
+
+
+# ---- translation from a 2D box, and its correction from depth ------------------------------------------------------------------------
+def op_fit_translation(verts: torch.Tensor, vert_off, vert_cnt, max_verts: int, R, K, box, max_iters: int = 32, tol_scale: float = 1e-9,
+                       tol_px: float = 1e-6) -> Dict[str, torch.Tensor]:
+    """nope_op_fit_translation as it is declared: verts (V, 3) f32 on the device, ranges per pose (P,), R (P, 3, 3), K (P, 3, 3), box (P, 4)
+    (u0, v0, u1, v1).  Returns {"t": (P, 3) f64, "residual": (P,) f64 pixels, "iters": (P,) int32, "status": (P,) int32 of FIT_* bits}.
+    Nothing is checked here that the entry checks."""
+    hip.require_device(verts)
+    dev = verts.device
+    Rt, Kt, bx = _as_f64(R, dev).reshape(-1, 3, 3), _as_f64(K, dev).reshape(-1, 3, 3), _as_f64(box, dev).reshape(-1, 4)
+    P = Rt.shape[0]
+    vo, vc = _i32(vert_off, dev), _i32(vert_cnt, dev)
+    if verts.dtype != torch.float32 or not verts.is_contiguous():
+        raise hip.NopeError(f"fit_translation: verts {verts.dtype}: contiguous f32 (V, 3) expected")
+    if Kt.shape[0] != P or bx.shape[0] != P or vo.numel() != P or vc.numel() != P:
+        raise hip.NopeError(f"fit_translation: {P} rotations, K {tuple(Kt.shape)}, box {tuple(bx.shape)}, ranges {[vo.numel(), vc.numel()]}")
+    out = {"t": torch.empty((P, 3), dtype=torch.float64, device=dev), "residual": torch.empty(P, dtype=torch.float64, device=dev),
+           "iters": torch.empty(P, dtype=torch.int32, device=dev), "status": torch.empty(P, dtype=torch.int32, device=dev)}
+    if P:
+        l = hip.lib()
+        l.check(l.dll.nope_op_fit_translation(verts.data_ptr(), verts.shape[0], vo.data_ptr(), vc.data_ptr(), int(max_verts), Rt.data_ptr(),
+                                              Kt.data_ptr(), bx.data_ptr(), P, int(max_iters), float(tol_scale), float(tol_px),
+                                              out["t"].data_ptr(), out["residual"].data_ptr(), out["iters"].data_ptr(),
+                                              out["status"].data_ptr(), hip._stream(verts)), "nope_op_fit_translation")
+    return out
+
+
+def _u8(x, device) -> torch.Tensor:
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))
+    t = t.to(device)
+    return (t if t.dtype == torch.uint8 else (t != 0).to(torch.uint8)).contiguous()
+
+
+def op_mask_boxes(mask: torch.Tensor):
+    """nope_op_mask_boxes: mask (B, H, W) (uint8, or anything whose non-zero pixels count) -> (box (B, 4) f64 = (xmin, ymin, xmax + 1,
+    ymax + 1), NaN for an empty mask; count (B,) int32)."""
+    hip.require_device(mask)
+    if mask.dim() != 3:
+        raise hip.NopeError(f"mask_boxes: mask {tuple(mask.shape)}: expected (B, H, W)")
+    m = _u8(mask, mask.device)
+    B, H, W = m.shape
+    box = torch.empty((B, 4), dtype=torch.float64, device=m.device)
+    count = torch.empty(B, dtype=torch.int32, device=m.device)
+    if B:
+        l = hip.lib()
+        l.check(l.dll.nope_op_mask_boxes(m.data_ptr(), B, H, W, box.data_ptr(), count.data_ptr(), hip._stream(m)), "nope_op_mask_boxes")
+    return box, count
+
+
+def op_depth_shift(depth_test: torch.Tensor, depth_est: torch.Tensor, tau: float, mask: Optional[torch.Tensor] = None):
+    """nope_op_depth_shift: depth_test (B, H, W), depth_est (B, k, H, W) f32 mm, mask (B, H, W) or None -> (shift (B, k) f64: the mean of
+    test - est over the pixels where both are > 0, the mask is set and |test - est| <= tau, NaN without such a pixel; count (B, k) int32)."""
+    hip.require_device(depth_est)
+    dev = depth_est.device
+    f32 = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))).to(device=dev, dtype=torch.float32).contiguous()
+    dt, de = f32(depth_test), f32(depth_est)
+    if de.dim() != 4 or dt.shape != de.shape[:1] + de.shape[2:]:
+        raise hip.NopeError(f"depth_shift: depth_test {tuple(dt.shape)}, depth_est {tuple(de.shape)}: expected (B,H,W), (B,k,H,W)")
+    B, k, H, W = de.shape
+    if not 1 <= k <= 16:
+        raise hip.NopeError(f"depth_shift: k = {k} estimates per query (1..16)")
+    m = None
+    if mask is not None:
+        m = _u8(mask, dev)
+        if tuple(m.shape) != (B, H, W):
+            raise hip.NopeError(f"depth_shift: mask {tuple(m.shape)} for depth_test {tuple(dt.shape)}")
+    shift = torch.empty((B, k), dtype=torch.float64, device=dev)
+    count = torch.empty((B, k), dtype=torch.int32, device=dev)
+    if B:
+        l = hip.lib()
+        ws = torch.empty(int(l.dll.nope_op_depth_shift_workspace_bytes(B, k, H, W)), dtype=torch.uint8, device=dev)
+        l.check(l.dll.nope_op_depth_shift(dt.data_ptr(), de.data_ptr(), hip._ptr(m), B, k, H, W, float(tau), shift.data_ptr(), count.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), hip._stream(de)), "nope_op_depth_shift")
+    return shift, count
+
+
+def _batch_K(K, B: int, dev) -> torch.Tensor:
+    Kt = _as_f64(K, dev)
+    if Kt.dim() == 2:
+        Kt = Kt.reshape(1, 3, 3).expand(B, 3, 3).contiguous()
+    return Kt
+
+
+def estimate_translation(meshes: MeshBank, obj_ids, pred_R, K, box=None, mask=None, max_iters: int = 32, tol_scale: float = 1e-9,
+                         tol_px: float = 1e-6) -> Dict[str, torch.Tensor]:
+    """The translation under which the projected box of mesh obj_ids[b] at rotation pred_R[b, j] is the detected box of query b
+    (op_fit_translation).  obj_ids (B,); pred_R (B, k, 3, 3); K (B, 3, 3) or (3, 3); exactly one of box (B, 4) =
+    (u0, v0, u1, v1) in the rasteriser's image coordinates and mask (B, H, W), whose box op_mask_boxes takes.  Returns {"t": (B, k, 3) f64
+    mm, "residual": (B, k) f64 pixels (how well the rotation explains the box's aspect), "iters", "status": (B, k) int32 of FIT_* bits}.
+    A candidate whose status is not 0 has no usable t (NaN, or not converged).  No host synchronisation."""
+    if (box is None) == (mask is None):
+        raise ValueError("estimate_translation: exactly one of box (B, 4) and mask (B, H, W) must be given")
+    dev = meshes.device
+    pred_R = _as_f64(pred_R, dev)
+    if pred_R.dim() != 4 or tuple(pred_R.shape[2:]) != (3, 3):
+        raise hip.NopeError(f"estimate_translation: pred_R {tuple(pred_R.shape)}: expected (B, k, 3, 3)")
+    B, k = pred_R.shape[:2]
+    ids = [int(o) for o in (obj_ids.tolist() if hasattr(obj_ids, "tolist") else obj_ids)]
+    Kt = _batch_K(K, B, dev)
+    if mask is not None:
+        box = op_mask_boxes(mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.asarray(mask)).to(dev))[0]
+    bx = _as_f64(box, dev)
+    if len(ids) != B or tuple(Kt.shape) != (B, 3, 3) or tuple(bx.shape) != (B, 4):
+        raise hip.NopeError(f"estimate_translation: {len(ids)} obj_ids, pred_R {tuple(pred_R.shape)}, K {tuple(Kt.shape)}, box {tuple(bx.shape)}")
+    vr = [r for r in meshes.vert_ranges(ids) for _ in range(k)]
+    if B * k == 0:
+        return {"t": torch.empty((B, k, 3), dtype=torch.float64, device=dev), "residual": torch.empty((B, k), dtype=torch.float64, device=dev),
+                "iters": torch.empty((B, k), dtype=torch.int32, device=dev), "status": torch.empty((B, k), dtype=torch.int32, device=dev)}
+    out = op_fit_translation(meshes.verts, [r[0] for r in vr], [r[1] for r in vr], max(r[1] for r in vr), pred_R.reshape(B * k, 3, 3),
+                             Kt.reshape(B, 1, 3, 3).expand(B, k, 3, 3).reshape(B * k, 3, 3), bx.reshape(B, 1, 4).expand(B, k, 4).reshape(B * k, 4),
+                             max_iters, tol_scale, tol_px)
+    return {name: t.reshape((B, k) + tuple(t.shape[1:])) for name, t in out.items()}
+
+
+def refine_translation_depth(meshes: MeshBank, obj_ids, pred_R, t, K, depth_test, tau: float, mask=None, rounds: int = 2,
+                             min_count: int = 1) -> Dict[str, torch.Tensor]:
+    """The distance of k estimates per query corrected from a depth image.  Per round: the estimates are rendered at (pred_R, t)
+    (vsd.render_depth), op_depth_shift gives the mean of test - rendered over the inliers within tau (mm; no default: nothing here is
+    tuned), and t <- t (t_z + shift) / t_z: a move along the viewing ray, which keeps the box centre.  t (B, k, 3); depth_test (B, H, W)
+    mm; mask (B, H, W) or None restricts the inliers to the detection.  Where a round finds fewer than min_count inliers (or none: a NaN
+    shift) t is kept and ST_DEPTH_FEW is set; where t cannot be rendered (a NaN, t_z <= 0, a triangle at Z <= znear) or the corrected
+    t_z would not be positive, t is kept and ST_DEPTH_POSE is set.  Returns {"t": (B, k, 3) f64, "shift": (B, k) f64 of the last round,
+    "count": (B, k) int32 of the last round, "status": (B, k) int32}.  No host synchronisation."""
+    from . import vsd
+    dev = meshes.device
+    pred_R, tt = _as_f64(pred_R, dev), _as_f64(t, dev)
+    if pred_R.dim() != 4 or tuple(pred_R.shape[2:]) != (3, 3) or tt.numel() != 3 * pred_R.shape[0] * pred_R.shape[1]:
+        raise hip.NopeError(f"refine_translation_depth: pred_R {tuple(pred_R.shape)}, t {tuple(tt.shape)}: expected (B, k, 3, 3), (B, k, 3)")
+    B, k = pred_R.shape[:2]
+    tt = tt.reshape(B, k, 3).clone()
+    ids = [int(o) for o in (obj_ids.tolist() if hasattr(obj_ids, "tolist") else obj_ids)]
+    dtest = (depth_test if isinstance(depth_test, torch.Tensor) else torch.from_numpy(np.asarray(depth_test))).to(device=dev, dtype=torch.float32)
+    if len(ids) != B or dtest.dim() != 3 or dtest.shape[0] != B:
+        raise hip.NopeError(f"refine_translation_depth: {len(ids)} obj_ids, pred_R {tuple(pred_R.shape)}, depth_test {tuple(dtest.shape)}")
+    H, W = dtest.shape[-2:]
+    Kp = _batch_K(K, B, dev).reshape(B, 1, 3, 3).expand(B, k, 3, 3).reshape(B * k, 3, 3)
+    status = torch.zeros((B, k), dtype=torch.int32, device=dev)
+    shift = torch.full((B, k), float("nan"), dtype=torch.float64, device=dev)
+    count = torch.zeros((B, k), dtype=torch.int32, device=dev)
+    if B * k == 0:
+        return {"t": tt, "shift": shift, "count": count, "status": status}
+    rep = [o for o in ids for _ in range(k)]
+    for _ in range(int(rounds)):
+        depth, skipped = vsd.render_depth(meshes, rep, compose_poses(pred_R, tt).reshape(B * k, 4, 4), Kp, H, W, return_skipped=True)
+        shift, count = op_depth_shift(dtest, depth.reshape(B, k, H, W), tau, mask)
+        tz = tt[..., 2]
+        new_z = tz + shift
+        bad_pose = (skipped.reshape(B, k) != 0) | ~torch.isfinite(tt).all(dim=-1) | ~(tz > 0)
+        few = ~bad_pose & ((count < int(min_count)) | torch.isnan(shift))
+        bad_pose = bad_pose | (~few & ~(new_z > 0))
+        keep = bad_pose | few
+        status = status | torch.where(few, ST_DEPTH_FEW, 0).to(torch.int32) | torch.where(bad_pose, ST_DEPTH_POSE, 0).to(torch.int32)
+        tt = torch.where(keep[..., None], tt, tt * (new_z / tz)[..., None])
+    return {"t": tt, "shift": shift, "count": count, "status": status}
 
 
 # ---- recalls --------------------------------------------------------------------------------------------------------------------------

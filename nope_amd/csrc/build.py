@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["kernels_gemm_dma_bf16_variants.hip", "kernels_gemm_dma_f32.hip", "kernels_gemm_dma_bf16.hip", "kernels_gemm_dma_f16.hip", "kernels_gemm_dma_bf16x3.hip",      # (longest first)
            "kernels_gemm.hip", "kernels_gemm_pp.hip", "kernels_gemm_small.hip", "kernels_gemm_stream.hip", "kernels_norm.hip", "kernels_attn.hip", "kernels_misc.hip", "kernels_retrieval.hip", "kernels_metric.hip", "kernels_modes.hip", "kernels_search.hip", "kernels_multiref.hip", "kernels_robust.hip", "kernels_refine.hip",
-           "kernels_encoder.hip", "kernels_ldm.hip", "kernels_vsd.hip", "kernels_poseerr.hip", "kernels_vis.hip", "unet_runtime.hip", "encoder_runtime.hip", "ldm_runtime.hip", "gd_runtime.hip", "vae_runtime.hip", "capi.hip"]
+           "kernels_encoder.hip", "kernels_ldm.hip", "kernels_vsd.hip", "kernels_poseerr.hip", "kernels_posefit.hip", "kernels_vis.hip", "unet_runtime.hip", "encoder_runtime.hip", "ldm_runtime.hip", "gd_runtime.hip", "vae_runtime.hip", "capi.hip"]
 LIB = os.path.join(HERE, "libnope_hip.so")
 ARCH = "gfx950"
 
@@ -54,7 +54,7 @@ def _record_usage(src: str, remarks: str, objdir: str) -> None:
     with open(os.path.join(objdir, src + ".usage.txt"), "w") as f:
         for r in rows:
             f.write(" ".join(f"{k}={v}" for k, v in r.items()) + "\n")
-    bad = [r["kernel"] for r in rows if r.get("ScratchSize", 0) > 0 and any(t in r["kernel"] for t in ("conv_gemm", "conv3x3", "sim_reg", "mr_reg", "mr_lds", "rb_reg", "rb_gen", "gn_", "linattn", "pe_point", "pe_sym", "diam_kernel"))]
+    bad = [r["kernel"] for r in rows if r.get("ScratchSize", 0) > 0 and any(t in r["kernel"] for t in ("conv_gemm", "conv3x3", "sim_reg", "mr_reg", "mr_lds", "rb_reg", "rb_gen", "gn_", "linattn", "pe_point", "pe_sym", "diam_kernel", "fit_kernel", "dshift_kernel"))]
     if bad:
         raise RuntimeError(f"{src}: kernels use scratch memory (register spill / runtime-indexed array): {bad}")
 

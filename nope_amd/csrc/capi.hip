@@ -257,6 +257,24 @@ int nope_op_mesh_diameter(const float* verts, int V, const int* vert_off, const 
     return launch_mesh_diameter(verts, V, vert_off, vert_cnt, n_obj, max_verts, diameter, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int nope_op_fit_translation(const float* verts, int V, const int* vert_off, const int* vert_cnt, int max_verts, const double* R, const double* K,
+                            const double* box, int P, int max_iters, double tol_scale, double tol_px, double* t, double* residual, int* iters,
+                            int* status, nope_stream_t stream) {
+    return launch_fit_translation(verts, V, vert_off, vert_cnt, max_verts, R, K, box, P, max_iters, tol_scale, tol_px, t, residual, iters, status,
+                                  (hipStream_t)stream);
+}
+
+int nope_op_mask_boxes(const unsigned char* mask, int B, int H, int W, double* box, int* count, nope_stream_t stream) {
+    return launch_mask_boxes(mask, B, H, W, box, count, (hipStream_t)stream);
+}
+
+size_t nope_op_depth_shift_workspace_bytes(int B, int k, int H, int W) { return depth_shift_workspace_bytes(B, k, H, W); }
+
+int nope_op_depth_shift(const float* depth_test, const float* depth_est, const unsigned char* mask, int B, int k, int H, int W, double tau,
+                        double* shift, int* count, void* workspace, size_t workspace_bytes, nope_stream_t stream) {
+    return launch_depth_shift(depth_test, depth_est, mask, B, k, H, W, tau, shift, count, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int nope_op_vis_grid(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, void* grid_f16, nope_stream_t stream) {
     return launch_vis_grid(cols, n_cols, B, F, H, W, static_cast<f16_t*>(grid_f16), (hipStream_t)stream);
 }

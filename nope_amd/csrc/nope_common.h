@@ -623,6 +623,14 @@ int launch_pose_errors(const float* verts, int V, const int* vert_off, const int
 size_t mesh_diameter_workspace_bytes(int n_obj, int max_verts);
 int launch_mesh_diameter(const float* verts, int V, const int* vert_off, const int* vert_cnt, int n_obj, int max_verts, double* diameter, void* ws,
                          size_t ws_bytes, hipStream_t s);
+// translation from a box, mask boxes, depth shift (kernels_posefit.hip)
+int launch_fit_translation(const float* verts, int V, const int* vert_off, const int* vert_cnt, int max_verts, const double* R, const double* K,
+                           const double* box, int P, int max_iters, double tol_scale, double tol_px, double* t, double* residual, int* iters,
+                           int* status, hipStream_t s);
+int launch_mask_boxes(const unsigned char* mask, int B, int H, int W, double* box, int* count, hipStream_t s);
+size_t depth_shift_workspace_bytes(int B, int k, int H, int W);
+int launch_depth_shift(const float* dtest, const float* dest, const unsigned char* mask, int B, int k, int H, int W, double tau, double* shift,
+                       int* count, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_vis_grid(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, f16_t* grid, hipStream_t s);
 int launch_vis_sheet(const nope_vis_column* cols, int n_cols, int B, int F, int H, int W, int tile, int nrow, int padding,
                      unsigned char* sheet, hipStream_t s);

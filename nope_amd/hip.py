@@ -16,7 +16,7 @@ import torch
 
 F32, BF16, F16, BF16X3 = 0, 1, 2, 3      # BF16X3: compute mode only (f32 storage, three bf16 MFMA passes per product)
 F16X2 = 4                                # compute mode only: BF16X3, but the ping-pong launches (tap-resident 3x3, per-tap 1x1 / up / down) run one f16 + one MX-fp8 MFMA pass (include/nope_hip.h)
-ABI_VERSION = 24                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
+ABI_VERSION = 25                         # NOPE_ABI_VERSION of include/nope_hip.h these ctypes structs mirror
 CONV_PLAIN, CONV_UP2, CONV_DOWN2, CONV_UP2P, CONV_STRIDE2, CONV_STRIDE2_PAD01 = 0, 1, 2, 3, 4, 5
 ERR_RANGE, ERR_RANGE_F16 = -7, -8        # nope_unet_x2_range_check (include/nope_hip.h)
 
@@ -136,6 +136,10 @@ _PROTOS = {
     "nope_op_pose_errors": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nope_op_mesh_diameter_workspace_bytes": (_sz, [_i, _i]),
     "nope_op_mesh_diameter": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "nope_op_fit_translation": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "nope_op_mask_boxes": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "nope_op_depth_shift_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "nope_op_depth_shift": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "nope_op_vis_grid": (_i, [C.POINTER(VisColumn), _i, _i, _i, _i, _i, _vp, _vp]),
     "nope_op_vis_sheet": (_i, [C.POINTER(VisColumn), _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "nope_unet_graph_limit": (_i, [_vp, C.c_longlong]),

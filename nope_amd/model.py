@@ -791,18 +791,29 @@ class PoseConditional(nn.Module):
         return self.tless_models_info
 
     @torch.no_grad()
-    def eval_bop(self, batch, data_name, save_path=None):
+    def eval_bop(self, batch, data_name, save_path=None, translation="gt", depth_tau=None):
         """The T-LESS evaluation under the BOP benchmark's errors: eval_vsd's batch, forward pass and retrieval, then MSSD, MSPD, ADD and
-        ADI of the retrieved rotations (nope_amd.bop.pose_errors, ground-truth translation) and VSD over tau in 0.05 ... 0.50 times the
+        ADI of the retrieved rotations (nope_amd.bop.pose_errors; `translation` below) and VSD over tau in 0.05 ... 0.50 times the
         diameter (delta 15, step cost, bop19) from ONE rendering.  Returns {f"loss/val_{data_name}", and nope_amd.bop.bop_scores' recalls:
         AR_MSSD, AR_MSPD, AR_VSD, AR, ADD / ADD-S at 0.1 d, for the top 1 / 3 / 5}.  Symmetries and diameters come from load_models_info;
         without it the symmetry sets are the identity and the diameters are measured on the meshes (bop.mesh_diameters).  save_path:
         np.savez of the error tables.  No reference counterpart (eval_vsd is the reference's evaluation); nothing is claimed about
-        accuracy on real data."""
+        accuracy on real data.
+        translation: "gt" -- the estimates take the ground-truth translation (the rotation retriever alone is measured);
+        "box" -- each of the k rotations gets the translation that fits the detection, batch["box"] (B, 4) = (u0, v0, u1, v1) or
+        batch["mask"] (B, H, W) (bop.estimate_translation): a 6D pose of the library's own; "box+depth" -- and its distance is corrected
+        on batch["depth"] within depth_tau mm (bop.refine_translation_depth, inliers inside batch["mask"] if there is one).  A candidate
+        whose translation status is not 0 is a miss: +inf in every error table.  The saved tables then hold t, residual and status too."""
         import numpy as np
         from . import bop, vsd
         if getattr(self, "tless_cad", None) is None:
             raise RuntimeError("eval_bop: no meshes: call load_mesh(cad_dir) first (model.py:378)")
+        if translation not in ("gt", "box", "box+depth"):
+            raise ValueError(f"eval_bop: translation {translation!r} (known: 'gt', 'box', 'box+depth')")
+        if translation != "gt" and batch.get("box") is None and batch.get("mask") is None:
+            raise ValueError(f"eval_bop: translation={translation!r} needs the detection: batch['box'] (B, 4) or batch['mask'] (B, H, W)")
+        if translation == "box+depth" and depth_tau is None:
+            raise ValueError("eval_bop: translation='box+depth' needs depth_tau (mm): nothing here is tuned")
         query, reference = batch["query"], batch["reference"]
         loss = self.forward(query=query, relativeR=batch["gt_relativeR"], reference=reference)
         pred_feat, _, _ = self.generate_templates(reference=reference, all_relativeR=batch["all_relativeR"])
@@ -826,10 +837,28 @@ class PoseConditional(nn.Module):
             if getattr(self, "_tless_diameters", None) is None or self._tless_diameters[0] is not self.tless_cad:
                 self._tless_diameters = (self.tless_cad, bop.mesh_diameters(self.tless_cad))
             diam = np.array([self._tless_diameters[1][o] for o in obj_ids])
+        pred_t = fit = miss = None
+        if translation != "gt":
+            cad_dev = self.tless_cad.device
+            if batch.get("box") is not None:
+                fit = bop.estimate_translation(self.tless_cad, obj_ids, retrieved_R, batch["intrinsic"], box=batch["box"])
+            else:
+                fit = bop.estimate_translation(self.tless_cad, obj_ids, retrieved_R, batch["intrinsic"], mask=batch["mask"])
+            status = fit["status"]
+            gt_t = vsd._as_f64(batch["query_translation"], cad_dev).reshape(B, 1, 3)
+            # a candidate without a usable translation is a miss below; it is rendered at the ground truth's, which can be rendered
+            pred_t = torch.where((status != 0)[..., None], gt_t, fit["t"])
+            if translation == "box+depth":
+                dep = bop.refine_translation_depth(self.tless_cad, obj_ids, retrieved_R, pred_t, batch["intrinsic"], depth_test, depth_tau,
+                                                   mask=batch.get("mask"))
+                status = status | dep["status"]
+                pred_t = torch.where((status != 0)[..., None], gt_t, dep["t"])
+            fit = dict(fit, t=torch.where((status != 0)[..., None], fit["t"], pred_t), status=status)
+            miss = status != 0
         errors = bop.pose_errors(self.tless_cad, getattr(self, "tless_symmetries", None), obj_ids, retrieved_R, batch["query_pose"],
-                                 batch["query_translation"], batch["intrinsic"])
+                                 batch["query_translation"], batch["intrinsic"], pred_t=pred_t)
         _, d_gt, d_est = vsd.vsd_error(depth_test, self.tless_cad, obj_ids, retrieved_R, batch["query_pose"], batch["query_translation"],
-                                       batch["intrinsic"], return_depth=True)
+                                       batch["intrinsic"], return_depth=True, pred_t=pred_t)
         dev = d_est.device
         dtest = (depth_test if isinstance(depth_test, torch.Tensor) else torch.from_numpy(np.asarray(depth_test))).to(dev)
         # tau differs per query (a fraction of its object's diameter): queries of one diameter share a launch
@@ -842,11 +871,17 @@ class PoseConditional(nn.Module):
             for ti, frac in enumerate(bop.THRESHOLDS):
                 vsd_stack[ti, sel] = vsd.vsd_from_depth(dtest[sel], d_gt[sel].contiguous(), d_est[sel].contiguous(), Kt[sel].contiguous(),
                                                         delta=15, tau=frac * d)
+        extra = {}
+        if miss is not None:
+            inf = torch.tensor(float("inf"), dtype=torch.float64, device=dev)
+            errors = {m: (torch.where(miss.to(e.device), inf.to(e.device), e) if m in bop.METRICS else e) for m, e in errors.items()}
+            vsd_stack = torch.where(miss.to(dev)[None], inf, vsd_stack)
+            extra = {name: fit[name].cpu().numpy() for name in ("t", "residual", "status")}
         width = depth_test.shape[-1]
         scores = {f"loss/val_{data_name}": float(loss)}
         scores.update(bop.bop_scores(errors, diam, width, vsd_errors=vsd_stack))
         if save_path is not None:
-            np.savez(save_path, vsd=vsd_stack.cpu().numpy(), diameter=diam, **{m: errors[m].cpu().numpy() for m in bop.METRICS})
+            np.savez(save_path, vsd=vsd_stack.cpu().numpy(), diameter=diam, **{m: errors[m].cpu().numpy() for m in bop.METRICS}, **extra)
         return scores
 
     @torch.no_grad()

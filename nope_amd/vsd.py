@@ -189,10 +189,12 @@ def _as_f64(x, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float64).contiguous()
 
 
-def render_depth(bank: MeshBank, obj_ids: Sequence[int], poses, K, height: int, width: int) -> torch.Tensor:
+def render_depth(bank: MeshBank, obj_ids: Sequence[int], poses, K, height: int, width: int, return_skipped: bool = False):
     """Depth maps (P, H, W) f32 in mm of mesh obj_ids[p] under poses[p] (4x4 object-to-camera, OpenCV axes) with intrinsics K[p] (3x3;
     one (3, 3) K serves every pose): pyrenderer(..., DEPTH_ONLY) of vsd.py:25-54 on the device.  Pixel (x, y) samples the image point
-    (x + 0.5, y + 0.5).  A pose that puts a vertex at Z <= 0.05 (pyrender's znear) raises: the renderer skips such triangles."""
+    (x + 0.5, y + 0.5).  A pose that puts a vertex at Z <= 0.05 (pyrender's znear) raises: the renderer skips such triangles.
+    return_skipped: nothing is raised and nothing waits for the device; (depth, skipped (P,) int32: the triangles each pose skipped) is
+    returned and the caller decides (a NaN pose skips every triangle)."""
     dev = bank.device
     hip.require_device(bank.verts)
     obj_ids = [int(o) for o in (obj_ids.tolist() if hasattr(obj_ids, "tolist") else obj_ids)]
@@ -205,7 +207,7 @@ def render_depth(bank: MeshBank, obj_ids: Sequence[int], poses, K, height: int, 
         raise hip.NopeError(f"render_depth: {P} obj_ids, poses {tuple(poses.shape)}, K {tuple(K.shape)}")
     depth = torch.empty((P, height, width), dtype=torch.float32, device=dev)
     if P == 0:
-        return depth
+        return (depth, torch.empty(0, dtype=torch.int32, device=dev)) if return_skipped else depth
     rng = bank.ranges(obj_ids)
     off = torch.tensor([r[0] for r in rng], dtype=torch.int32).to(dev)
     cnt = torch.tensor([r[1] for r in rng], dtype=torch.int32).to(dev)
@@ -216,6 +218,8 @@ def render_depth(bank: MeshBank, obj_ids: Sequence[int], poses, K, height: int, 
     l.check(l.dll.nope_op_render_depth(bank.verts.data_ptr(), bank.verts.shape[0], bank.faces.data_ptr(), bank.faces.shape[0], off.data_ptr(),
                                        cnt.data_ptr(), max_faces, poses.data_ptr(), K.data_ptr(), P, height, width, depth.data_ptr(),
                                        skipped.data_ptr(), ws.data_ptr(), ws.numel(), hip._stream(depth)), "nope_op_render_depth")
+    if return_skipped:
+        return depth, skipped
     sk = skipped.cpu()
     if bool((sk != 0).any()):
         bad = [(p, int(sk[p])) for p in range(P) if sk[p] != 0]
@@ -268,13 +272,14 @@ def compose_poses(R, t) -> torch.Tensor:
 
 
 def vsd_error(depth_test, meshes: MeshBank, obj_ids, pred_R, gt_R, gt_t, K, delta=15, tau=20, cost_type="step",
-              use_gt_translation=True, visib_mode="bop19", return_depth=False):
+              use_gt_translation=True, visib_mode="bop19", return_depth=False, pred_t=None):
     """VSD errors (B, k) f64 of k predicted rotations per query -- vsd_obj (vsd.py:57-132), batched over B queries.
     depth_test (B, H, W) in mm (load_depth); obj_ids (B,); pred_R (B, k, 3, 3); gt_R (B, 3, 3); gt_t (B, 3, 1) or (B, 3) in mm;
     K (B, 3, 3).  The predictions take the ground-truth translation (use_gt_translation=True, vsd.py:84-87; False raises
-    NotImplementedError as the reference does).  The B (1 + k) depth maps are rendered in one launch.  return_depth: also return
-    (depth_gt (B,H,W), depth_est (B,k,H,W))."""
-    if not use_gt_translation:
+    NotImplementedError as the reference does) unless pred_t (B, k, 3) is given (nope_amd.bop.estimate_translation): then the
+    estimates are rendered at it, and it has to be renderable (finite, every vertex beyond znear).  The B (1 + k) depth maps are rendered
+    in one launch.  return_depth: also return (depth_gt (B,H,W), depth_est (B,k,H,W))."""
+    if pred_t is None and not use_gt_translation:
         raise NotImplementedError
     if cost_type not in _COST:
         raise ValueError("Unknown pixel matching cost.")
@@ -289,7 +294,14 @@ def vsd_error(depth_test, meshes: MeshBank, obj_ids, pred_R, gt_R, gt_t, K, delt
     if Kt.dim() == 2:
         Kt = Kt.reshape(1, 3, 3).expand(B, 3, 3).contiguous()
     gt_pose = compose_poses(gt_R, gt_t)                                              # (B, 4, 4)
-    pred_pose = compose_poses(pred_R, gt_t.reshape(B, 1, 3).expand(B, k, 3))         # (B, k, 4, 4), translation of the ground truth
+    if pred_t is None:
+        pt = gt_t.reshape(B, 1, 3).expand(B, k, 3)                                   # translation of the ground truth
+    else:
+        pt = _as_f64(pred_t, dev)
+        if pt.numel() != 3 * B * k:
+            raise hip.NopeError(f"vsd_error: pred_t {tuple(pt.shape)} for pred_R {tuple(pred_R.shape)}")
+        pt = pt.reshape(B, k, 3)
+    pred_pose = compose_poses(pred_R, pt)                                            # (B, k, 4, 4)
     ids = [int(o) for o in (obj_ids.tolist() if hasattr(obj_ids, "tolist") else obj_ids)]
     all_pose = torch.cat([gt_pose.reshape(B, 1, 4, 4), pred_pose], dim=1).reshape(B * (1 + k), 4, 4)
     all_K = Kt.reshape(B, 1, 3, 3).expand(B, 1 + k, 3, 3).reshape(B * (1 + k), 3, 3)
